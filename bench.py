@@ -13,9 +13,12 @@ data-parallel across ranks with no data-path collective in the forward (weak sca
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel (largest share of the
-step's GPU time), timed live with HIP events on the launch stream inside the timed region;
-`cpu_baseline` is the CPU oracle (a port: TensorFlow cannot run here) on the host cores, N=1 only.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps forward steps and prints
+the headline (`value`, `ms_per_step`, ...); `--dump-outputs DIR` also writes what the last timed step
+returned.  `--full` adds everything else the line has carried: `roofline` is for the dominant kernel
+(largest share of the step's GPU time), timed live with HIP events on the launch stream inside the
+timed region; `cpu_baseline` is the CPU oracle (a port: TensorFlow cannot run here) on the host cores,
+N=1 only; and the sub-lines beside the headline.
 """
 import argparse
 import json
@@ -76,7 +79,7 @@ def live_pmc_traffic(label, args, tune_file):
         for counter in ('FETCH_SIZE', 'WRITE_SIZE'):
             out = os.path.join(td, counter)
             cmd = [rp, '--pmc', counter, '--kernel-trace', '--output-format', 'csv', '-d', out, '--', sys.executable,
-                   os.path.join(ROOT, 'bench.py'), '--headline-only', '--steps', '4', '--warmup', '2', '--precision', args.precision,
+                   os.path.join(ROOT, 'bench.py'), '--full', '--headline-only', '--steps', '4', '--warmup', '2', '--precision', args.precision,
                    '--uv', str(args.uv), '--cam', str(args.cam), '--frames', str(args.frames), '--k', str(args.k),
                    '--depth', str(args.depth), '--warp', args.warp, '--tune-cache', tune_file]
             env = dict(os.environ, TMPDIR='/tmp')
@@ -235,8 +238,20 @@ def parse():
     ap.add_argument('--train-graph', action='store_true',
                     help='train step: replay forward + loss + backward as one hipGraph (trainvali.GraphedTrainStep); measured '
                          'slower than eager launches on ROCm 7.0 (5.15 vs 4.75 ms), so off by default')
-    ap.add_argument('--headline-only', action='store_true', help='only the timed forward (profiling runs): no loader-inclusive legs, train steps or CPU leg')
-    ap.add_argument('--pipelined', action='store_true', help='with --headline-only: also the several-batches-in-flight sub-line')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: roofline / whole-pass figures (per-launch survey, dominant launch timed in the '
+                         'timed region, live PMC passes), loader-inclusive legs, train steps, released shapes, config 5, 64-ch stress, '
+                         'other precisions, inference mode, pipelined legs, CPU baseline.  Without it the run sets up, warms up, times '
+                         '--steps forward steps and prints the headline; a leg asked for by its own flag (--per-op, --per-op-train, '
+                         '--pipelined, --train-steps N > 0) still runs')
+    ap.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                    help="after the timed steps, write what the last one's Model.call returned as DIR/<name>.npy (float32): "
+                         "pred_camspc, base_camspc and pred (UV space); an array of more than 2^22 elements as a fixed seeded "
+                         "sample, DIR/<name>_sample.npy (pred at the default workload).  Plan-time tile choices are made by timing "
+                         "and may round differently from run to run; runs given the same --tune-cache agree bit for bit")
+    ap.add_argument('--headline-only', action='store_true', help='with --full: only the timed forward and its roofline figures (profiling runs): '
+                    'no loader-inclusive legs, train steps or CPU leg')
+    ap.add_argument('--pipelined', action='store_true', help='also the several-batches-in-flight sub-line')
     ap.add_argument('--no-released-shapes', action='store_true', help='skip the config 1 / config 2 sub-lines (released .ini shapes)')
     ap.add_argument('--per-op-train', action='store_true', help='per-launch timing table of one train step (stderr)')
     ap.add_argument('--no-live-pmc', action='store_true', help='skip the two rocprofv3 --pmc child passes that measure the dominant '
@@ -1180,6 +1195,25 @@ def bench_stress_64ch(device):
     return out
 
 
+DUMP_MAX_ELEMENTS = 1 << 22      # per array: three float32 arrays stay under 64 MB together
+
+
+def dump_outputs(outdir, result):
+    """`--dump-outputs DIR`: what the caller of the last timed `Model.call(batch, 'test')` receives, as float32 .npy files
+    (the inputs are seeded, so two builds run with the same arguments can be compared array by array).  An array of more
+    than DUMP_MAX_ELEMENTS elements is written as `<name>_sample.npy`: the elements at a fixed, seeded set of flat indices
+    (ascending), the same set for every run of the same shape -- at the default workload that is `pred` (4 x 1024^2 x 3)."""
+    import numpy as np
+    pred_camspc, _, _, vis = result
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in (('pred_camspc', pred_camspc), ('base_camspc', vis['base_camspc']), ('pred', vis['pred'])):
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(outdir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def relaunch_multi_rank(n):
     """`python bench.py --gpus N` (N > 1) WITHOUT a torchrun environment: one rank per GPU is the only way this line means
     anything, so the process re-executes itself under `python -m torch.distributed.run` (the launcher the driver uses) and
@@ -1303,63 +1337,75 @@ def main():
         calls[0] += 1
         return model.call(batches[calls[0] % len(batches)], 'test')
 
-    # per-launch survey (outside the timed region) -> dominant kernel
+    # plan set-up (plan-time trials, launch tapes) outside the timed region
     for _ in range(2):
         step()
     if args.tune_cache and not os.path.exists(args.tune_cache) and rank == 0:
         model.plan.save_tuning(args.tune_cache)
-    timer = OpTimer()
-    model.plan.timer = timer
-    for _ in range(3):
-        step()
-    rec = timer.collect()
-    model.plan.timer = None
-    table = sorted(((r[1] / r[0], l, r[2]) for l, r in rec.items()), reverse=True)
-    if args.per_op and rank == 0:
-        tot = sum(t for t, _, _ in table)
-        sys.stderr.write("%-12s %10s %7s %10s %8s\n" % ("launch", "ms", "%", "GB/s", "TFLOP/s"))
-        for t, l, nb in table:
-            sys.stderr.write("%-12s %10.4f %6.1f%% %10.1f %8.1f\n" % (l, t, 100 * t / tot, timer.moved.get(l, nb) / t / 1e6,
-                                                                     timer.flops.get(l, 0) / t / 1e9))
-        sys.stderr.write("sum of launches %.3f ms\n" % tot)
-    dominant = args.dominant or table[0][1]
+    # --full / --per-op: per-launch survey (outside the timed region) -> dominant kernel
+    timer, dominant = OpTimer(), None
+    if args.full or args.per_op:
+        model.plan.timer = timer
+        for _ in range(3):
+            step()
+        rec = timer.collect()
+        model.plan.timer = None
+        table = sorted(((r[1] / r[0], l, r[2]) for l, r in rec.items()), reverse=True)
+        if args.per_op and rank == 0:
+            tot = sum(t for t, _, _ in table)
+            sys.stderr.write("%-12s %10s %7s %10s %8s\n" % ("launch", "ms", "%", "GB/s", "TFLOP/s"))
+            for t, l, nb in table:
+                sys.stderr.write("%-12s %10.4f %6.1f%% %10.1f %8.1f\n" % (l, t, 100 * t / tot, timer.moved.get(l, nb) / t / 1e6,
+                                                                         timer.flops.get(l, 0) / t / 1e9))
+            sys.stderr.write("sum of launches %.3f ms\n" % tot)
+        if args.full:
+            dominant = args.dominant or table[0][1]
 
     for _ in range(args.warmup):
         step()
-    dom = OpTimer(); dom.only = {dominant}
+    # The timed steps run the plan's launches one by one with a timer attached (a plan with a timer does not replay its launch
+    # tape), as they always have; only --full names a launch for it to time, a plain run records no event.
+    dom = OpTimer(); dom.only = {dominant} if dominant else set()
     model.plan.timer = None if args.graph else dom      # events cannot be recorded inside a replayed graph
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step() if args.steps > 0 else None          # (what the caller of the last step receives: --dump-outputs)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if args.graph:                                      # same steps, eager, only to time the dominant launch
+    model.plan.timer = None
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last)
+    del last
+    if args.graph and dominant:                         # same steps, eager, only to time the dominant launch
         model.use_graphs = False
         model.plan.timer = dom
         for _ in range(args.steps):
             step()
         torch.cuda.synchronize()
         model.use_graphs = True
-    model.plan.timer = None
+        model.plan.timer = None
     if world > 1:
         te = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
-    drec = dom.collect()[dominant]
-    dom_ms = drec[1] / drec[0]
-    dom_layerwise = drec[2]                                   # SURVEY 8d layer-wise bytes of what the launch computes
-    dom_bytes = timer.moved.get(dominant, dom_layerwise)      # a fused launch: the bytes it must itself move
-    dom_flops = timer.flops.get(dominant, 0)
+    if dominant:
+        drec = dom.collect()[dominant]
+        dom_ms = drec[1] / drec[0]
+        dom_layerwise = drec[2]                                   # SURVEY 8d layer-wise bytes of what the launch computes
+        dom_bytes = timer.moved.get(dominant, dom_layerwise)      # a fused launch: the bytes it must itself move
+        dom_flops = timer.flops.get(dominant, 0)
+    extra = args.full and not args.headline_only       # the sub-lines beside the headline
 
     # beside the headline: the same forward INCLUDING the loader, fed (a) the way the reference is (float32 batch assembled
     # per step) and (b) store-resident (uint8 frame ids; the front kernel converts in registers)
     with_loader = {}
-    if not args.graph and not args.headline_only:
+    if not args.graph and extra:
         n_l = max(10, min(args.steps, 50))
         for name, resident in (("float32_batch_assembled_per_step", False), ("uint8_store_resident", True)):
             for i in range(2 * len(id_lists)):
@@ -1378,12 +1424,12 @@ def main():
     n_train = max(50, args.steps // 2) if args.train_steps < 0 else args.train_steps
     if world > 1:
         n_train = args.steps            # the data-parallel line IS the train step: exactly --steps timed steps
-    if n_train > 0 and not args.headline_only:
+    if n_train > 0 and not args.headline_only and (args.full or args.train_steps > 0 or args.per_op_train):
         for loss in args.train_loss.split(','):
             train.append(bench_train(args, device, world, rank, n_train, loss))
 
     released = None
-    if not args.headline_only and not args.no_released_shapes and args.uv == 1024:
+    if extra and not args.no_released_shapes and args.uv == 1024:
         if world == 1:
             released = child_leg('--released-shapes-worker', extra=['--steps', str(args.steps), '--depth', str(args.depth)])
             if "error" in released:
@@ -1394,55 +1440,56 @@ def main():
     if rank == 0:
         texels = world * args.frames * args.uv * args.uv * args.steps
         value = texels / elapsed / 1e6
-        ach = dom_bytes / (dom_ms * 1e-3) / 1e9
-        bpt = algorithmic_bytes_per_texel(args.k)
-        # HBM bytes per launch of the dominant kernel: NOT measured in this run (PMC needs rocprofv3 around the process) --
-        # read from the newest committed counter pass; `traffic_source` names the file so a stale figure is visible
-        traffic, traffic_src = pmc_traffic(dominant)
-        if traffic_src is not None:
-            traffic_src = "profiles/%s (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, not this run)" % traffic_src
-        traffic_committed, live_note, live_step_bytes = traffic, None, None
-        if world == 1 and not args.headline_only and not args.no_live_pmc and not args.graph:
-            import tempfile
-            with tempfile.NamedTemporaryFile(suffix='.json', dir='/tmp', delete=False) as tf_:
-                tune_tmp = tf_.name
-            try:
-                os.unlink(tune_tmp)
-                model.plan.save_tuning(tune_tmp)
-                live, live_note = live_pmc_traffic(dominant, args, tune_tmp)
-            finally:
-                if os.path.exists(tune_tmp):
+        if dominant:                                            # --full: the dominant launch's roofs
+            ach = dom_bytes / (dom_ms * 1e-3) / 1e9
+            bpt = algorithmic_bytes_per_texel(args.k)
+            # HBM bytes per launch of the dominant kernel: NOT measured in this run (PMC needs rocprofv3 around the process) --
+            # read from the newest committed counter pass; `traffic_source` names the file so a stale figure is visible
+            traffic, traffic_src = pmc_traffic(dominant)
+            if traffic_src is not None:
+                traffic_src = "profiles/%s (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, not this run)" % traffic_src
+            traffic_committed, live_note, live_step_bytes = traffic, None, None
+            if world == 1 and not args.headline_only and not args.no_live_pmc and not args.graph:
+                import tempfile
+                with tempfile.NamedTemporaryFile(suffix='.json', dir='/tmp', delete=False) as tf_:
+                    tune_tmp = tf_.name
+                try:
                     os.unlink(tune_tmp)
-            if live is not None:
-                live_step_bytes = live['step']
-                traffic = live['dominant']
-                traffic_src = ("measured in this run: two child passes of the timed forward under rocprofv3 --pmc FETCH_SIZE / "
-                               "--pmc WRITE_SIZE (FETCH_SIZE doubled per MI355X_MICROARCH.md, WRITE_SIZE as reported)")
-        if dom_flops / max(dom_bytes, 1) > MFMA_F32_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9):   # above the fp32 ridge
-            tf = dom_flops / (dom_ms * 1e-3) / 1e12
-            roof = {"bound": "mfma", "kernel": dominant, "achieved": round(tf, 2), "peak": MFMA_F32_PEAK_TFLOPS,
-                    "unit": "TFLOP/s", "frac": round(tf / MFMA_F32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    "launch_ms": round(dom_ms, 4), "flops_per_launch": int(dom_flops),
-                    "algorithmic_bytes_per_launch": int(dom_bytes)}
-        else:
-            roof = {"bound": "hbm", "kernel": dominant, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                    "launch_ms": round(dom_ms, 4), "algorithmic_bytes_per_launch": int(dom_bytes)}
-        if traffic is not traffic_committed or live_note:
-            roof["traffic_committed_profile"] = traffic_committed
-            if live_note:
-                roof["traffic_live_pass"] = "not taken: " + live_note
-        if dom_layerwise != dom_bytes:                          # fused launch: also what it replaces, layer by layer
-            roof["layerwise_bytes_replaced"] = int(dom_layerwise)
-        # both roofs of the dominant launch, whichever binds: algorithmic (compulsory) bytes and measured (PMC) bytes over its
-        # duration against the HBM peak; its folded FLOPs against the fp32 matrix peak
-        roof["hbm"] = {"algorithmic_GBps": round(ach, 1), "frac": round(ach / HBM_PEAK_GBS, 4),
-                       "traffic_GBps": round(traffic / (dom_ms * 1e-3) / 1e9, 1) if traffic else None,
-                       "traffic_frac": round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
-                       "peak_GBps": HBM_PEAK_GBS}
-        if dom_flops:
-            tf_ = dom_flops / (dom_ms * 1e-3) / 1e12
-            roof["mfma"] = {"TFLOPs": round(tf_, 2), "frac": round(tf_ / MFMA_F32_PEAK_TFLOPS, 4), "peak_TFLOPs": MFMA_F32_PEAK_TFLOPS}
+                    model.plan.save_tuning(tune_tmp)
+                    live, live_note = live_pmc_traffic(dominant, args, tune_tmp)
+                finally:
+                    if os.path.exists(tune_tmp):
+                        os.unlink(tune_tmp)
+                if live is not None:
+                    live_step_bytes = live['step']
+                    traffic = live['dominant']
+                    traffic_src = ("measured in this run: two child passes of the timed forward under rocprofv3 --pmc FETCH_SIZE / "
+                                   "--pmc WRITE_SIZE (FETCH_SIZE doubled per MI355X_MICROARCH.md, WRITE_SIZE as reported)")
+            if dom_flops / max(dom_bytes, 1) > MFMA_F32_PEAK_TFLOPS * 1e12 / (HBM_PEAK_GBS * 1e9):   # above the fp32 ridge
+                tf = dom_flops / (dom_ms * 1e-3) / 1e12
+                roof = {"bound": "mfma", "kernel": dominant, "achieved": round(tf, 2), "peak": MFMA_F32_PEAK_TFLOPS,
+                        "unit": "TFLOP/s", "frac": round(tf / MFMA_F32_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                        "launch_ms": round(dom_ms, 4), "flops_per_launch": int(dom_flops),
+                        "algorithmic_bytes_per_launch": int(dom_bytes)}
+            else:
+                roof = {"bound": "hbm", "kernel": dominant, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                        "launch_ms": round(dom_ms, 4), "algorithmic_bytes_per_launch": int(dom_bytes)}
+            if traffic is not traffic_committed or live_note:
+                roof["traffic_committed_profile"] = traffic_committed
+                if live_note:
+                    roof["traffic_live_pass"] = "not taken: " + live_note
+            if dom_layerwise != dom_bytes:                          # fused launch: also what it replaces, layer by layer
+                roof["layerwise_bytes_replaced"] = int(dom_layerwise)
+            # both roofs of the dominant launch, whichever binds: algorithmic (compulsory) bytes and measured (PMC) bytes over its
+            # duration against the HBM peak; its folded FLOPs against the fp32 matrix peak
+            roof["hbm"] = {"algorithmic_GBps": round(ach, 1), "frac": round(ach / HBM_PEAK_GBS, 4),
+                           "traffic_GBps": round(traffic / (dom_ms * 1e-3) / 1e9, 1) if traffic else None,
+                           "traffic_frac": round(traffic / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
+                           "peak_GBps": HBM_PEAK_GBS}
+            if dom_flops:
+                tf_ = dom_flops / (dom_ms * 1e-3) / 1e12
+                roof["mfma"] = {"TFLOPs": round(tf_, 2), "frac": round(tf_ / MFMA_F32_PEAK_TFLOPS, 4), "peak_TFLOPs": MFMA_F32_PEAK_TFLOPS}
         out = {
             "metric": "rendered Mtexels/s at %d^2 UV (full Model.call forward: U-Net + UV->camera warp)" % args.uv,
             "value": round(value, 2), "unit": "Mtexels/s", "n_gpus": world, "steps": args.steps,
@@ -1460,12 +1507,13 @@ def main():
                        "distinct_batches_rotated": len(batches), "batch_source": "Dataset.load_batch (uint8 store -> float32 11-tuple, staging ring)",
                        "launch_tape_replays": fwd_replays, "parallelism": "dp%d (frames sharded, no forward collective)" % world,
                        "world": world, "dist_world_size": dist.get_world_size() if world > 1 else 1, "device": str(device)},
-            "roofline": roof,
-            "whole_pass": whole_pass(args, timer, elapsed / args.steps, bpt, live_step_bytes, plan=model.plan),
         }
+        if dominant:
+            out["roofline"] = roof
+            out["whole_pass"] = whole_pass(args, timer, elapsed / args.steps, bpt, live_step_bytes, plan=model.plan)
         if with_loader:
             out["forward_including_loader"] = with_loader
-        if world == 1 and not args.headline_only and args.uv == 1024:
+        if world == 1 and extra and args.uv == 1024:
             out["config5_2048_bf16"] = bench_config5(args, device)
             out["stress_64ch"] = bench_stress_64ch(device)
             if args.precision in ('fp32', 'f32x3_9') and not args.no_fused:
@@ -1475,7 +1523,7 @@ def main():
                 out["config3_f32_split"] = others
         if released:
             out["released_shapes"] = released
-        if world == 1 and not args.headline_only and args.uv == 1024 and not args.no_fused:
+        if world == 1 and extra and args.uv == 1024 and not args.no_fused:
             out["nlt_test_infer"] = child_leg('--infer-mode-worker', extra=['--steps', str(args.steps), '--depth', str(args.depth)])
             if "error" in out["nlt_test_infer"]:
                 try:
@@ -1503,34 +1551,35 @@ def main():
                 out["train_step_other_losses"] = train[1:]
         # several batches in flight: last of the GPU legs (the lanes' streams / graph pools stay with the process and were
         # measured to perturb legs that run after them: config 5 fp32 1.60 -> 1.70 ms)
-        if world == 1 and not args.graph and (args.pipelined or not args.headline_only):
+        if world == 1 and not args.graph and (args.pipelined or extra):
             out["pipelined"] = bench_pipelined(args, device, model, batches)
-            if args.precision in ('fp32', 'f32x3_9') and not args.no_fused and not args.headline_only:
+            if args.precision in ('fp32', 'f32x3_9') and not args.no_fused and extra:
                 try:
                     out["pipelined"]["f32x3_4_lanes"] = bench_f32_split_pipelined(args, device, model, batches)
                 except Exception as e:                                # a sub-sub-line: never take the line with it
                     out["pipelined"]["f32x3_4_lanes"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:200])}
             if released and args.uv == 1024:
                 out["released_shapes"]["forward_4_frames_pipelined"] = released_pipelined_child(args)
-        if world == 1 and not args.no_cpu_baseline and not args.headline_only:
+        if world == 1 and not args.no_cpu_baseline and extra:
             out["cpu_baseline"] = cpu_baseline(args)
         # what a 2000-byte tail of the line should still show goes last: the two baselines, then a digest of the line
         for key in ("native_fp32", "cpu_baseline"):
             if key in out:
                 out[key] = out.pop(key)
-        ts = {t_["loss"]: t_ for t_ in train if isinstance(t_, dict) and "loss" in t_}
-        out["summary"] = {
-            "forward_ms_per_step": out["ms_per_step"], "forward_Mtexels_per_s": out["value"], "forward_dtype": args.precision,
-            "native_fp32_ms_per_step": out.get("native_fp32", {}).get("ms_per_step"),
-            "dominant_kernel": dominant, "dominant_ms": round(dom_ms, 4), "dominant_frac_of_fp32_mfma_peak": roof.get("mfma", {}).get("frac"),
-            "dominant_frac_of_hbm_peak_algorithmic": roof["hbm"]["frac"], "dominant_frac_of_hbm_peak_pmc_traffic": roof["hbm"]["traffic_frac"],
-            "nlt_test_infer_1024_ms_per_step": out.get("nlt_test_infer", {}).get("uv1024_cam512", {}).get("ms_per_step"),
-            "nlt_test_infer_1024_Mtexels_per_s": out.get("nlt_test_infer", {}).get("uv1024_cam512", {}).get("Mtexels_per_s"),
-            "train_step_l2_ms": ts.get("l2", {}).get("ms_per_step"), "train_step_barron_ms": ts.get("barron", {}).get("ms_per_step"),
-            "train_step_l2_host_enqueue_ms": ts.get("l2", {}).get("host_enqueue_ms_per_step"),
-            "train_step_speedup_vs_one_rank": (train[0]["comm"].get("speedup_vs_one_rank") if train else None),
-            "train_step_scaling_efficiency": (train[0]["comm"].get("scaling_efficiency") if train else None),
-            "cpu_baseline_Mtexels_per_s": out.get("cpu_baseline", {}).get("value"), "cpu_cores": out.get("cpu_baseline", {}).get("cores")}
+        if dominant:
+            ts = {t_["loss"]: t_ for t_ in train if isinstance(t_, dict) and "loss" in t_}
+            out["summary"] = {
+                "forward_ms_per_step": out["ms_per_step"], "forward_Mtexels_per_s": out["value"], "forward_dtype": args.precision,
+                "native_fp32_ms_per_step": out.get("native_fp32", {}).get("ms_per_step"),
+                "dominant_kernel": dominant, "dominant_ms": round(dom_ms, 4), "dominant_frac_of_fp32_mfma_peak": roof.get("mfma", {}).get("frac"),
+                "dominant_frac_of_hbm_peak_algorithmic": roof["hbm"]["frac"], "dominant_frac_of_hbm_peak_pmc_traffic": roof["hbm"]["traffic_frac"],
+                "nlt_test_infer_1024_ms_per_step": out.get("nlt_test_infer", {}).get("uv1024_cam512", {}).get("ms_per_step"),
+                "nlt_test_infer_1024_Mtexels_per_s": out.get("nlt_test_infer", {}).get("uv1024_cam512", {}).get("Mtexels_per_s"),
+                "train_step_l2_ms": ts.get("l2", {}).get("ms_per_step"), "train_step_barron_ms": ts.get("barron", {}).get("ms_per_step"),
+                "train_step_l2_host_enqueue_ms": ts.get("l2", {}).get("host_enqueue_ms_per_step"),
+                "train_step_speedup_vs_one_rank": (train[0]["comm"].get("speedup_vs_one_rank") if train else None),
+                "train_step_scaling_efficiency": (train[0]["comm"].get("scaling_efficiency") if train else None),
+                "cpu_baseline_Mtexels_per_s": out.get("cpu_baseline", {}).get("value"), "cpu_cores": out.get("cpu_baseline", {}).get("cores")}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

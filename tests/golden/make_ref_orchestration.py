@@ -137,9 +137,13 @@ def main():
             m.call((None,) * 11, mode)
         except ValueError:
             out['bad_mode_raises_ValueError/' + mode] = np.array(1)
-    path = os.path.join(HERE, 'ref_orchestration.npz')
-    np.savez_compressed(path, **out)
-    print("wrote %s (%.1f KB, %d arrays)" % (path, os.path.getsize(path) / 1024, len(out)))
+    # two files, each under the repository's 1 MiB limit for a file: these cases go to the second
+    second = ('d256_override', 'd256_train', 'd256_vali', 'd64_train')
+    for fname, part in (('ref_orchestration.npz', {k: v for k, v in out.items() if k.split('/')[0] not in second}),
+                        ('ref_orchestration_2.npz', {k: v for k, v in out.items() if k.split('/')[0] in second})):
+        path = os.path.join(HERE, fname)
+        np.savez_compressed(path, **part)
+        print("wrote %s (%.1f KB, %d arrays)" % (path, os.path.getsize(path) / 1024, len(part)))
 
 
 if __name__ == '__main__':

@@ -17,8 +17,12 @@ import nlt_amd
 from nlt_amd.models import get_model_class
 from oracle import nlt_oracle as O
 
-G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_orchestration.npz'))
-CASES = sorted({k.split('/')[0] for k in G.files if k.startswith('d')})
+# the fixture is stored in two parts, each under the repository's 1 MiB limit for a file (make_ref_orchestration.py)
+G = {}
+for _part in ('ref_orchestration.npz', 'ref_orchestration_2.npz'):
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', _part)) as _z:
+        G.update((k, _z[k]) for k in _z.files)
+CASES = sorted({k.split('/')[0] for k in G if k.startswith('d')})
 
 
 def rel(a, b):
@@ -91,7 +95,7 @@ def test_oracle_model_equals_the_reference_s_own_model_code(name):
 
 
 def test_bad_modes_raise_like_the_reference():
-    assert 'bad_mode_raises_ValueError/training' in G.files and 'bad_mode_raises_ValueError/bogus' in G.files
+    assert 'bad_mode_raises_ValueError/training' in G and 'bad_mode_raises_ValueError/bogus' in G
     om = O.OracleModel(depth=256, uvh=64, uvw=64, imh=32, imw=32)
     pm = get_model_class('nlt')(nlt_amd.make_config(depth=256, uvh=64, uvw=64, imh=32, imw=32))
     for m in (om, pm):

@@ -13,7 +13,8 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -40 gpurun_out/pytest_gpu.log
 fi
 (timeout 300 python __graft_entry__.py smoke 2>&1 | tail -5) > gpurun_out/smoke.log; cat gpurun_out/smoke.log
-timeout 900 python bench.py --per-op --per-op-train --tune-cache gpurun_out/tune_fused.json > gpurun_out/bench.json 2> gpurun_out/bench_perop.txt
+OUT=$(dirname "$NLT_PARITY_DUMP")     # this session's output folder
+timeout 900 python bench.py --full --per-op --per-op-train --tune-cache "$OUT/tune_fused.json" > "$OUT/bench.json" 2> "$OUT/bench_perop.txt"
 cat gpurun_out/bench.json; tail -130 gpurun_out/bench_perop.txt
 B="python $R/bench.py --steps ${PROF_STEPS:-100} --warmup 10 --headline-only --tune-cache $R/gpurun_out/tune_fused.json"
 cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/prof" -o bench -- $B > "$R/gpurun_out/prof_bench.json" 2> "$R/gpurun_out/prof.err"
