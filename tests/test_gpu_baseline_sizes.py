@@ -8,7 +8,6 @@ benchmarked at.  The oracle needs ~0.5 s per 1024^2, k = 4 frame on 32 host thre
 Bars: rendered texels <= 1e-4 rel-L2; integer UV gather indices bit-exact; train-step loss and gradients against
 the oracle's float64 autograd, PER TENSOR (every kernel and bias of both nets), bounds GRAD_TOL_* below.
 """
-import json
 import os
 
 import numpy as np
@@ -18,7 +17,7 @@ import torch
 import nlt_amd
 from oracle import nlt_oracle as O
 from oracle import tf_ops as T
-from gpu_util import rel_l2, make_pair, to_device_batch
+from gpu_util import rel_l2, make_pair, to_device_batch, _dump, _set_alpha, _oracle_grads, _per_tensor
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -33,22 +32,6 @@ TOL = 1e-4
 # (alpha = 1 needs no conditioning: the activation is the identity.)
 GRAD_TOL_FLAT = 1e-5
 GRAD_TOL_TENSOR = 1e-5
-DUMP = os.environ.get('NLT_PARITY_DUMP')
-
-
-def _dump(name, rec):
-    if DUMP:
-        os.makedirs(os.path.dirname(DUMP) or '.', exist_ok=True)
-        try:
-            with open(DUMP) as f:
-                d = json.load(f)
-        except (OSError, ValueError):
-            d = {}
-        d[name] = rec
-        with open(DUMP, 'w') as f:
-            json.dump(d, f, indent=1)
-
-
 def _forward_vs_oracle(name, depth, uv, cam, n, k, identity_warp, seed, tol=TOL, **product_only):
     torch.set_num_threads(min(os.cpu_count() or 1, 64))
     om, pm = make_pair(depth=depth, uv=uv, im=cam, seed=seed, **product_only)
@@ -155,47 +138,6 @@ def test_headline_precision_at_the_bench_shape_and_at_config_5():
     conditions for this precision to carry the headline)."""
     _forward_vs_oracle('config3_1024_k4_n4_f32x3_9', 256, 1024, 512, 4, 4, False, seed=7, tol=1e-6, precision='f32x3_9')
     _forward_vs_oracle('config5_2048_k1_n2_f32x3_9', 256, 2048, 512, 2, 1, False, seed=52, tol=1e-6, precision='f32x3_9')
-
-
-def _set_alpha(om, pm, alpha):
-    """Same negative slope on both sides (alpha = 1: LeakyReLU becomes the identity -- a kink-free network)."""
-    from nlt_amd.networks.elements import Act, Sequential
-    om.alpha = alpha
-    for net in pm.net.values():
-        for blk in net.layers:
-            if isinstance(blk, Sequential):
-                for l in blk.layers:
-                    if isinstance(l, Act):
-                        l.alpha = alpha
-
-
-def _oracle_grads(loss, uv, cam, n, dtype, batch, nn, alpha=None, masks=None):
-    om = O.OracleModel(depth=256, uvh=uv, uvw=uv, imh=cam, imw=cam, loss=loss, seed=41, dtype=dtype)
-    if alpha is not None:
-        om.alpha = alpha
-    om.act_masks = masks
-    b = tuple(t.to(dtype) if torch.is_tensor(t) else t for t in batch)
-    nnl = [(a.to(dtype), c.to(dtype)) for a, c in nn]
-    po, go, _, _ = om.call(b, 'train', nn_list=nnl)
-    lo = om.compute_loss(po, go, keep_batch=True).sum() / n
-    grads = [g.double() for g in torch.autograd.grad(lo, om.parameters())]
-    return float(lo.detach()), grads
-
-
-def _per_tensor(pm, grads):
-    it = iter(grads)
-    names, errs = [], []
-    num = den = 0.0
-    for li, c in enumerate(pm._conv_layers()):
-        for nm in ('dkernel', 'dbias'):
-            g = next(it)
-            got = getattr(c, nm).detach().cpu().double()
-            d = float((got - g).norm())
-            r = float(g.norm())
-            num += d * d; den += r * r
-            names.append('conv%d.%s%s' % (li, nm, tuple(g.shape)))
-            errs.append(d / max(r, 1e-300))
-    return (num / den) ** 0.5, sorted(zip(errs, names), reverse=True)[:8]
 
 
 @pytest.mark.parametrize('loss,alpha,n,precision', [('l2', 0.3, 1, 'fp32'), ('barron', 0.3, 1, 'fp32'), ('l2', 1.0, 1, 'fp32'),

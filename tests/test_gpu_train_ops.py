@@ -525,3 +525,181 @@ def test_clip_by_norm_slots_matches_tf_clip_by_norm():
     for o, n in offs:
         pad[o:o + n] = False
     assert torch.equal(got[pad], ref[pad])                       # padding between slots untouched
+
+
+# ---- the depth-1024 network's deep levels (1 x 1 .. 8 x 8 texels, 512 .. 4096 channels) against FLOAT64 autograd, per tensor.
+# `wgrad_case` above compares with fp32 autograd at 3e-5 x max(|g|, 1), which a wrong small gradient can pass.
+DEEP_TOL = 1e-5                  # rel-L2 per tensor: the BASELINE config-4 bar (measured ~1e-7: K <= 8 x 4096, fp32 accumulation)
+DEEP_LAYERS = [(C.CONV_K2S1, 1024, 0, 1024),           # L7 / L8 q.s1, o.s1
+               (C.CONV_K2S2, 2048, 0, 1024),           # L8 q.s2 over fm[7] = [query | observation mean]
+               (C.CONV_K2S2, 1024, 0, 1024),           # L7 q.s2, L8 o.s2
+               (C.CONV_K2S2, 512, 0, 1024),            # L7 o.s2
+               (C.DECONV_K2S2, 2048, 2048, 512),       # the bottleneck deconv over concat(fm[8], fm[8]) (nlt.py:190)
+               (C.DECONV_K2S2, 512, 2048, 256),        # the next expanding block over [dec[0] | fm[7]]
+               (C.DECONV_K2S1, 512, 0, 512),
+               (C.DECONV_K2S1, 256, 0, 256)]
+deep_id = lambda p: '%s-%d+%d-%d' % ({C.CONV_K2S1: 'c2s1', C.CONV_K2S2: 'c2s2', C.DECONV_K2S2: 'd2s2', C.DECONV_K2S1: 'd2s1'}[p[0]],
+                                      p[1], p[2], p[3])
+
+
+def _rel(got, ref):
+    return float(np.linalg.norm(np.asarray(got, np.float64) - ref) / max(np.linalg.norm(ref), 1e-300))
+
+
+def wgrad_f64_case(mode, n, gw, c0, c1, cout, algo, seed=0):
+    """Weight + bias gradient of one deep layer on a gw x gw grid of GEMM texels (the stride-2 conv reads 2gw x 2gw), laid out
+    as the plan lays it out: the sources are channel slices of wider maps (leading dimension + 4; c0 == c1 is the bottleneck's
+    self-concatenation, both halves ONE map), dP the query half of a map twice as wide (dfm[l]), the result ACCUMULATED into a
+    non-zero buffer (dkernel / dbias are views of the flat gradient bucket).  Against float64 autograd, rel-L2 per tensor."""
+    rng = np.random.default_rng(seed)
+    k, s, tr = MODES[mode]
+    h = w = 2 * gw if mode == C.CONV_K2S2 else gw
+    self_concat = c1 == c0
+    x0 = rng.standard_normal((n, h, w, c0 + 4)).astype(np.float32)
+    x1 = x0 if self_concat else (rng.standard_normal((n, h, w, c1 + 4)).astype(np.float32) if c1 else None)
+    x = x0[..., :c0] if not c1 else np.concatenate((x0[..., :c0], x1[..., :c1]), -1)
+    cin = c0 + c1
+    wshape = (k, k, cout, cin) if tr else (k, k, cin, cout)
+    wz = torch.zeros(wshape, dtype=torch.float64, requires_grad=True)
+    bz = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
+    y = (T.conv2d_transpose_same if tr else T.conv2d_same)(torch.tensor(x, dtype=torch.float64), wz, bz, s)
+    oh, ow = y.shape[1:3]
+    dp = rng.standard_normal((n, oh, ow, 2 * cout)).astype(np.float32)
+    gw64, gb64 = (g.numpy() for g in torch.autograd.grad(y, (wz, bz), torch.tensor(dp[..., :cout], dtype=torch.float64)))
+    w0 = rng.standard_normal(wshape, dtype=np.float32) * np.float32(gw64.std())
+    b0 = rng.standard_normal(cout, dtype=np.float32) * np.float32(gb64.std())
+    dw, db = d(w0), d(b0)
+    xd0 = d(x0)
+    xd1 = xd0 if self_concat else d(x1)
+    args = (mode, xd0, c0, c0 + 4, xd1, c1, (c1 + 4) if c1 else 0, n, h, w, d(dp), 2 * cout, cout, dw, db)
+    if algo == 'tiled':
+        C.conv_backward_weights_tiled(*args)
+    else:
+        C.conv_backward_weights(*args, algo=algo)
+    torch.cuda.synchronize()
+    ew = _rel(dw.cpu().numpy().astype(np.float64) - w0, gw64)
+    eb = _rel(db.cpu().numpy().astype(np.float64) - b0, gb64)
+    assert ew <= DEEP_TOL and eb <= DEEP_TOL, ('dkernel', ew, 'dbias', eb, deep_id((mode, c0, c1, cout)), n, gw, algo)
+
+
+@pytest.mark.parametrize('layer', DEEP_LAYERS, ids=deep_id)
+@pytest.mark.parametrize('gw', [1, 2, 3])
+def test_wgrad_first_generation_at_depth1024_deep_levels_vs_float64(layer, gw):
+    """csrc/wgrad.hip (MFMA path), the kernel the plan gives every level narrower than 4 texels per grid row (the tiled and
+    narrow kernels refuse gw < 4): the depth-1024 layers at their 1 x 1 / 2 x 2-texel levels (+ gw = 3), 2 and 4 frames."""
+    for n in (2, 4):
+        wgrad_f64_case(layer[0], n, gw, *layer[1:], C.ALGO_MFMA, seed=100 * gw + n)
+
+
+@pytest.mark.parametrize('gw', [1, 2, 3])
+def test_wgrad_first_generation_direct_path_on_deep_level_grids_vs_float64(gw):
+    """The DIRECT path of csrc/wgrad.hip (the plan's choice for channel counts that are not multiples of 4) keeps K x N + N
+    partial sums in LDS, so it takes layers up to 8192 of them -- none of the depth-1024 deep layers, which it must refuse
+    rather than compute wrongly.  On the deep levels' grids: the widest layers it takes, odd channels, the dual source."""
+    for n in (2, 4):
+        for mode, c0, c1, cout in ((C.CONV_K2S1, 5, 3, 12), (C.CONV_K2S2, 30, 0, 60), (C.DECONV_K2S2, 8, 8, 12),
+                                   (C.DECONV_K2S1, 44, 0, 44), (C.CONV_K2S2, 7, 9, 5)):
+            wgrad_f64_case(mode, n, gw, c0, c1, cout, C.ALGO_DIRECT, seed=300 * gw + n + c0)
+    mode, c0, c1, cout = DEEP_LAYERS[0]
+    x, dp = torch.zeros(2, gw, gw, c0, device='cuda'), torch.zeros(2, gw, gw, cout, device='cuda')
+    with pytest.raises(C.NLTError):
+        C.conv_backward_weights(mode, x, c0, c0, None, 0, 0, 2, gw, gw, dp, cout, cout, torch.zeros(2, 2, c0, cout, device='cuda'),
+                                torch.zeros(cout, device='cuda'), algo=C.ALGO_DIRECT)
+
+
+@pytest.mark.parametrize('layer', DEEP_LAYERS, ids=deep_id)
+@pytest.mark.parametrize('gw', [4, 8])
+def test_wgrad_tiled_at_depth1024_deep_levels_vs_float64(layer, gw):
+    """csrc/wgrad_tile.hip on the same layers at the first levels wide enough for it (4 x 4: level 7 at 512^2, level 6 at 256^2)."""
+    wgrad_f64_case(layer[0], 2, gw, *layer[1:], 'tiled', seed=200 + gw)
+
+
+# Backward-data launches of the depth-1024 bottleneck: a handful of GEMM rows, K = taps x the layer's output channels.
+#   (layer mode, layer cin, layer cout, slice lo, hi, frames, output grid of the layer (dpre), level-split c (0: mask epilogue))
+DEEP_DGRAD = [(C.CONV_K2S1, 1024, 1024, 0, 1024, 2, 1, 0),       # L8 q.s1 at 256^2: 2 rows, K 4096
+              (C.CONV_K2S1, 1024, 1024, 0, 1024, 4, 4, 0),       # L7 q.s1 at 512^2: 64 rows, K 4096
+              (C.CONV_K2S1, 512, 2048, 0, 512, 4, 2, 0),         # 16 rows, K 8192
+              (C.DECONV_K2S2, 4096, 512, 0, 2048, 4, 2, 0),      # bottleneck deconv, the x half (dgrad.x), K 2048
+              (C.DECONV_K2S2, 4096, 512, 2048, 4096, 2, 2, 1024),  # its skip half, finishing dfm[8]: the level-split epilogue
+              (C.CONV_K2S2, 2048, 1024, 0, 2048, 4, 1, 1024)]    # L8 q.s2 finishing dfm[7] (level split with a partial dobs)
+SPLITS = (16, 64, 128, -16, -64, -128)
+
+
+def _deep_dgrad_setup(case, seed):
+    from nlt_amd.networks.elements import Conv2D
+    mode, cin, cout, lo, hi, n, g, sc = case
+    rng = np.random.default_rng(seed)
+    k, s, tr = MODES[mode]
+    R = lambda *shape: rng.standard_normal(shape).astype(np.float32)
+    wk = R(*((2, 2, cout, cin) if tr else (2, 2, cin, cout))) / np.float32(np.sqrt(4 * cin))
+    h = w = 2 * g if mode == C.CONV_K2S2 else (g // 2 if mode == C.DECONV_K2S2 else g)
+    x = torch.zeros((n, h, w, cin), dtype=torch.float64, requires_grad=True)
+    y = (T.conv2d_transpose_same if tr else T.conv2d_same)(x, torch.tensor(wk, dtype=torch.float64), torch.zeros(cout, dtype=torch.float64), s)
+    dp = R(*y.shape)
+    (gx,) = torch.autograd.grad(y, x, torch.tensor(dp, dtype=torch.float64))
+    gx = gx.numpy()[..., lo:hi]
+    layer = Conv2D(cout, 2, s, transpose=tr)
+    layer.set_weights(wk, np.zeros(cout, np.float32))
+    c = hi - lo
+    existing, mask = R(n, h, w, c), R(n, h, w, c)
+    tot = gx + existing
+    if sc:                                               # target dfm[l] = [query sc | observation mean sc], one observation per frame
+        obs_y, dobs0 = R(n, h, w, sc), R(n, h, w, sc)
+        partial = lo == 0
+        ref_q = tot[..., :sc] * np.where(mask[..., :sc] > 0, 1.0, 0.3)
+        ref_o = (tot[..., sc:] + (dobs0 if partial else 0)) * np.where(obs_y > 0, 1.0, 0.2)
+        ref = np.concatenate((ref_q, ref_o), -1)
+        split = lambda dobs: dict(split=(sc, d(obs_y), dobs, 0.2, partial))
+    else:
+        ref = tot * np.where(mask > 0, 1.0, 0.3)
+        obs_y = dobs0 = None
+        split = lambda dobs: {}
+    packed, ks = layer.packed_adjoint(lo, hi)
+    zb = torch.zeros(4096, device='cuda')
+    dpd, maskd, existd = d(dp), d(mask), d(existing)
+
+    def launch(ksplit):
+        out = d(existing)
+        dobs = d(dobs0) if sc else None
+        C.conv_backward_data(layer.ADJOINT[mode], dpd, cout, cout, n, y.shape[1], y.shape[2], packed, zb, c, out, c,
+                             mask_src=maskd, ldm=c, mask_alpha=0.3, accumulate=True, ksplit=ksplit, w_keras=ks, **split(dobs))
+        if not sc:
+            return out
+        assert torch.equal(out[..., sc:], existd[..., sc:]), ksplit     # the observation half of dfm[l] is not rewritten
+        return torch.cat((out[..., :sc], dobs), -1)
+    return launch, ref
+
+
+@pytest.mark.parametrize('case', DEEP_DGRAD, ids=lambda c: '%s-%d-%d:%d-n%d-g%d%s' % (
+    {C.CONV_K2S1: 'c2s1', C.CONV_K2S2: 'c2s2', C.DECONV_K2S2: 'd2s2'}[c[0]], c[1], c[3], c[4], c[5], c[6], '-split' if c[7] else ''))
+def test_split_k_backward_data_at_depth1024_bottleneck_shapes(case):
+    """nlt_conv_backward_data with ksplit in {16, 64, 128} (one launch) and {-16, -64, -128} (two launches) on the depth-1024
+    bottleneck's adjoint shapes (2-64 GEMM rows, K 2048-8192), with the producer's LeakyReLU' and accumulate = True, or the
+    level-split epilogue where the plan finishes dfm[l] with it: against float64 autograd (rel-L2 <= 1e-5), against the
+    single-slice launch (<= 2e-5 of scale), and bit-identical when repeated."""
+    launch, ref = _deep_dgrad_setup(case, seed=case[1] + case[3] + case[5] + case[6])
+    one = launch(1)
+    torch.cuda.synchronize()
+    assert _rel(one.cpu().numpy(), ref) <= DEEP_TOL, ('ksplit 1', _rel(one.cpu().numpy(), ref))
+    scale = float(one.abs().max())
+    for ksplit in SPLITS:
+        out, again = launch(ksplit), launch(ksplit)
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        assert _rel(got, ref) <= DEEP_TOL, (ksplit, _rel(got, ref))
+        assert float((out - one).abs().max()) <= 2e-5 * scale, (ksplit, float((out - one).abs().max()), scale)
+        assert torch.equal(out, again), ksplit
+
+
+def test_split_k_backward_data_deep_shapes_alternating_on_one_workspace():
+    """The deep backward-data launches above, at different slice counts and in both forms, in random order on ONE stream's split-K
+    workspace (as the backward plan issues them): each against the single-slice launch of the same inputs."""
+    setups = [_deep_dgrad_setup(c, seed=7 + i) for i, c in enumerate(DEEP_DGRAD)]
+    refs = [s[0](1) for s in setups]
+    order = torch.randint(0, len(setups) * len(SPLITS), (60,), generator=torch.Generator().manual_seed(11)).tolist()
+    for it, j in enumerate(order):
+        ci, ksplit = j // len(SPLITS), SPLITS[j % len(SPLITS)]
+        out = setups[ci][0](ksplit)
+        err = float((out - refs[ci]).abs().max())
+        scale = float(refs[ci].abs().max())
+        assert err <= 2e-5 * scale, (it, DEEP_DGRAD[ci], ksplit, err, scale)
