@@ -17,11 +17,14 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
-def make_pair(depth=256, uv=64, im=64, loss='l2', seed=0, use_obs=True, skip_connect_base=True, act='leakyrelu', **product_only):
-    """(oracle model, product model) sharing the same Keras-layout weights."""
-    om = O.OracleModel(depth=depth, uvh=uv, uvw=uv, imh=im, imw=im, loss=loss, seed=seed,
+def make_pair(depth=256, uv=64, im=64, loss='l2', seed=0, use_obs=True, skip_connect_base=True, act='leakyrelu', uvh=None, uvw=None,
+              imh=None, imw=None, **product_only):
+    """(oracle model, product model) sharing the same Keras-layout weights.  uv / im are the square shorthand; uvh, uvw, imh,
+    imw (each defaulting to it) set the axes apart."""
+    uvh, uvw, imh, imw = uvh or uv, uvw or uv, imh or im, imw or im
+    om = O.OracleModel(depth=depth, uvh=uvh, uvw=uvw, imh=imh, imw=imw, loss=loss, seed=seed,
                        use_obs=use_obs, skip_connect_base=skip_connect_base, act=act)
-    cfg = nlt_amd.make_config(depth=depth, uvh=uv, uvw=uv, imh=im, imw=im, loss=loss,
+    cfg = nlt_amd.make_config(depth=depth, uvh=uvh, uvw=uvw, imh=imh, imw=imw, loss=loss,
                               use_obs=use_obs, skip_connect_base=skip_connect_base, act=act, **product_only)
     pm = get_model_class('nlt')(cfg)
     pm.load_weights(om.numpy_weights())
@@ -84,10 +87,12 @@ def _set_alpha(om, pm, alpha):
                         l.alpha = alpha
 
 
-def _oracle_grads(loss, uv, cam, n, dtype, batch, nn, alpha=None, masks=None, depth=256, seed=41):
+def _oracle_grads(loss, uv, cam, n, dtype, batch, nn, alpha=None, masks=None, depth=256, seed=41, uvh=None, uvw=None, imh=None,
+                  imw=None):
     """(loss, every kernel / bias gradient) of one train step of a fresh OracleModel(depth, seed) in `dtype`; masks: the
-    activation branches to take (OracleModel.act_masks, e.g. `hip_activation_masks`)."""
-    om = O.OracleModel(depth=depth, uvh=uv, uvw=uv, imh=cam, imw=cam, loss=loss, seed=seed, dtype=dtype)
+    activation branches to take (OracleModel.act_masks, e.g. `hip_activation_masks`).  uv / cam: the square shorthand for
+    uvh x uvw / imh x imw."""
+    om = O.OracleModel(depth=depth, uvh=uvh or uv, uvw=uvw or uv, imh=imh or cam, imw=imw or cam, loss=loss, seed=seed, dtype=dtype)
     if alpha is not None:
         om.alpha = alpha
     om.act_masks = masks
@@ -114,3 +119,76 @@ def _per_tensor(pm, grads):
             names.append('conv%d.%s%s' % (li, nm, tuple(g.shape)))
             errs.append(d / max(r, 1e-300))
     return (num / den) ** 0.5, sorted(zip(errs, names), reverse=True)[:8]
+
+
+WGRAD_FNS = ('conv_backward_weights', 'conv_backward_weights_tiled', 'conv_backward_weights_narrow')
+
+
+def _spy_backward(monkeypatch, plan):
+    """Every weight-gradient and backward-data launch the plan issues outside its plan-time trials, as
+    (function, mode, c0, c1, n, h, w, src0, src1, dw).  The engine looks `C.<fn>` up at call time."""
+    from nlt_amd import capi as C
+    calls = []
+    for name in WGRAD_FNS + ('conv_backward_data',):
+        real = getattr(C, name)
+
+        def spy(*a, _name=name, _real=real, **kw):
+            if not plan._tuning:
+                if _name == 'conv_backward_data':
+                    calls.append((_name, a[0], a[2], 0, a[4], a[5], a[6], None, None, None))
+                else:
+                    calls.append((_name, a[0], a[2], a[5], a[7], a[8], a[9], a[1], a[4], a[13]))
+            return _real(*a, **kw)
+        monkeypatch.setattr(C, name, spy)
+    return calls
+
+
+def _force(plan, kind, hint, labels):
+    """Exactly one plan-time candidate on `labels`, every other launch on its default, no trials: the way
+    `RenderPlan._autotune` turns a winner into hints."""
+    from nlt_amd import capi as C
+    plan.tile_hints, plan.lds_hints, plan.wino_hints, plan.c32_hints, plan.splitk_hints, plan.algo_hints = {}, {}, {}, {}, {}, {}
+    for label in labels:
+        if kind == 'direct':
+            plan.algo_hints[label] = C.ALGO_DIRECT
+        elif kind == 'lds':
+            plan.lds_hints[label] = hint
+        elif kind == 'wino':
+            plan.wino_hints[label] = hint
+        elif kind == 'c32':
+            plan.c32_hints[label] = hint
+        elif kind == 'splitk':
+            plan.tile_hints[label], plan.splitk_hints[label] = hint
+        else:
+            plan.tile_hints[label] = hint
+    plan.autotune = plan.tune_backward = False
+    plan._drop_tapes()
+
+
+def _sweep_candidates(plan, run):
+    """Every (kind, hint) the plan-time trials recorded in `plan.tuned` (run the autotuned plan first), forced alone on every
+    launch it ran on (`_force`), each through `run() -> (bad, record)`.  Returns (records by candidate, failures, the
+    families covered: for the forward and for the backward-data launches)."""
+    tuned = {label: sorted({(kind, hint) for _, kind, hint in res}) for label, res in plan.tuned.items()}
+    cands = sorted({c for cs in tuned.values() for c in cs}, key=repr)
+    ran_on = {c: sorted(label for label, cs in tuned.items() if c in cs) for c in cands}
+    failures, recs = [], {}
+    for kind, hint in cands:
+        _force(plan, kind, hint, ran_on[(kind, hint)])
+        bad, rec = run()
+        recs[repr((kind, hint))] = dict(rec, launches=len(ran_on[(kind, hint)]))
+        if bad:
+            failures.append(((kind, hint), rec))
+
+    bwd = lambda c: [label for label in ran_on[c] if 'dgrad' in label]
+    fwd = lambda c: [label for label in ran_on[c] if not label.startswith('bwd.')]
+    covered = {'fwd.c32': sorted({h for k, h in cands if k == 'c32' and fwd((k, h))}),
+               'fwd.lds': sorted({h for k, h in cands if k == 'lds' and fwd((k, h))}),
+               'fwd.wino': sorted({h for k, h in cands if k == 'wino' and fwd((k, h))}),
+               'fwd.tile': sorted({h for k, h in cands if k == 'tile' and fwd((k, h))}),
+               'fwd.splitk': sorted({h for k, h in cands if k == 'splitk' and fwd((k, h))}),
+               'dgrad.splitk_one_launch': sorted({h for k, h in cands if k == 'splitk' and h[1] > 0 and bwd((k, h))}),
+               'dgrad.splitk_two_launches': sorted({h for k, h in cands if k == 'splitk' and h[1] < 0 and bwd((k, h))}),
+               'dgrad.lds': sorted({h for k, h in cands if k == 'lds' and bwd((k, h))}),
+               'dgrad.wino': sorted({h for k, h in cands if k == 'wino' and bwd((k, h))})}
+    return recs, failures, covered, len(tuned), len(cands)

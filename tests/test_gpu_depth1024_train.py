@@ -25,7 +25,7 @@ from nlt_amd import capi as C
 from nlt_amd import trainvali
 from oracle import nlt_oracle as O
 from gpu_util import (rel_l2, make_pair, to_device_batch, hip_activation_masks, _dump, _set_alpha, _oracle_grads,
-                      _per_tensor)
+                      _per_tensor, WGRAD_FNS, _spy_backward, _sweep_candidates)
 from test_gpu_train_step import flat_oracle_grads, per_tensor_worst, FLAT_TOL, TENSOR_TOL
 
 pytestmark = pytest.mark.gpu
@@ -33,29 +33,10 @@ DEPTH = 1024
 SEED = 43
 GRAD_TOL_FLAT = 1e-5
 GRAD_TOL_TENSOR = 1e-5
-WGRAD_FNS = ('conv_backward_weights', 'conv_backward_weights_tiled', 'conv_backward_weights_narrow')
 
 
 def _threads():
     torch.set_num_threads(min(os.cpu_count() or 1, 16))
-
-
-def _spy_backward(monkeypatch, plan):
-    """Every weight-gradient and backward-data launch the plan issues outside its plan-time trials, as
-    (function, mode, c0, c1, n, h, w, src0, src1, dw).  The engine looks `C.<fn>` up at call time."""
-    calls = []
-    for name in WGRAD_FNS + ('conv_backward_data',):
-        real = getattr(C, name)
-
-        def spy(*a, _name=name, _real=real, **kw):
-            if not plan._tuning:
-                if _name == 'conv_backward_data':
-                    calls.append((_name, a[0], a[2], 0, a[4], a[5], a[6], None, None, None))
-                else:
-                    calls.append((_name, a[0], a[2], a[5], a[7], a[8], a[9], a[1], a[4], a[13]))
-            return _real(*a, **kw)
-        monkeypatch.setattr(C, name, spy)
-    return calls
 
 
 def _gw(mode, w):
@@ -179,27 +160,6 @@ def test_depth1024_adam_and_clipnorm_steps_match_oracle(monkeypatch):
     assert worst < 2e-4, worst
 
 
-def _force(plan, kind, hint, labels):
-    """Exactly one plan-time candidate on `labels`, every other launch on its default, no trials: the way
-    `RenderPlan._autotune` turns a winner into hints."""
-    plan.tile_hints, plan.lds_hints, plan.wino_hints, plan.c32_hints, plan.splitk_hints, plan.algo_hints = {}, {}, {}, {}, {}, {}
-    for label in labels:
-        if kind == 'direct':
-            plan.algo_hints[label] = C.ALGO_DIRECT
-        elif kind == 'lds':
-            plan.lds_hints[label] = hint
-        elif kind == 'wino':
-            plan.wino_hints[label] = hint
-        elif kind == 'c32':
-            plan.c32_hints[label] = hint
-        elif kind == 'splitk':
-            plan.tile_hints[label], plan.splitk_hints[label] = hint
-        else:
-            plan.tile_hints[label] = hint
-    plan.autotune = plan.tune_backward = False
-    plan._drop_tapes()
-
-
 @pytest.mark.parametrize('mode', ['train', 'test'])
 def test_every_tuning_candidate_gives_float64_gradients(mode):
     """Every (kind, hint) the plan-time trials ran at depth 1024 (256^2, k = 1, n = 2, alpha = 1: kink-free, so the unconditioned
@@ -250,29 +210,9 @@ def test_every_tuning_candidate_gives_float64_gradients(mode):
 
     bad, base = run()                                       # autotuned: the forward (and in train mode the backward) trials
     assert not bad, ('autotuned plan', base)
-    tuned = {label: sorted({(kind, hint) for _, kind, hint in res}) for label, res in plan.tuned.items()}
-    cands = sorted({c for cs in tuned.values() for c in cs}, key=repr)
-    ran_on = {c: sorted(label for label, cs in tuned.items() if c in cs) for c in cands}
-    failures, recs = [], {}
-    for kind, hint in cands:
-        _force(plan, kind, hint, ran_on[(kind, hint)])
-        bad, rec = run()
-        recs[repr((kind, hint))] = dict(rec, launches=len(ran_on[(kind, hint)]))
-        if bad:
-            failures.append(((kind, hint), rec))
-
-    bwd = lambda c: [label for label in ran_on[c] if 'dgrad' in label]
-    fwd = lambda c: [label for label in ran_on[c] if not label.startswith('bwd.')]
-    covered = {'fwd.c32': sorted({h for k, h in cands if k == 'c32' and fwd((k, h))}),
-               'fwd.lds': sorted({h for k, h in cands if k == 'lds' and fwd((k, h))}),
-               'fwd.wino': sorted({h for k, h in cands if k == 'wino' and fwd((k, h))}),
-               'fwd.splitk': sorted({h for k, h in cands if k == 'splitk' and fwd((k, h))}),
-               'dgrad.splitk_one_launch': sorted({h for k, h in cands if k == 'splitk' and h[1] > 0 and bwd((k, h))}),
-               'dgrad.splitk_two_launches': sorted({h for k, h in cands if k == 'splitk' and h[1] < 0 and bwd((k, h))}),
-               'dgrad.lds': sorted({h for k, h in cands if k == 'lds' and bwd((k, h))}),
-               'dgrad.wino': sorted({h for k, h in cands if k == 'wino' and bwd((k, h))})}
+    recs, failures, covered, n_tuned, n_cands = _sweep_candidates(plan, run)
     _dump('depth1024_candidate_sweep_%s' % mode, {'autotuned': base, 'forced': recs, 'covered': covered,
-                                                 'tuned_labels': len(tuned), 'candidates': len(cands)})
+                                                 'tuned_labels': n_tuned, 'candidates': n_cands})
     assert not failures, "candidates off the float64 bars (candidate, worst): %s" % failures
     assert covered['fwd.c32'], "the forward trials ran no c32 launch"
     if mode == 'train':

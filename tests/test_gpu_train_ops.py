@@ -546,14 +546,16 @@ def _rel(got, ref):
     return float(np.linalg.norm(np.asarray(got, np.float64) - ref) / max(np.linalg.norm(ref), 1e-300))
 
 
-def wgrad_f64_case(mode, n, gw, c0, c1, cout, algo, seed=0):
-    """Weight + bias gradient of one deep layer on a gw x gw grid of GEMM texels (the stride-2 conv reads 2gw x 2gw), laid out
+def wgrad_f64_case(mode, n, gw, c0, c1, cout, algo, seed=0, gh=None):
+    """Weight + bias gradient of one deep layer on a gh x gw grid of GEMM texels (gh defaults to gw; the stride-2 conv reads
+    2gh x 2gw), laid out
     as the plan lays it out: the sources are channel slices of wider maps (leading dimension + 4; c0 == c1 is the bottleneck's
     self-concatenation, both halves ONE map), dP the query half of a map twice as wide (dfm[l]), the result ACCUMULATED into a
     non-zero buffer (dkernel / dbias are views of the flat gradient bucket).  Against float64 autograd, rel-L2 per tensor."""
     rng = np.random.default_rng(seed)
     k, s, tr = MODES[mode]
-    h = w = 2 * gw if mode == C.CONV_K2S2 else gw
+    gh = gw if gh is None else gh
+    h, w = (2 * gh, 2 * gw) if mode == C.CONV_K2S2 else (gh, gw)
     self_concat = c1 == c0
     x0 = rng.standard_normal((n, h, w, c0 + 4)).astype(np.float32)
     x1 = x0 if self_concat else (rng.standard_normal((n, h, w, c1 + 4)).astype(np.float32) if c1 else None)
@@ -574,12 +576,15 @@ def wgrad_f64_case(mode, n, gw, c0, c1, cout, algo, seed=0):
     args = (mode, xd0, c0, c0 + 4, xd1, c1, (c1 + 4) if c1 else 0, n, h, w, d(dp), 2 * cout, cout, dw, db)
     if algo == 'tiled':
         C.conv_backward_weights_tiled(*args)
+    elif algo == 'narrow':
+        C.conv_backward_weights_narrow(*args)
     else:
         C.conv_backward_weights(*args, algo=algo)
     torch.cuda.synchronize()
     ew = _rel(dw.cpu().numpy().astype(np.float64) - w0, gw64)
     eb = _rel(db.cpu().numpy().astype(np.float64) - b0, gb64)
-    assert ew <= DEEP_TOL and eb <= DEEP_TOL, ('dkernel', ew, 'dbias', eb, deep_id((mode, c0, c1, cout)), n, gw, algo)
+    assert ew <= DEEP_TOL and eb <= DEEP_TOL, ('dkernel', ew, 'dbias', eb, deep_id((mode, c0, c1, cout)), n, gh, gw, algo)
+    return max(ew, eb)
 
 
 @pytest.mark.parametrize('layer', DEEP_LAYERS, ids=deep_id)
@@ -628,11 +633,12 @@ SPLITS = (16, 64, 128, -16, -64, -128)
 def _deep_dgrad_setup(case, seed):
     from nlt_amd.networks.elements import Conv2D
     mode, cin, cout, lo, hi, n, g, sc = case
+    gh, gw = g if isinstance(g, tuple) else (g, g)                # output grid of the layer: square, or (rows, texels per row)
     rng = np.random.default_rng(seed)
     k, s, tr = MODES[mode]
     R = lambda *shape: rng.standard_normal(shape).astype(np.float32)
     wk = R(*((2, 2, cout, cin) if tr else (2, 2, cin, cout))) / np.float32(np.sqrt(4 * cin))
-    h = w = 2 * g if mode == C.CONV_K2S2 else (g // 2 if mode == C.DECONV_K2S2 else g)
+    h, w = (2 * gh, 2 * gw) if mode == C.CONV_K2S2 else ((gh // 2, gw // 2) if mode == C.DECONV_K2S2 else (gh, gw))
     x = torch.zeros((n, h, w, cin), dtype=torch.float64, requires_grad=True)
     y = (T.conv2d_transpose_same if tr else T.conv2d_same)(x, torch.tensor(wk, dtype=torch.float64), torch.zeros(cout, dtype=torch.float64), s)
     dp = R(*y.shape)
@@ -658,11 +664,22 @@ def _deep_dgrad_setup(case, seed):
     zb = torch.zeros(4096, device='cuda')
     dpd, maskd, existd = d(dp), d(mask), d(existing)
 
-    def launch(ksplit):
+    def launch(ksplit, lds=0, wino=0):
+        """ksplit: nlt_conv_backward_data (1: single slice, > 0 one launch, < 0 two launches); lds / wino = tn: the LDS-tiled /
+        Winograd kernel instead."""
         out = d(existing)
         dobs = d(dobs0) if sc else None
-        C.conv_backward_data(layer.ADJOINT[mode], dpd, cout, cout, n, y.shape[1], y.shape[2], packed, zb, c, out, c,
-                             mask_src=maskd, ldm=c, mask_alpha=0.3, accumulate=True, ksplit=ksplit, w_keras=ks, **split(dobs))
+        adj = layer.ADJOINT[mode]
+        kw = dict(mask_src=maskd, ldm=c, mask_alpha=0.3, accumulate=True)
+        if lds:
+            C.conv_tile_backward_data(adj, dpd, cout, cout, n, y.shape[1], y.shape[2], layer.packed_adjoint_tile(lo, hi, lds), c, lds,
+                                      out, c, **kw, **split(dobs))
+        elif wino:
+            packed_w = C.pack_conv_wino_weights(adj, torch.tensor(wk).cuda(), cout, c, wino, full=cin, lo=lo)
+            C.conv_wino_backward_data(adj, dpd, cout, cout, n, y.shape[1], y.shape[2], packed_w, c, wino, out, c, **kw)
+        else:
+            C.conv_backward_data(adj, dpd, cout, cout, n, y.shape[1], y.shape[2], packed, zb, c, out, c,
+                                 ksplit=ksplit, w_keras=ks, **kw, **split(dobs))
         if not sc:
             return out
         assert torch.equal(out[..., sc:], existd[..., sc:]), ksplit     # the observation half of dfm[l] is not rewritten
@@ -703,3 +720,113 @@ def test_split_k_backward_data_deep_shapes_alternating_on_one_workspace():
         err = float((out - refs[ci]).abs().max())
         scale = float(refs[ci].abs().max())
         assert err <= 2e-5 * scale, (it, DEEP_DGRAD[ci], ksplit, err, scale)
+
+
+# ---- flat and tall grids (non-square UV maps): a grid 1-3 rows high, where one 16-row step of the tiled / narrow kernels' incremental
+# row walk wraps the frame index several times, and a grid narrower than 4 texels but many rows high (the first-generation kernel).
+# At depth 256 a 64 x 512 map ends in 1 x 8-texel levels, 512 x 64 in 8 x 1.  (gh, gw) of the GEMM grid:
+FLAT_TALL = [(1, 4), (1, 8), (1, 16), (2, 4), (3, 5), (4, 1), (8, 1), (5, 3)]
+D256_LAYERS = [(C.CONV_K2S1, 256, 0, 256),             # L5 / L6 q.s1, o.s1
+               (C.CONV_K2S2, 512, 0, 256),             # L6 q.s2 over fm[5] = [query | observation mean]
+               (C.CONV_K2S2, 256, 0, 256),             # L6 o.s2, L5 q.s2 over fm[4]
+               (C.DECONV_K2S2, 512, 512, 128),         # the bottleneck deconv over concat(fm[6], fm[6])
+               (C.DECONV_K2S2, 128, 512, 64),          # the next expanding block over [dec[0] | fm[5]]
+               (C.DECONV_K2S1, 128, 0, 128)]
+NARROW_LAYERS = [(C.CONV_K2S1, 16, 0, 16), (C.CONV_K2S2, 16, 0, 32), (C.DECONV_K2S2, 8, 32, 4), (C.DECONV_K2S1, 8, 0, 8)]
+grid_id = lambda g: '%dx%d' % g
+
+
+@pytest.mark.parametrize('grid', FLAT_TALL, ids=grid_id)
+def test_wgrad_every_kernel_on_flat_and_tall_grids_vs_float64(grid):
+    """The tiled, narrow and first-generation (MFMA and DIRECT) weight gradients on a gh x gw grid, 1 and 3 frames, against float64
+    (rel-L2 <= DEEP_TOL per tensor): the depth-256 layers of the levels that sit at these grids, three DEEP_LAYERS, the narrow
+    kernel's layers.  A grid under 4 texels wide is refused by the tiled and narrow kernels (NLTError) -- the plan routes it to
+    the first-generation kernel -- and must stay refused rather than be computed wrongly."""
+    gh, gw = grid
+    for n in (1, 3):
+        for i, (mode, c0, c1, cout) in enumerate(D256_LAYERS + DEEP_LAYERS[1:4:2] + DEEP_LAYERS[4:5]):
+            seed = 1000 + 97 * gh + 13 * gw + 5 * n + i
+            wgrad_f64_case(mode, n, gw, c0, c1, cout, C.ALGO_MFMA, seed=seed, gh=gh)
+            if gw >= 4:
+                wgrad_f64_case(mode, n, gw, c0, c1, cout, 'tiled', seed=seed, gh=gh)
+        for mode, c0, c1, cout in NARROW_LAYERS:
+            seed = 2000 + 97 * gh + 13 * gw + 5 * n + c0
+            wgrad_f64_case(mode, n, gw, c0, c1, cout, C.ALGO_DIRECT, seed=seed, gh=gh)
+            if gw >= 4:
+                wgrad_f64_case(mode, n, gw, c0, c1, cout, 'narrow', seed=seed, gh=gh)
+        for mode, c0, c1, cout in ((C.CONV_K2S1, 5, 3, 12), (C.CONV_K2S2, 30, 0, 60), (C.DECONV_K2S2, 8, 8, 12)):
+            wgrad_f64_case(mode, n, gw, c0, c1, cout, C.ALGO_DIRECT, seed=3000 + gh + gw + n + c0, gh=gh)
+    if gw < 4:
+        x, dp = torch.zeros(1, gh, gw, 16, device='cuda'), torch.zeros(1, gh, gw, 16, device='cuda')
+        for fn in (C.conv_backward_weights_tiled, C.conv_backward_weights_narrow):
+            with pytest.raises(C.NLTError):
+                fn(C.CONV_K2S1, x, 16, 16, None, 0, 0, 1, gh, gw, dp, 16, 16, torch.zeros(2, 2, 16, 16, device='cuda'),
+                   torch.zeros(16, device='cuda'))
+
+
+# (layer mode, layer cin, layer cout, slice lo, hi, frames, output grid (gh, gw) of the layer, level-split c): the depth-256 backward-data
+# launches of the 1 x 8 / 8 x 1 levels (and their neighbours) of 64 x 512 / 512 x 64 maps
+FLAT_TALL_DGRAD = [(C.CONV_K2S1, 256, 256, 0, 256, 1, (1, 8), 0),         # L6 q.s1 at 64 x 512
+                   (C.CONV_K2S1, 256, 256, 0, 256, 3, (8, 1), 0),         # ... at 512 x 64
+                   (C.CONV_K2S1, 256, 256, 0, 256, 3, (3, 5), 0),
+                   (C.CONV_K2S1, 256, 256, 0, 256, 1, (5, 3), 0),
+                   (C.DECONV_K2S1, 128, 128, 0, 128, 3, (2, 16), 0),      # first expanding block's k2s1 at 64 x 512
+                   (C.DECONV_K2S1, 128, 128, 0, 128, 1, (16, 2), 0),
+                   (C.DECONV_K2S2, 1024, 128, 0, 512, 1, (2, 16), 0),     # bottleneck deconv, the x half
+                   (C.DECONV_K2S2, 1024, 128, 512, 1024, 3, (16, 2), 256),  # its skip half, finishing dfm[6]: level split
+                   (C.CONV_K2S2, 512, 256, 0, 512, 3, (1, 8), 256),       # L6 q.s2 finishing dfm[5] (level split, partial dobs)
+                   (C.CONV_K2S2, 512, 256, 0, 512, 1, (8, 1), 256)]
+
+
+@pytest.mark.parametrize('case', FLAT_TALL_DGRAD, ids=lambda c: '%s-%d-%d:%d-n%d-g%dx%d%s' % (
+    {C.CONV_K2S1: 'c2s1', C.CONV_K2S2: 'c2s2', C.DECONV_K2S2: 'd2s2', C.DECONV_K2S1: 'd2s1'}[c[0]], c[1], c[3], c[4], c[5],
+    c[6][0], c[6][1], '-split' if c[7] else ''))
+def test_backward_data_on_flat_and_tall_grids_vs_float64(case):
+    """Backward-data on flat and tall grids against float64 autograd (rel-L2 <= DEEP_TOL), with the producer's LeakyReLU' and
+    accumulate, or the level-split epilogue: the single-slice launch, split-K in one launch and in two, and -- for the launches
+    the plan may give them -- the LDS-tiled kernel (no level split) and the Winograd kernel (stride-1 layers)."""
+    launch, ref = _deep_dgrad_setup(case, seed=case[1] + case[3] + case[5] + 7 * case[6][0] + case[6][1])
+    mode, sc = case[0], case[7]
+    runs = [('ksplit', ks, launch(ks)) for ks in (1, 16, 64, -16, -64)]
+    if not sc:
+        runs += [('lds', tn, launch(1, lds=tn)) for tn in (32, 64)]
+    if not sc and mode in (C.CONV_K2S1, C.DECONV_K2S1):
+        runs += [('wino', tn, launch(1, wino=tn)) for tn in (32, 64)]
+    torch.cuda.synchronize()
+    for kind, hint, out in runs:
+        e = _rel(out.cpu().numpy(), ref)
+        assert e <= DEEP_TOL, (kind, hint, e)
+
+
+def test_warp_and_resize_backward_non_square_vs_float64():
+    """nlt_warp_backward with uvh != uvw and hc != wc (x scaled by uvw, y by uvh), warp coordinates inside the last UV row and
+    the last UV column, and the resize adjoint from a hc x wc grid to an image of another aspect, against float64 autograd."""
+    rng = np.random.default_rng(5)
+    n, uvh, uvw, hc, wc = 2, 12, 40, 10, 18
+    q = lambda a: (np.round(np.asarray(a) * 1024) / 1024).astype(np.float32)           # exactly representable coordinates
+    warp = q(rng.random((n, hc, wc, 2)))
+    warp[rng.random((n, hc, wc)) > 0.7] = 0
+    warp[0, 1, 2] = q([(uvw - 0.25) / uvw, 0.5])                    # x inside the last column
+    warp[0, 2, 3] = q([0.5, (uvh - 0.5) / uvh])                     # y inside the last row
+    warp[1, 3, 4] = q([(uvw - 0.75) / uvw, (uvh - 0.25) / uvh])     # both: the bottom-right texel
+    warp[1, 4, 5] = q([(uvw - 1.0) / uvw + 0.5 / 1024, (uvh - 1.0) / uvh + 0.5 / 1024])
+    xs, ys = warp[..., 0] * uvw, warp[..., 1] * uvh
+    assert np.any((xs > uvw - 1) & (xs < uvw)) and np.any((ys > uvh - 1) & (ys < uvh))
+    dcam = rng.standard_normal((n, hc, wc, 3)).astype(np.float32)
+    dpred = torch.empty(n, uvh, uvw, 3, device='cuda')
+    C.warp_backward(d(dcam), d(warp), n, uvh, uvw, hc, wc, dpred)
+    data = torch.zeros(n, uvh, uvw, 3, dtype=torch.float64, requires_grad=True)
+    scale = torch.tensor([uvw, uvh], dtype=torch.float64)
+    out = T.resampler(T.set_left_top_corner(data, 0), torch.tensor(warp, dtype=torch.float64) * scale)
+    (ref,) = torch.autograd.grad(out, data, torch.tensor(dcam, dtype=torch.float64))
+    got = dpred.cpu().numpy().astype(np.float64)
+    assert _rel(got, ref.numpy()) <= 1e-6, _rel(got, ref.numpy())
+    np.testing.assert_allclose(got[:, -1], ref.numpy()[:, -1], atol=1e-6)            # the last row
+    np.testing.assert_allclose(got[:, :, -1], ref.numpy()[:, :, -1], atol=1e-6)      # the last column
+    assert np.abs(ref.numpy()[:, -1]).max() > 0 and np.abs(ref.numpy()[:, :, -1]).max() > 0
+    for (ih, iw), (oh, ow) in (((hc, wc), (24, 14)), ((wc, hc), (14, 24)), ((hc, wc), (7, 30))):
+        dout = rng.standard_normal((2, oh, ow, 3)).astype(np.float32)
+        x = torch.zeros(2, ih, iw, 3, dtype=torch.float64, requires_grad=True)
+        (ref,) = torch.autograd.grad(T.resize_bilinear(x, oh, ow), x, torch.tensor(dout, dtype=torch.float64))
+        got = C.resize_bilinear_backward(d(dout), ih, iw).cpu().numpy().astype(np.float64)
+        assert _rel(got, ref.numpy()) <= 1e-6, ((ih, iw), (oh, ow), _rel(got, ref.numpy()))

@@ -17,9 +17,10 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a.numpy().astype(np.float64) - b.numpy()) / np.linalg.norm(b.numpy()))
 
 
-def make(depth, uv, im, **kw):
-    om = O.OracleModel(depth=depth, uvh=uv, uvw=uv, imh=im, imw=im, seed=1, **kw)
-    pm = get_model_class('nlt')(nlt_amd.make_config(depth=depth, uvh=uv, uvw=uv, imh=im, imw=im, **kw))
+def make(depth, uv, im, uvh=None, uvw=None, imh=None, imw=None, **kw):
+    uvh, uvw, imh, imw = uvh or uv, uvw or uv, imh or im, imw or im
+    om = O.OracleModel(depth=depth, uvh=uvh, uvw=uvw, imh=imh, imw=imw, seed=1, **kw)
+    pm = get_model_class('nlt')(nlt_amd.make_config(depth=depth, uvh=uvh, uvw=uvw, imh=imh, imw=imw, **kw))
     # CPU weights (the fake adapters take CPU tensors)
     for name in ('query', 'obs'):
         for layer, lw in zip(pm.net[name].layers, om.numpy_weights()[name]):
@@ -49,6 +50,24 @@ def test_fused_plan_matches_oracle(monkeypatch, depth, uv, k):
     assert rel_l2(vis['pred'], ref_vis['pred']) < 1e-5
     assert rel_l2(got_c, ref_c) < 1e-5 and rel_l2(got_gt, ref_gt) < 1e-5
     assert got_c.shape == (1, 32, 32, 3)                     # warp res 16 -> image res 32 (resize path)
+
+
+@pytest.mark.parametrize('uvh,uvw,hc,wc,imh,imw', [(64, 192, 24, 40, 48, 80), (192, 64, 40, 24, 80, 48)])
+@pytest.mark.parametrize('mode', ['train', 'test'])
+def test_fused_plan_matches_oracle_on_non_square_maps(monkeypatch, uvh, uvw, hc, wc, imh, imw, mode):
+    """UV map, warp grid and camera image each non-square (and of three different aspects), both orientations, k = 2: every
+    launch of the plan and the warp / resize sequence must keep the axes apart."""
+    fake_capi.install(monkeypatch)
+    om, pm = make(256, 0, 0, uvh=uvh, uvw=uvw, imh=imh, imw=imw)
+    batch, nn = O.synth_batch(2, uvh, uvw, hc, wc, imh, imw, k=2, seed=3)
+    with torch.no_grad():
+        ref_c, ref_gt, _, ref_vis = om.call(batch, mode, nn_list=nn)
+    got_c, got_gt, _, vis = pm.call(cpu_batch(batch, nn), mode, want_indices=True)
+    assert vis['pred'].shape == (2, uvh, uvw, 3) and got_c.shape == (2, imh, imw, 3)
+    assert rel_l2(vis['pred'], ref_vis['pred']) < 1e-5 and rel_l2(got_c, ref_c) < 1e-5
+    assert rel_l2(vis['base_camspc'], ref_vis['base_camspc']) < 1e-6
+    if mode != 'test':
+        assert rel_l2(got_gt, ref_gt) < 1e-6
 
 
 def test_layerwise_call_and_override_and_flags(monkeypatch):
