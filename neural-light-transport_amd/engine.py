@@ -48,6 +48,19 @@ class OpTimer:
         return self.records
 
 
+def _act_kw(act):
+    """The fused-activation keywords of every conv entry point."""
+    return {'act': act is not None, 'alpha': act.alpha if act is not None else 0.0}
+
+
+def _gemm(mode, n, h, w, cin, cout):
+    """The conv of this mode over [n,h,w,cin] as a GEMM: (rows, columns, FLOPs)."""
+    ncols = cout * (4 if mode == C.DECONV_K2S2 else 1)
+    taps = 4 if mode in (C.CONV_K2S2, C.CONV_K2S1, C.DECONV_K2S1) else 1
+    rows = n * h * w // (4 if mode == C.CONV_K2S2 else 1)
+    return rows, ncols, 2 * rows * taps * cin * ncols
+
+
 class RenderPlan(OverrideMixin):
     def __init__(self, net_query, net_obs, use_obs=True):
         self.timer = None               # set to an OpTimer (or a set of labels via timer.only) to time launches
@@ -141,7 +154,7 @@ class RenderPlan(OverrideMixin):
         E = lambda *s, lo=False: torch.empty(s, device=device, dtype=torch.bfloat16 if (bf and lo) else torch.float32)
         q, D = self.q, self.n_down
         mult = 2 if self.use_obs else 1
-        cl = [q.layers[0].n_ch_out] + [q.layers[l].convs()[0][0].n_ch_out for l in range(1, D + 1)]
+        cl = self._level_channels()
         b = {'C': cl, 'fm': [], 'obs': [], 'qtmp': [None], 'otmp': [None], 'dtmp': [], 'dec': []}
         hh, ww = h, w
         for l in range(D + 1):
@@ -178,6 +191,20 @@ class RenderPlan(OverrideMixin):
         else:
             fn(*args, **kw)
 
+    def _tile_splitk(self, label, rows, ncols, star, trial):
+        """Wave tile and split-K slices of a register-tiled launch: the plan's choice for the label, else what the running
+        plan-time trial asks of every launch (star: its tile_hints['*']; trial: its slices, where the waves are few)."""
+        tile_hint = self.tile_hints.get(label, self.tile_hints.get('*', 0) if star else 0)
+        if tile_hint and ((ncols + 15) // 16) % (tile_hint & 15):
+            tile_hint = 0                # CT must divide the number of 16-column tiles
+        ks = self.splitk_hints.get(label, 1)
+        if trial:
+            rt, ct = (tile_hint >> 4, tile_hint & 15) if tile_hint else (1, 1)
+            waves = -(-rows // (16 * rt)) * (-(-ncols // 16) // ct)
+            npad = -(-ncols // 16) * 16
+            ks = self._trial_splitk if (waves < 4096 and rows * npad * abs(self._trial_splitk) <= (1 << 24)) else 1
+        return tile_hint, ks
+
     def _conv(self, label, layer, act, src0, c0, ld0, src1, c1, ld1, n, h, w, out, ldo, algo=C.ALGO_AUTO, bmap=None):
         """bmap: per-output-texel bias map [1 | n, oh, ow, cout] added before the activation (engine_infer.py; MFMA path only)."""
         layer.build(c0 + c1, src0.device)
@@ -190,42 +217,52 @@ class RenderPlan(OverrideMixin):
         oh, ow = layer.out_hw(h, w)
         # SURVEY 8d accounting: every input element read once, every output element written once
         nbytes = 4 * (n * h * w * (c0 + c1) + n * oh * ow * layer.n_ch_out)
-        tile_hint = self.tile_hints.get(label, self.tile_hints.get('*', 0))
-        ncols = layer.n_ch_out * (4 if layer.mode == C.DECONV_K2S2 else 1)
-        taps = 4 if layer.mode in (C.CONV_K2S2, C.CONV_K2S1, C.DECONV_K2S1) else 1
-        rows = n * h * w // (4 if layer.mode == C.CONV_K2S2 else 1)
-        flops = 2 * rows * taps * (c0 + c1) * ncols
-        if tile_hint and ((ncols + 15) // 16) % (tile_hint & 15):
-            tile_hint = 0                # CT must divide the number of 16-column tiles
-        if c1 == 0 and ok and algo == C.ALGO_AUTO and self._wino(label, layer, act, src0, c0, ld0, n, 1, h, w, out, ldo, None, 0, flops):
+        rows, ncols, flops = _gemm(layer.mode, n, h, w, c0 + c1, layer.n_ch_out)
+        if c1 == 0 and ok and algo == C.ALGO_AUTO and self._wino(label, layer, act, src0, c0, ld0, n, 1, h, w, out, ldo):
             return
-        ks = self.splitk_hints.get(label, 1)
-        if self._trial_splitk and ok:
-            rt, ct = (tile_hint >> 4, tile_hint & 15) if tile_hint else (1, 1)
-            waves = -(-rows // (16 * rt)) * (-(-ncols // 16) // ct)
-            npad = -(-ncols // 16) * 16
-            ks = self._trial_splitk if (waves < 4096 and rows * npad * abs(self._trial_splitk) <= (1 << 24)) else 1
+        tile_hint, ks = self._tile_splitk(label, rows, ncols, True, self._trial_splitk and ok)
+        srcs = (src0, c0, ld0, src1, c1, ld1, n, h, w)
+        dst = (layer.bias.detach(), layer.n_ch_out, out, ldo)
+        kw = dict(_act_kw(act), flops=flops)
         if bmap is not None:
             if not ok:
                 raise C.NLTError("a bias-map conv needs channel counts that are multiples of 4 (%s)" % label)
             if abs(ks) > 1:
                 self._ran_splitk.add(label)
-            self._launch(label, nbytes, C.conv_forward_map, layer.mode, ks or 1, src0, c0, ld0, src1, c1, ld1, n, h, w,
-                         layer.packed(c0, c1), layer.bias.detach(), layer.n_ch_out, out, ldo, bmap, act=act is not None,
-                         alpha=act.alpha if act is not None else 0.0, tile_hint=tile_hint, w_keras=layer.kernel.detach(), flops=flops)
-            return
-        if abs(ks) > 1 and ok:
+            self._launch(label, nbytes, C.conv_forward_map, layer.mode, ks or 1, *srcs, layer.packed(c0, c1), *dst, bmap,
+                         tile_hint=tile_hint, w_keras=layer.kernel.detach(), **kw)
+        elif abs(ks) > 1 and ok:
             self._ran_splitk.add(label)
-            self._launch(label, nbytes, C.conv_forward_splitk, layer.mode, ks, src0, c0, ld0, src1, c1, ld1, n, h, w,
-                         layer.packed(c0, c1), layer.bias.detach(), layer.n_ch_out, out, ldo, act=act is not None,
-                         alpha=act.alpha if act is not None else 0.0, tile_hint=tile_hint, flops=flops)
-            return
-        self._launch(label, nbytes, C.conv_forward, layer.mode, src0, c0, ld0, src1, c1, ld1, n, h, w, layer.kernel.detach(),
-                       layer.packed(c0, c1) if ok else None, layer.bias.detach(), layer.n_ch_out, out, ldo,
-                       act=act is not None, alpha=act.alpha if act is not None else 0.0,
-                       algo=algo if ok else C.ALGO_DIRECT, tile_hint=tile_hint if ok else 0, flops=flops)
+            self._launch(label, nbytes, C.conv_forward_splitk, layer.mode, ks, *srcs, layer.packed(c0, c1), *dst,
+                         tile_hint=tile_hint, **kw)
+        else:
+            self._launch(label, nbytes, C.conv_forward, layer.mode, *srcs, layer.kernel.detach(),
+                         layer.packed(c0, c1) if ok else None, *dst, algo=algo if ok else C.ALGO_DIRECT,
+                         tile_hint=tile_hint if ok else 0, **kw)
 
-    def _wino(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, mean_out, ldm, flops, obs_weights=None):
+    def _mean(self, label, obs, obs_weights, frames, kobs, hw, c, mean_out, ldm):
+        """The mean over the kobs observations of a level as a launch of its own, under the stride-1 conv's label + '.mean'."""
+        self._launch(label.replace('.s1', '.mean'), 4 * frames * hw * c * (kobs + 1), C.obs_mean_forward,
+                     obs, obs_weights, frames, kobs, hw, c, mean_out, ldm)
+
+    def _enc_launch(self, fn, packed, extra, ran, unfold, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo,
+                    mean_out, ldm, **kw):
+        """The launch of `_conv_enc` on a kernel family that can fold the observation mean in (fn: its entry point, packed: its
+        fragments, extra: its own positional arguments, ran: its `_ran_*` set); unfold: observations as frames, the mean apart."""
+        oh, ow = layer.out_hw(h, w)
+        nf, c = frames * kobs, layer.n_ch_out
+        fold_mean = mean_out is not None and not unfold
+        nbytes = 4 * (nf * h * w * cin + nf * oh * ow * c)
+        if fold_mean:
+            nbytes += 4 * frames * oh * ow * c * (kobs + 1)       # what the separate mean launch would move
+        ran.add(label)
+        self._launch(label, nbytes, fn, layer.mode, src, ld, cin, nf if unfold else frames, 1 if unfold else kobs, h, w, packed,
+                     layer.bias.detach(), c, *extra, out, ldo, mean_out if fold_mean else None, ldm, **_act_kw(act), **kw,
+                     flops=2 * nf * oh * ow * 4 * cin * c)
+        if mean_out is not None and unfold:
+            self._mean(label, out, None, frames, kobs, oh * ow, c, mean_out, ldm)
+
+    def _wino(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, mean_out=None, ldm=0, obs_weights=None):
         """The launch on the Winograd kernel if the plan (or the running trial) gave it to it; False otherwise.
         The observation mean stays in the kernel's registers; +256 runs the observations as frames and the mean in its own launch."""
         hint = self._trial_wino or self.wino_hints.get(label, 0)
@@ -239,17 +276,8 @@ class RenderPlan(OverrideMixin):
             if self._trial_wino >> 8:
                 return False                            # nothing to unfold here: leave this launch to the other trials
             unfold = False
-        nf = frames * kobs
-        c = layer.n_ch_out
-        fold_mean = mean_out is not None and not unfold
-        nbytes = 4 * nf * h * w * (cin + c) + (4 * frames * h * w * c * (kobs + 1) if fold_mean else 0)
-        self._ran_wino.add(label)
-        self._launch(label, nbytes, C.conv_wino_forward, layer.mode, src, ld, cin, nf if unfold else frames, 1 if unfold else kobs,
-                     h, w, layer.packed_wino(tn), layer.bias.detach(), c, tn, out, ldo, mean_out if fold_mean else None, ldm,
-                     act=act is not None, alpha=act.alpha if act is not None else 0.0, flops=flops)
-        if mean_out is not None and unfold:
-            self._launch(label.replace('.s1', '.mean'), 4 * frames * h * w * c * (kobs + 1), C.obs_mean_forward,
-                         out, None, frames, kobs, h * w, c, mean_out, ldm)
+        self._enc_launch(C.conv_wino_forward, layer.packed_wino(tn), (tn,), self._ran_wino, unfold, label, layer, act, src, cin, ld,
+                         frames, kobs, h, w, out, ldo, mean_out, ldm)
         return True
 
     def _conv_bf(self, label, layer, act, src0, c0, ld0, src1, c1, ld1, n, h, w, out, ldo):
@@ -259,38 +287,26 @@ class RenderPlan(OverrideMixin):
         oh, ow = layer.out_hw(h, w)
         bpe = lambda t: 4 if t.dtype == torch.float32 else 2
         moved = n * h * w * (c0 * bpe(src0) + (c1 * bpe(src1) if c1 else 0)) + n * oh * ow * layer.n_ch_out * bpe(out)
-        ncols = layer.n_ch_out * (4 if layer.mode == C.DECONV_K2S2 else 1)
-        taps = 4 if layer.mode in (C.CONV_K2S2, C.CONV_K2S1, C.DECONV_K2S1) else 1
-        rows = n * h * w // (4 if layer.mode == C.CONV_K2S2 else 1)
         self._launch(label, 4 * (n * h * w * (c0 + c1) + n * oh * ow * layer.n_ch_out), C.conv_bf16_forward, layer.mode,
                      src0, c0, ld0, src1, c1, ld1, n, h, w, layer.packed_bf16(c0, c1), layer.bias.detach(), layer.n_ch_out, out, ldo,
-                     act=act is not None, alpha=act.alpha if act is not None else 0.0,
-                     tile_hint=self.tile_hints.get('bf.' + label, 0), flops=2 * rows * taps * (c0 + c1) * ncols, moved=moved)
+                     **_act_kw(act), tile_hint=self.tile_hints.get('bf.' + label, 0),
+                     flops=_gemm(layer.mode, n, h, w, c0 + c1, layer.n_ch_out)[2], moved=moved)
 
     def _conv_enc(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, algo, mean_out=None, ldm=0,
                   obs_weights=None):
         """One encoder conv (single source) over frames*kobs frames; with mean_out also the mean over the kobs
-        observations (label + '.mean' when it needs its own launch).  Goes to the LDS-tiled kernel when the plan
-        chose it for this launch, else to the register-tiled MFMA / direct kernels."""
+        observations (label + '.mean' when it needs its own launch).  Goes to the kernel family the plan (or the running
+        trial) chose for this launch -- narrow-level, Winograd, LDS-tiled, in that order -- else to the register-tiled MFMA /
+        direct kernels."""
         layer.build(cin, src.device)
+        conv = (label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, mean_out, ldm)
         chint = self._trial_c32 or self.c32_hints.get(label, 0)
         if (chint and self.use_c32 and algo == C.ALGO_AUTO and obs_weights is None and layer.cin == cin and ld % 4 == 0 and ldo % 4 == 0
                 and C.conv_c32_supported(layer.mode, cin, layer.n_ch_out) and not (chint == 2 and kobs == 1 and self._trial_c32)):
-            unfold = chint == 2 and kobs > 1
-            nf, c = frames * kobs, layer.n_ch_out
-            fold_mean = mean_out is not None and not unfold
-            nbytes = 4 * nf * h * w * (cin + c) + (4 * frames * h * w * c * (kobs + 1) if fold_mean else 0)
-            self._ran_c32.add(label)
-            self._launch(label, nbytes, C.conv_c32_forward, layer.mode, src, ld, cin, nf if unfold else frames, 1 if unfold else kobs, h, w,
-                         layer.packed_tile(32), layer.bias.detach(), c, out, ldo, mean_out if fold_mean else None, ldm,
-                         act=act is not None, alpha=act.alpha if act is not None else 0.0, flops=2 * nf * h * w * 4 * cin * c)
-            if mean_out is not None and unfold:
-                self._launch(label.replace('.s1', '.mean'), 4 * frames * h * w * c * (kobs + 1), C.obs_mean_forward,
-                             out, None, frames, kobs, h * w, c, mean_out, ldm)
+            self._enc_launch(C.conv_c32_forward, layer.packed_tile(32), (), self._ran_c32, chint == 2 and kobs > 1, *conv)
             return
         if (algo == C.ALGO_AUTO and layer.mode == C.CONV_K2S1 and (self._trial_wino or label in self.wino_hints)
-                and self._wino(label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, mean_out, ldm,
-                               2 * frames * kobs * h * w * 4 * cin * layer.n_ch_out, obs_weights)):
+                and self._wino(*conv, obs_weights)):
             return
         hint = self._trial_lds or (0 if (self._trial_wino or self._trial_c32) else self.lds_hints.get(label, 0))
         tn, unfold = hint & 255, bool(hint >> 8)       # +256: observations as separate frames, mean in its own launch
@@ -299,37 +315,25 @@ class RenderPlan(OverrideMixin):
         if ok and unfold and kobs == 1:
             ok = self._trial_lds == 0                   # nothing to unfold here: leave this launch to the other trials
             unfold = False
-        oh, ow = layer.out_hw(h, w)
-        if ok:
-            nf = frames * kobs
-            nbytes = 4 * (nf * h * w * cin + nf * oh * ow * layer.n_ch_out)
-            fold_mean = mean_out is not None and not unfold
-            if fold_mean:
-                nbytes += 4 * frames * oh * ow * layer.n_ch_out * (kobs + 1)       # what the separate mean launch would move
-            flops = 2 * nf * oh * ow * 4 * cin * layer.n_ch_out
-            self._ran_lds.add(label)
-            if self.precision in ('f32x3', 'f32x3_9'):
-                # fp32 operands as three bf16 terms on the bf16 matrix cores (csrc/conv_tile3.hip): 6 or all 9 term products
-                self._launch(label, nbytes, C.conv_tile3_forward, layer.mode, src, ld, cin, nf if unfold else frames,
-                             1 if unfold else kobs, h, w, layer.packed_tile3(tn), layer.bias.detach(), layer.n_ch_out, tn, out, ldo,
-                             mean_out if fold_mean else None, ldm, act=act is not None,
-                             alpha=act.alpha if act is not None else 0.0, nprod=9 if self.precision == 'f32x3_9' else 6, flops=flops)
-            else:
-                self._launch(label, nbytes, C.conv_tile_forward, layer.mode, src, ld, cin, nf if unfold else frames,
-                             1 if unfold else kobs, h, w, layer.packed_tile(tn), layer.bias.detach(), layer.n_ch_out, tn, out, ldo,
-                             mean_out if fold_mean else None, ldm, act=act is not None,
-                             alpha=act.alpha if act is not None else 0.0, flops=flops)
-            if mean_out is not None and unfold:
-                c = layer.n_ch_out
-                self._launch(label.replace('.s1', '.mean'), 4 * frames * oh * ow * c * (kobs + 1), C.obs_mean_forward,
-                             out, None, frames, kobs, oh * ow, c, mean_out, ldm)
-            return
-        self._conv(label, layer, act, src, cin, ld, None, 0, 0, frames * kobs, h, w, out, ldo, algo)
-        if mean_out is not None:
-            oh, ow = layer.out_hw(h, w)
-            c = layer.n_ch_out
-            self._launch(label.replace('.s1', '.mean'), 4 * frames * oh * ow * c * (kobs + 1), C.obs_mean_forward,
-                         out, obs_weights, frames, kobs, oh * ow, c, mean_out, ldm)
+        if ok and self.precision in ('f32x3', 'f32x3_9'):
+            # fp32 operands as three bf16 terms on the bf16 matrix cores (csrc/conv_tile3.hip): 6 or all 9 term products
+            self._enc_launch(C.conv_tile3_forward, layer.packed_tile3(tn), (tn,), self._ran_lds, unfold, *conv,
+                             nprod=9 if self.precision == 'f32x3_9' else 6)
+        elif ok:
+            self._enc_launch(C.conv_tile_forward, layer.packed_tile(tn), (tn,), self._ran_lds, unfold, *conv)
+        else:
+            self._conv(label, layer, act, src, cin, ld, None, 0, 0, frames * kobs, h, w, out, ldo, algo)
+            if mean_out is not None:
+                oh, ow = layer.out_hw(h, w)
+                self._mean(label, out, obs_weights, frames, kobs, oh * ow, layer.n_ch_out, mean_out, ldm)
+
+    def _dec_block_plain(self, b, j, lab, da, dact_a, db, dact_b, srcs, n, hh, ww, algo, s2_label=None, bmap=None):
+        """Expanding block j as its two convs, the first over srcs = (src0, c0, ld0, src1, c1, ld1); returns (map, channels).
+        The override plan hands in its derived stride-2 conv with that launch's label and bias map (engine_infer.py)."""
+        nl = da.n_ch_out
+        self._conv(s2_label or lab + '.s2', da, dact_a, *srcs, n, hh, ww, b['dtmp'][j], nl, algo, bmap=bmap)
+        self._conv(lab + '.s1', db, dact_b, b['dtmp'][j], nl, nl, None, 0, 0, n, 2 * hh, 2 * ww, b['dec'][j], db.n_ch_out, algo)
+        return b['dec'][j], db.n_ch_out
 
     # ------------------------------------------------------------------ autotune
     def _autotune(self, run, backward=False):
@@ -524,65 +528,86 @@ class RenderPlan(OverrideMixin):
         use_ovr = (obs_override is not None and inference and obs_weights is None
                    and self.can_fuse_override(self._level_channels(), obs_override, h, w, (base, cvis, lvis)))
         b = self._buffers(n, 0 if use_ovr else k, h, w, dev)
-        if not self._tuning:
-            self.generation += 1
-        reg = getattr(self.q.layers[0], '_registry', None)
-        if reg is not None:
-            if not self._tuning:
-                reg.tick()
-            reg.refresh_if_stale()          # all packed fragments, one launch, before any stream is forked
+        reg = self._begin_pass()
         ovr = self._prepare_override(b, obs_override, dev) if use_ovr else None
         fused = not use_ovr and (inference or self.fuse_train) and self.can_fuse(b, obs_weights, obs_override)
         if fused and not inference and w % 8:                           # the training ends: w/2 in groups of 4 texels
             fused = False
         b['train_fused'] = fused and not inference
         tuned_key = 'tuned_ovr' if use_ovr else (('tuned_fused' if inference else 'tuned_train') if fused else 'tuned')
-        if self.autotune and not b.get(tuned_key) and base.is_cuda:
-            b[tuned_key] = True
-            self._autotune(lambda: self.forward(base, cvis, lvis, nn_rgb, nn_base, obs_weights, obs_override,
-                                                skip_connect_base, algo, inference, pred_out=pred_out))
-        # launch tape (second sight of the same inputs records, later sights replay)
+        self._tune_once(b, tuned_key, base.is_cuda, lambda: self.forward(
+            base, cvis, lvis, nn_rgb, nn_base, obs_weights, obs_override, skip_connect_base, algo, inference, pred_out=pred_out))
         if fused or use_ovr:
             self._front_weights(dev, l2=inference or self.front4_train)   # folded front-kernel weights, refreshed in place OUTSIDE any tape
         tkey = None
-        if (self.use_tape and base.is_cuda and self.timer is None and not self._tuning and reg is not None
-                and obs_weights is None and (obs_override is None or use_ovr)
+        if (self._tape_ok(reg, base.is_cuda) and not self._tuning and obs_weights is None and (obs_override is None or use_ovr)
                 and all(t.is_contiguous() for t in (base, cvis, lvis, nn_rgb, nn_base))):    # (a replay skips the adapters' layout checks)
             tkey = ('fwd', base.data_ptr(), cvis.data_ptr(), lvis.data_ptr(), nn_rgb.data_ptr(), nn_base.data_ptr(),
                     bool(skip_connect_base), algo, inference, fused, C._stream(), pred_out is not None,
                     ovr['serial'] if use_ovr else 0)
-            return self._run_taped(b, reg, tkey, lambda: self._forward_body(
-                b, base, cvis, lvis, nn_rgb, nn_base, obs_weights, obs_override, skip_connect_base, algo, fused, inference, ovr))
-        return self._forward_body(b, base, cvis, lvis, nn_rgb, nn_base, obs_weights, obs_override, skip_connect_base, algo,
-                                  fused, inference, ovr)
+        return self._run_taped(b, reg, tkey, lambda: self._forward_body(
+            b, base, cvis, lvis, nn_rgb, nn_base, obs_weights, obs_override, skip_connect_base, algo, fused, inference, ovr))
 
-    def _run_taped(self, b, reg, tkey, body):
+    # The prologue of `forward`, `_forward_resident`, `_forward_resident_ovr` (engine_infer.py) and `backward`.  Where the four
+    # differed before they shared it, each keeps what it did: the backward ticks the registry but neither refreshes it nor bumps
+    # `generation`, and tapes without asking for `not self._tuning`; `_forward_resident` tunes and tapes without asking whether
+    # its store is on the GPU (the others: base.is_cuda / dev.type / dpred.is_cuda); only `forward` and `backward` want contiguous
+    # inputs and no obs_weights before they tape; a backward tape is valid by `tape_valid` alone (no output closure to keep).
+    def _begin_pass(self, bump=True, refresh=True):
+        """Start of a pass (a plan-time trial is none): `generation`, the pack registry's clock, and its stale fragments
+        re-packed in one launch before any stream is forked.  Returns the registry (None: the weights are no flat bucket)."""
+        reg = getattr(self.q.layers[0], '_registry', None)
+        if not self._tuning:
+            if bump:
+                self.generation += 1
+            if reg is not None:
+                reg.tick()
+        if reg is not None and refresh:
+            reg.refresh_if_stale()
+        return reg
+
+    def _tune_once(self, b, key, on_gpu, run, backward=False):
+        """The plan-time trials over `run`, once per buffer set and kind of pass; True if they ran now."""
+        if not (self.autotune and on_gpu) or b.get(key):
+            return False
+        b[key] = True
+        self._autotune(run, backward=backward)
+        return True
+
+    def _tape_ok(self, reg, on_gpu):
+        """Launch tapes at all?  (Each entry point adds its own conditions.)"""
+        return self.use_tape and on_gpu and self.timer is None and reg is not None
+
+    def _run_taped(self, b, reg, tkey, body, valid=None, finish=None):
         """`body()` under the launch tape of this (inputs, plan state) key: first sight runs it, second sight records it, later
-        sights replay the record (csrc/tape.hip) -- as long as the buffers and packed fragments it baked in are still the ones."""
+        sights replay the record (csrc/tape.hip) and return finish(b) -- as long as valid(b, ent, reg): the buffers and packed
+        fragments it baked in are still the ones.  Defaults: the forwards' `_replayable` / `_finish_pred`.  tkey None: no tape."""
+        if tkey is None:
+            return body()
         tapes = b.setdefault('tapes', {})
         if len(tapes) > 16:                     # ever-changing input addresses (a loader that allocates per step): forget
             tapes.clear()
         ent = tapes.get(tkey, 0)
         if isinstance(ent, tuple):
-            if self._replayable(b, ent, reg):
+            if (valid or self._replayable)(b, ent, reg):
                 reg.touch_keys(ent[4])              # (a replay reads its fragment buffers without asking: tell a running census)
                 C.replay(ent)
                 self.tape_replays += 1
-                return self._finish_pred(b), b
+                return (finish or self._finish_pred)(b)
             ent = 1
         tapes[tkey] = 1
-        if ent == 1:
-            C.tape_begin()
-            reg.begin_record()
-            try:
-                out = body()
-            except BaseException:
-                C.tape_abort()
-                reg.end_record()
-                raise
-            tapes[tkey] = C.tape_end(reg.version, reg.end_record()) or 1  # (None: a workspace grew while recording -> record again)
-            return out
-        return body()
+        if ent != 1:
+            return body()
+        C.tape_begin()
+        reg.begin_record()
+        try:
+            out = body()
+        except BaseException:
+            C.tape_abort()
+            reg.end_record()
+            raise
+        tapes[tkey] = C.tape_end(reg.version, reg.end_record()) or 1  # (None: a workspace grew while recording -> record again)
+        return out
 
     def _forward_resident(self, res, skip_connect_base, algo):
         """Inference forward whose inputs are still in the resident uint8 store: same plan, the front launch is
@@ -590,26 +615,18 @@ class RenderPlan(OverrideMixin):
         n, k, h, w = res.n, res.k, res.h, res.w
         dev = res.cvis.device
         b = self._buffers(n, k, h, w, dev)
-        if not self._tuning:
-            self.generation += 1
-        reg = getattr(self.q.layers[0], '_registry', None)
-        if reg is not None:
-            if not self._tuning:
-                reg.tick()
-            reg.refresh_if_stale()
+        reg = self._begin_pass()
         if not self.can_fuse(b, None, None):
             raise C.NLTError("this network / plan cannot take store-resident inputs: materialise the batch")
         b['train_fused'] = False
-        if self.autotune and not b.get('tuned_fused'):
-            b['tuned_fused'] = True
-            self._autotune(lambda: self._forward_resident(res, skip_connect_base, algo))
+        # (on_gpu = True: unlike the other entry points this one does not look where the store lives)
+        self._tune_once(b, 'tuned_fused', True, lambda: self._forward_resident(res, skip_connect_base, algo))
         self._front_weights(dev)
         tkey = None
-        if self.use_tape and self.timer is None and not self._tuning and reg is not None:
+        if self._tape_ok(reg, True) and not self._tuning:
             tkey = ('fwd_u8',) + res.key() + (bool(skip_connect_base), algo, C._stream(), self._pred_out is not None)
-            return self._run_taped(b, reg, tkey, lambda: self._forward_fused(b, None, None, None, None, None, skip_connect_base, algo,
-                                                                             resident=res))
-        return self._forward_fused(b, None, None, None, None, None, skip_connect_base, algo, resident=res)
+        return self._run_taped(b, reg, tkey, lambda: self._forward_fused(b, None, None, None, None, None, skip_connect_base, algo,
+                                                                         resident=res))
 
     def _forward_body(self, b, base, cvis, lvis, nn_rgb, nn_base, obs_weights, obs_override, skip_connect_base, algo, fused,
                       inference, ovr=None):
@@ -663,14 +680,10 @@ class RenderPlan(OverrideMixin):
         x, cx = b['fm'][D], mult * cl[D]
         for j in range(self.n_up):
             (da, dact_a), (db, dact_b) = q.layers[D + 1 + j].convs()
-            skip = b['fm'][D - j]
             cs = mult * cl[D - j]
-            lab = 'L%d.q' % (D + 1 + j)
-            self._conv(lab + '.s2', da, dact_a, x, cx, cx, skip, cs, cs, n, hh, ww, b['dtmp'][j], da.n_ch_out, algo)
+            x, cx = self._dec_block_plain(b, j, 'L%d.q' % (D + 1 + j), da, dact_a, db, dact_b, (x, cx, cx, b['fm'][D - j], cs, cs),
+                                          n, hh, ww, algo)
             hh, ww = hh * 2, ww * 2
-            self._conv(lab + '.s1', db, dact_b, b['dtmp'][j], da.n_ch_out, da.n_ch_out, None, 0, 0, n, hh, ww,
-                       b['dec'][j], db.n_ch_out, algo)
-            x, cx = b['dec'][j], db.n_ch_out
 
         head = q.layers[-1]
         cs = mult * cl[0]
@@ -837,11 +850,8 @@ class RenderPlan(OverrideMixin):
                 hh, ww = hh * 2, ww * 2
                 x, cx = b['dec'][j], nl
                 continue
-            self._conv(lab + '.s2', da, dact_a, x, cx, cx, skip, cs, cs, n, hh, ww, b['dtmp'][j], da.n_ch_out, algo)
+            x, cx = self._dec_block_plain(b, j, lab, da, dact_a, db, dact_b, (x, cx, cx, skip, cs, cs), n, hh, ww, algo)
             hh, ww = hh * 2, ww * 2
-            self._conv(lab + '.s1', db, dact_b, b['dtmp'][j], da.n_ch_out, da.n_ch_out, None, 0, 0, n, hh, ww,
-                       b['dec'][j], db.n_ch_out, algo)
-            x, cx = b['dec'][j], db.n_ch_out
         (da, _), (db, _) = q.layers[D + U].convs()
         head = q.layers[-1]
         da.build(cx + 2 * cl[1], dev); db.build(4, dev)
@@ -855,15 +865,19 @@ class RenderPlan(OverrideMixin):
 
         def back(pred):
             self._launch('F.back', nbytes, C.back_forward_train if train else C.back_forward, *back_args, pred, *extra, **back_kw)
+        # One closure per kind of pass: the train forward's last launch also keeps two maps for the backward.
+        return self._emit_back(b, 'back_train' if train else 'back_infer', back)
+
+    def _emit_back(self, b, slot, back):
+        """The last launch of a fused forward, back(pred).  Into the caller's own output tensor (`forward`, pred_out) it is not
+        part of the launch tape (that address differs every step): b[slot] keeps it for `_finish_pred`."""
         out = self._pred_out if not self._tuning else None
         if out is None:
             # (leaves the closures alone: a timed survey or a copy-out pass over these buffers must not take them away from
             # the tapes recorded with pred_out -- they would hand out a stale b['pred'])
             back(b['pred'])
             return b['pred'], b
-        # the caller's own output tensor: this launch is not part of the launch tape (its output address differs every step).
-        # One closure per kind of pass: the train forward's last launch also keeps two maps for the backward.
-        b['back_train' if train else 'back_infer'] = back
+        b[slot] = back
         paused = C.tape_pause()
         try:
             back(out)
@@ -872,11 +886,11 @@ class RenderPlan(OverrideMixin):
         return out, b
 
     def _finish_pred(self, b):
-        """After a tape replay: the launch that was kept out of the tape (see `forward`, pred_out)."""
+        """After a tape replay: the launch that was kept out of the tape (see `forward`, pred_out); what `forward` returns."""
         if self._pred_out is None:
-            return b['pred']
+            return b['pred'], b
         b[self._pred_slot](self._pred_out)      # (`_replayable` made sure it exists)
-        return self._pred_out
+        return self._pred_out, b
 
     def _replayable(self, b, ent, reg):
         """A recorded forward tape may be replayed: still valid, and -- when this call brought its own output tensor -- the
@@ -973,19 +987,8 @@ class RenderPlan(OverrideMixin):
         out_px = n * oh * ow * (4 if adj == C.DECONV_K2S2 else 1) // (4 if adj == C.CONV_K2S2 else 1)
         nbytes = 4 * (n * oh * ow * layer.n_ch_out + out_px * (hi - lo))
         # wave tile / split-K of this launch: chosen by timing at plan time like the forward's (`_autotune` on the backward)
-        ncols = (hi - lo) * (4 if adj == C.DECONV_K2S2 else 1)
-        rows = n * oh * ow // (4 if adj == C.CONV_K2S2 else 1)
-        tile_hint = self.tile_hints.get(label, self.tile_hints.get('*', 0) if self._tuning else 0)
-        if tile_hint and ((ncols + 15) // 16) % (tile_hint & 15):
-            tile_hint = 0
-        nks = self.splitk_hints.get(label, 1)
-        if self._trial_splitk:
-            rt, ct = (tile_hint >> 4, tile_hint & 15) if tile_hint else (1, 1)
-            waves = -(-rows // (16 * rt)) * (-(-ncols // 16) // ct)
-            npad = -(-ncols // 16) * 16
-            nks = self._trial_splitk if (waves < 4096 and rows * npad * abs(self._trial_splitk) <= (1 << 24)) else 1
-        taps = 1 if adj == C.DECONV_K2S2 else 4
-        flops = 2 * rows * taps * layer.n_ch_out * ncols
+        rows, ncols, flops = _gemm(adj, n, oh, ow, layer.n_ch_out, hi - lo)
+        tile_hint, nks = self._tile_splitk(label, rows, ncols, self._tuning, self._trial_splitk)
         # LDS-tiled kernel (csrc/conv_tile.hip) for the launches the plan-time trials gave to it: the adjoint families it has
         # (CONV_K2S1 / CONV_K2S2 of the expanding blocks, the transposed k2s1 of the encoder's stride-1 convs), no split epilogue
         wtn = (self._trial_wino or self.wino_hints.get(label, 0)) & 255
@@ -1031,49 +1034,20 @@ class RenderPlan(OverrideMixin):
         k = nn_rgb.shape[1]
         b = self._buffers(n, k, h, w, base.device)
         g = self._grad_buffers(b)
-        q, o, D, U, cl = self.q, self.o, self.n_down, self.n_up, b['C']
-        zb = g['zero_bias']
-        reg = getattr(self.q.layers[0], '_registry', None)
-        if reg is not None and not self._tuning:
-            reg.tick()
-        if self.autotune and self.tune_backward and dpred.is_cuda and not b.get('tuned_bwd') and not self._tuning:
+        reg = self._begin_pass(bump=False, refresh=False)      # (this pass has always ticked the registry and never refreshed it)
+        run = lambda: self._backward_streams(dpred, base, cvis, lvis, nn_rgb, nn_base, obs_weights, b, g, n, h, w, k)
+        if self.tune_backward and not self._tuning and self._tune_once(b, 'tuned_bwd', dpred.is_cuda, run, backward=True):
             # plan-time choice of the backward-data launches' wave tiles / split-K (the same trial machinery as the forward).
             # The trial passes accumulate into the weight-gradient bucket: it is cleared again before the real pass.
-            b['tuned_bwd'] = True
-            self._autotune(lambda: self._backward_streams(dpred, base, cvis, lvis, nn_rgb, nn_base, obs_weights, b, g, n, h, w, k),
-                           backward=True)
-            bucket = getattr(q.layers[0].dkernel, '_base', None)
+            bucket = getattr(self.q.layers[0].dkernel, '_base', None)
             if bucket is not None:
                 bucket.zero_()
         tkey = None
-        if (self.use_tape and dpred.is_cuda and self.timer is None and reg is not None and obs_weights is None
+        if (self._tape_ok(reg, dpred.is_cuda) and obs_weights is None
                 and all(t.is_contiguous() for t in (dpred, base, cvis, lvis, nn_rgb, nn_base))):
             tkey = ('bwd', dpred.data_ptr(), base.data_ptr(), cvis.data_ptr(), lvis.data_ptr(), nn_rgb.data_ptr(),
                     nn_base.data_ptr(), bool(b.get('train_fused')), self.bwd_streams, C._stream())
-            tapes = b.setdefault('tapes', {})
-            if len(tapes) > 16:                     # ever-changing input addresses (a loader that allocates per step): forget
-                tapes.clear()
-            ent = tapes.get(tkey, 0)
-            if isinstance(ent, tuple):
-                if C.tape_valid(ent, reg.version):
-                    reg.touch_keys(ent[4])
-                    C.replay(ent)
-                    self.tape_replays += 1
-                    return
-                ent = 1
-            tapes[tkey] = 1
-            if ent == 1:
-                C.tape_begin()
-                reg.begin_record()
-        try:
-            self._backward_streams(dpred, base, cvis, lvis, nn_rgb, nn_base, obs_weights, b, g, n, h, w, k)
-        except BaseException:
-            if tkey is not None and ent == 1:
-                C.tape_abort()
-                reg.end_record()
-            raise
-        if tkey is not None and ent == 1:
-            b['tapes'][tkey] = C.tape_end(reg.version, reg.end_record()) or 1
+        self._run_taped(b, reg, tkey, run, valid=lambda b, ent, reg: C.tape_valid(ent, reg.version), finish=lambda b: None)
 
     def _backward_streams(self, dpred, base, cvis, lvis, nn_rgb, nn_base, obs_weights, b, g, n, h, w, k):
         concurrent = self.bwd_streams and dpred.is_cuda and self.timer is None

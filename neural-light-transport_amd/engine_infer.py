@@ -189,25 +189,17 @@ class OverrideMixin:
         if not self.resident_override_ok(res, obs_override, self.q.layers[1].convs()[0][1].alpha):
             raise C.NLTError("this network / plan / obs_override cannot take store-resident inputs: materialise the batch")
         b = self._buffers(n, 0, h, w, dev)
-        if not self._tuning:
-            self.generation += 1
-        reg = getattr(self.q.layers[0], '_registry', None)
-        if reg is not None:
-            if not self._tuning:
-                reg.tick()
-            reg.refresh_if_stale()
+        reg = self._begin_pass()
         ovr = self._prepare_override(b, obs_override, dev)
         b['train_fused'] = False
-        if self.autotune and not b.get('tuned_ovr') and dev.type == 'cuda':
-            b['tuned_ovr'] = True
-            self._autotune(lambda: self._forward_resident_ovr(res, obs_override, skip_connect_base, algo))
+        on_gpu = dev.type == 'cuda'
+        self._tune_once(b, 'tuned_ovr', on_gpu, lambda: self._forward_resident_ovr(res, obs_override, skip_connect_base, algo))
         self._front_weights(dev, l2=True)
-        body = lambda: self._forward_ovr(b, None, None, None, ovr, skip_connect_base, algo, resident=res)
-        if self.use_tape and dev.type == 'cuda' and self.timer is None and not self._tuning and reg is not None:
+        tkey = None
+        if self._tape_ok(reg, on_gpu) and not self._tuning:
             tkey = ('ovr_u8', res.diffuse.data_ptr(), res.cvis.data_ptr(), res.lvis.data_ptr(), res.ids.data_ptr(), n,
                     bool(skip_connect_base), algo, C._stream(), self._pred_out is not None, ovr['serial'])
-            return self._run_taped(b, reg, tkey, body)
-        return body()
+        return self._run_taped(b, reg, tkey, lambda: self._forward_ovr(b, None, None, None, ovr, skip_connect_base, algo, resident=res))
 
     def _forward_ovr(self, b, base, cvis, lvis, st, skip_connect_base, algo, resident=None):
         """front_ovr -> levels 2..D (query path only) -> expanding blocks -> back kernel; one stream."""
@@ -266,13 +258,9 @@ class OverrideMixin:
                 continue
             dq, dmap = st['dec'][j]
             c = cl[D - j]
-            if j == 0:
-                self._conv('V' + lab[1:] + '.s2', dq, dact_a, skip, c, 2 * c, None, 0, 0, n, hh, ww, b['dtmp'][j], nl, algo, bmap=dmap)
-            else:
-                self._conv('V' + lab[1:] + '.s2', dq, dact_a, x, cx, cx, skip, c, 2 * c, n, hh, ww, b['dtmp'][j], nl, algo, bmap=dmap)
+            srcs = (skip, c, 2 * c, None, 0, 0) if j == 0 else (x, cx, cx, skip, c, 2 * c)
+            x, cx = self._dec_block_plain(b, j, lab, dq, dact_a, db, dact_b, srcs, n, hh, ww, algo, 'V' + lab[1:] + '.s2', dmap)
             hh, ww = hh * 2, ww * 2
-            self._conv(lab + '.s1', db, dact_b, b['dtmp'][j], nl, nl, None, 0, 0, n, hh, ww, b['dec'][j], db.n_ch_out, algo)
-            x, cx = b['dec'][j], db.n_ch_out
         (da, _), (db, _) = q.layers[D + U].convs()
         head = q.layers[-1]
         db.build(4, dev)
@@ -285,17 +273,7 @@ class OverrideMixin:
 
         def back(pred):
             self._launch('F.back', nbytes, C.back_forward_map, *back_args, pred, **back_kw)
-        out = self._pred_out if not self._tuning else None
-        if out is None:
-            back(b['pred'])
-            return b['pred'], b
-        b['back_infer'] = back
-        paused = C.tape_pause()
-        try:
-            back(out)
-        finally:
-            C.tape_resume(paused)
-        return out, b
+        return self._emit_back(b, 'back_infer', back)
 
 
 OverrideMixin._serial = [1]
