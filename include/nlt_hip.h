@@ -264,6 +264,63 @@ int nlt_barron_loss(const float* pred, const float* gt, int n, int h, int w, flo
 /* out[f,:] = x[f,:] * scale[f] */
 int nlt_scale_rows(const float* x, const float* scale, int n, long per_row, float* out, void* stream);
 
+/* ---- Deterministic mode (`deterministic = true`): siblings of the train-step entry points above that end in float atomics.
+ * Every sum runs in an order fixed by shapes and launch geometry alone, so a train step repeats bit for bit.  Each takes a
+ * caller-supplied workspace whose size depends on shapes only; nothing is allocated and nothing read back to the host
+ * (capturable in a hipGraph).  The arithmetic per term is that of the sibling; only the order in which terms meet differs.
+ *
+ * nlt_warp_backward_det: same arguments and result as nlt_warp_backward (same weights, texel (0,0) and zero-weight
+ * corners skipped; dpred fully written, no zero-fill needed).  The contributions of each texel are collected (integer
+ * counters, exclusive scan, integer cursors), sorted by key = camera pixel * 4 + corner and added in ascending key order.
+ * Unsupported when n*hc*wc >= 2^29. */
+long nlt_warp_backward_det_workspace_bytes(int n, int uvh, int uvw, int hc, int wc);
+int nlt_warp_backward_det(const float* dpred_cam, const float* warp, int n, int uvh, int uvw, int hc, int wc,
+                          float* dpred, void* workspace, long workspace_bytes, void* stream);
+
+/* nlt_resize_bilinear_backward in gather form: one thread per element of dx adds the taps of the output pixels whose footprint
+ * holds it, in ascending (oy, ox); weights formed as nlt_resize_bilinear_backward forms them.  No workspace, no zero-fill. */
+int nlt_resize_bilinear_backward_gather(const float* dout, int n, int h, int w, int c, int oh, int ow, float* dx,
+                                        void* stream);
+
+/* The three L2 sums with the workgroup partials in workspace slots (frame, workgroup), added by one ordered pass.
+ * workspace: nlt_loss_det_workspace_floats(n) floats. */
+long nlt_loss_det_workspace_floats(int n);
+int nlt_l2_loss_forward_det(const float* pred, const float* gt, int n, long per_example, float* loss,
+                            float* workspace, long workspace_floats, void* stream);
+int nlt_l2_loss_weighted_forward_det(const float* pred, const float* gt, const float* weights, int n, long hw, int c,
+                                     float* loss, float* workspace, long workspace_floats, void* stream);
+int nlt_l2_train_loss_det(const float* pred, const float* rgb, const float* fg, int n, long per_example, float inv_global_bs,
+                          float* gt, float* dpred, float* loss, float* workspace, long workspace_floats, void* stream);
+
+/* nlt_barron_loss with the per-frame Charbonnier sums through slots (nlt_barron_det_slots_floats(n,h,w) floats) and the
+ * adjoint of axes shorter than 6 in gather form.  workspace: as nlt_barron_loss. */
+long nlt_barron_det_slots_floats(int n, int h, int w);
+int nlt_barron_loss_det(const float* pred, const float* gt, int n, int h, int w, float* workspace,
+                        float* loss, float* dpred_unit, float* slots, long slots_floats, void* stream);
+
+/* nlt_stem_backward / nlt_head_backward / nlt_conv_backward_weights without float atomics: per-thread partials meet in LDS rows
+ * in lane order, per-workgroup (per row slice) partials in the workspace in workgroup (slice) order.  Gradients are
+ * ACCUMULATED into dw / db like the siblings'. */
+long nlt_stem_backward_det_workspace_floats(int n, int h, int w, int c);
+int nlt_stem_backward_det(const float* base, const float* cvis, const float* lvis, const float* nn_rgb,
+                          const float* nn_base, const float* obs_weights, int n, int k, int h, int w, int c,
+                          const float* dfm0, const float* dobs0_partial,
+                          float* dwq, float* dbq, float* dwo, float* dbo, float* workspace, long workspace_floats,
+                          void* stream);
+long nlt_head_backward_det_workspace_floats(int n, int h, int w, int cd, int cs);
+int nlt_head_backward_det(const float* dec, int ldd, int cd, const float* skip, int lds, int cs,
+                          const float* w_keras, const float* dpred, int n, int h, int w,
+                          float* d_dec, int ldgd, float* d_skip, int ldgs, float* dw, float* db,
+                          float* workspace, long workspace_floats, void* stream);
+long nlt_conv_backward_weights_det_workspace_floats(int mode, int c0, int c1, int n, int h, int w, int cout);
+int nlt_conv_backward_weights_det(int mode, int algo,
+                                  const float* src0, int ld0, int c0,
+                                  const float* src1, int ld1, int c1,
+                                  int n, int h, int w,
+                                  const float* dpre, int ldp, int cout,
+                                  float* dw_keras, float* dbias, float* workspace, long workspace_floats,
+                                  void* stream);
+
 /*
  * bf16 middle of the network (BASELINE config 5): the conv family on v_mfma_f32_16x16x32_bf16 with fp32 accumulation,
  * bf16-STORED activations between layers, fp32 bias + LeakyReLU on the accumulator.  Same modes, geometry, virtual

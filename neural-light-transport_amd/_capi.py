@@ -153,6 +153,24 @@ SIGNATURES = {
     'nlt_psnr_sums': (_c_int, [_vp, _vp, _vp, _c_long, _c_int, _vp, _vp, _vp]),
     'nlt_gather_frames_u8': (_c_int, [_vp, _vp, _c_int, _c_long, _vp, _vp]),
     'nlt_assemble_batch': (_c_int, [_vp] * 6 + [_c_int, _c_int, _c_long, _c_int] + [_vp] * 6 + [_vp]),
+    # deterministic mode (csrc/deterministic.hip and the owning files): atomic-free siblings, caller-supplied workspaces
+    'nlt_warp_backward_det_workspace_bytes': (_c_long, [_c_int] * 5),
+    'nlt_warp_backward_det': (_c_int, [_vp, _vp] + [_c_int] * 5 + [_vp, _vp, _c_long, _vp]),
+    'nlt_resize_bilinear_backward_gather': (_c_int, [_vp] + [_c_int] * 6 + [_vp, _vp]),
+    'nlt_loss_det_workspace_floats': (_c_long, [_c_int]),
+    'nlt_l2_loss_forward_det': (_c_int, [_vp, _vp, _c_int, _c_long, _vp, _vp, _c_long, _vp]),
+    'nlt_l2_loss_weighted_forward_det': (_c_int, [_vp, _vp, _vp, _c_int, _c_long, _c_int, _vp, _vp, _c_long, _vp]),
+    'nlt_l2_train_loss_det': (_c_int, [_vp, _vp, _vp, _c_int, _c_long, _c_float, _vp, _vp, _vp, _vp, _c_long, _vp]),
+    'nlt_barron_det_slots_floats': (_c_long, [_c_int] * 3),
+    'nlt_barron_loss_det': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _c_long, _vp]),
+    'nlt_stem_backward_det_workspace_floats': (_c_long, [_c_int] * 4),
+    'nlt_stem_backward_det': (_c_int, [_vp] * 6 + [_c_int] * 5 + [_vp] * 6 + [_vp, _c_long, _vp]),
+    'nlt_head_backward_det_workspace_floats': (_c_long, [_c_int] * 5),
+    'nlt_head_backward_det': (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _c_int, _c_int, _c_int,
+                                       _vp, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_long, _vp]),
+    'nlt_conv_backward_weights_det_workspace_floats': (_c_long, [_c_int] * 7),
+    'nlt_conv_backward_weights_det': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int,
+                                               _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_long, _vp]),
 }
 
 _real = None
@@ -566,7 +584,46 @@ def mul_forward(a, b):
 
 
 # ---------------------------------------------------------------- train step
+# Deterministic mode (`deterministic = true`, models/nlt.py): while it is on for this thread, the adapters below whose kernels end
+# in float atomics hand their arguments to the atomic-free `_det` / `_gather` siblings instead (+ a workspace from `_det_ws`).
+# A case with no sibling raises NotImplementedError and names the kernel: nothing falls back to atomics silently.
+class deterministic_scope:
+    """`with deterministic_scope(on):` -- the mode of this thread's calls inside the block (nesting restores the outer value)."""
+
+    def __init__(self, on):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = getattr(_tls, 'det', False)
+        _tls.det = self.on
+        return self
+
+    def __exit__(self, *exc):
+        _tls.det = self.prev
+        return False
+
+
+def deterministic():
+    return getattr(_tls, 'det', False)
+
+
+def _det_ws(name, device, floats):
+    """Workspace of a deterministic entry point: cached per (kernel family, stream, device) like the other two-pass
+    reductions' scratch -- a stable address (launch tapes and captured graphs point at it), sized from shapes."""
+    return _workspace('det.%s.%d' % (name, _stream()), device, max(int(floats), 1))
+
+
 def conv_backward_weights(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, dpre, ldp, cout, dw, db, algo=ALGO_AUTO):
+    if deterministic():
+        need = lib().nlt_conv_backward_weights_det_workspace_floats(mode, c0, c1, n, h, w, cout)
+        if need <= 0:
+            raise NotImplementedError("deterministic mode: wgrad_mfma_kernel / wgrad_direct_kernel (nlt_conv_backward_weights) has no "
+                                      "atomic-free form for mode %d, c0 %d, c1 %d, cout %d" % (mode, c0, c1, cout))
+        ws = _det_ws('wgrad', dpre.device, need)
+        _check(lib().nlt_conv_backward_weights_det(mode, algo, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
+                                                   _ptr(dpre), ldp, cout, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
+               'nlt_conv_backward_weights_det')
+        return
     _check(lib().nlt_conv_backward_weights(mode, algo, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
                                            _ptr(dpre), ldp, cout, _ptr(dw), _ptr(db), _stream()),
            'nlt_conv_backward_weights')
@@ -650,18 +707,50 @@ def level_split_backward(dfm, fm_y, ld, obs_y, obs_weights, dobs_partial, n, k, 
 
 
 def stem_backward(base, cvis, lvis, nn_rgb, nn_base, obs_weights, n, k, h, w, c, dfm0, dobs0, dwq, dbq, dwo, dbo):
+    if deterministic():
+        need = lib().nlt_stem_backward_det_workspace_floats(n, h, w, c)
+        if need <= 0:
+            raise NotImplementedError("deterministic mode: stem_bwd_kernel (nlt_stem_backward) has no atomic-free form for c = %d" % c)
+        ws = _det_ws('stem', dfm0.device, need)
+        _check(lib().nlt_stem_backward_det(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), _ptr(obs_weights),
+                                           n, k, h, w, c, _ptr(dfm0), _ptr(dobs0), _ptr(dwq), _ptr(dbq), _ptr(dwo), _ptr(dbo),
+                                           _ptr(ws), ws.numel(), _stream()), 'nlt_stem_backward_det')
+        return
     _check(lib().nlt_stem_backward(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), _ptr(obs_weights),
                                    n, k, h, w, c, _ptr(dfm0), _ptr(dobs0), _ptr(dwq), _ptr(dbq), _ptr(dwo), _ptr(dbo),
                                    _stream()), 'nlt_stem_backward')
 
 
 def head_backward(dec, ldd, cd, skip, lds, cs, w_keras, dpred, n, h, w, d_dec, ldgd, d_skip, ldgs, dw, db):
+    if deterministic():
+        need = lib().nlt_head_backward_det_workspace_floats(n, h, w, cd, cs)
+        if need <= 0:
+            raise NotImplementedError("deterministic mode: head_bwd_kernel (nlt_head_backward) has no atomic-free form for "
+                                      "cd = %d, cs = %d" % (cd, cs))
+        ws = _det_ws('head', dpred.device, need)
+        _check(lib().nlt_head_backward_det(_ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(_dense(dpred, 'dpred')),
+                                           n, h, w, _ptr(d_dec), ldgd, _ptr(d_skip), ldgs, _ptr(dw), _ptr(db),
+                                           _ptr(ws), ws.numel(), _stream()), 'nlt_head_backward_det')
+        return
     _check(lib().nlt_head_backward(_ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(_dense(dpred, 'dpred')),
                                    n, h, w, _ptr(d_dec), ldgd, _ptr(d_skip), ldgs, _ptr(dw), _ptr(db), _stream()),
            'nlt_head_backward')
 
 
+def warp_backward_det(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred):
+    """nlt_warp_backward with each texel's contributions added in ascending (camera pixel, corner) order: bit-repeatable."""
+    need = lib().nlt_warp_backward_det_workspace_bytes(n, uvh, uvw, hc, wc)
+    if need <= 0:
+        raise NotImplementedError("deterministic mode: warp_bwd_kernel (nlt_warp_backward) has no atomic-free form for %d x %d x %d "
+                                  "camera pixels (>= 2^29)" % (n, hc, wc))
+    ws = _det_ws('warp', dpred.device, (need + 3) // 4)
+    _check(lib().nlt_warp_backward_det(_ptr(_dense(dpred_cam, 'dpred_cam')), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc,
+                                       _ptr(dpred), _ptr(ws), 4 * ws.numel(), _stream()), 'nlt_warp_backward_det')
+
+
 def warp_backward(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred):
+    if deterministic():
+        return warp_backward_det(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred)
     _check(lib().nlt_warp_backward(_ptr(_dense(dpred_cam, 'dpred_cam')), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc,
                                    _ptr(dpred), _stream()), 'nlt_warp_backward')
 
@@ -669,6 +758,10 @@ def warp_backward(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred):
 def resize_bilinear_backward(dout, h, w):
     n, oh, ow, c = dout.shape
     dx = torch.empty((n, h, w, c), device=dout.device, dtype=torch.float32)
+    if deterministic():
+        _check(lib().nlt_resize_bilinear_backward_gather(_ptr(_dense(dout, 'dout')), n, h, w, c, oh, ow, _ptr(dx), _stream()),
+               'nlt_resize_bilinear_backward_gather')
+        return dx
     _check(lib().nlt_resize_bilinear_backward(_ptr(_dense(dout, 'dout')), n, h, w, c, oh, ow, _ptr(dx), _stream()),
            'nlt_resize_bilinear_backward')
     return dx
@@ -678,6 +771,11 @@ def l2_loss_forward(pred, gt):
     _same_shape(pred, gt, 'l2_loss_forward')
     n = pred.shape[0]
     loss = torch.empty(n, device=pred.device, dtype=torch.float32)
+    if deterministic():
+        ws = _det_ws('loss', pred.device, lib().nlt_loss_det_workspace_floats(n))
+        _check(lib().nlt_l2_loss_forward_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, pred[0].numel(),
+                                             _ptr(loss), _ptr(ws), ws.numel(), _stream()), 'nlt_l2_loss_forward_det')
+        return loss
     _check(lib().nlt_l2_loss_forward(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, pred[0].numel(),
                                      _ptr(loss), _stream()), 'nlt_l2_loss_forward')
     return loss
@@ -688,6 +786,12 @@ def l2_train_loss(pred, rgb, fg, global_bs):
     _same_shape(pred, rgb, 'l2_train_loss'); _same_shape(pred, fg, 'l2_train_loss')
     gt, dpred = torch.empty_like(pred), torch.empty_like(pred)
     loss = torch.empty((), device=pred.device, dtype=torch.float32)
+    if deterministic():
+        ws = _det_ws('loss', pred.device, lib().nlt_loss_det_workspace_floats(pred.shape[0]))
+        _check(lib().nlt_l2_train_loss_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(rgb, 'rgb')), _ptr(_dense(fg, 'fg')), pred.shape[0],
+                                           pred[0].numel(), 1.0 / float(global_bs), _ptr(gt), _ptr(dpred), _ptr(loss),
+                                           _ptr(ws), ws.numel(), _stream()), 'nlt_l2_train_loss_det')
+        return loss, gt, dpred
     _check(lib().nlt_l2_train_loss(_ptr(_dense(pred, 'pred')), _ptr(_dense(rgb, 'rgb')), _ptr(_dense(fg, 'fg')), pred.shape[0],
                                    pred[0].numel(), 1.0 / float(global_bs), _ptr(gt), _ptr(dpred), _ptr(loss), _stream()),
            'nlt_l2_train_loss')
@@ -712,6 +816,12 @@ def l2_loss_weighted_forward(pred, gt, weights):
     if weights.numel() != n * hw:
         raise NLTError("l2_loss_weighted_forward: %d weights for %d texels" % (weights.numel(), n * hw))
     loss = torch.empty(n, device=pred.device, dtype=torch.float32)
+    if deterministic():
+        ws = _det_ws('loss', pred.device, lib().nlt_loss_det_workspace_floats(n))
+        _check(lib().nlt_l2_loss_weighted_forward_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')),
+                                                      _ptr(_dense(weights, 'weights')), n, hw, c, _ptr(loss), _ptr(ws), ws.numel(),
+                                                      _stream()), 'nlt_l2_loss_weighted_forward_det')
+        return loss
     _check(lib().nlt_l2_loss_weighted_forward(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), _ptr(_dense(weights, 'weights')),
                                               n, hw, c, _ptr(loss), _stream()), 'nlt_l2_loss_weighted_forward')
     return loss
@@ -741,6 +851,11 @@ def barron_loss(pred, gt, want_grad):
     ws = torch.empty(nws, device=pred.device, dtype=torch.float32)
     loss = torch.empty(n, device=pred.device, dtype=torch.float32)
     dunit = torch.empty_like(pred) if want_grad else None
+    if deterministic():
+        slots = _det_ws('barron', pred.device, lib().nlt_barron_det_slots_floats(n, h, w))
+        _check(lib().nlt_barron_loss_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(ws), _ptr(loss),
+                                         _ptr(dunit), _ptr(slots), slots.numel(), _stream()), 'nlt_barron_loss_det')
+        return loss, dunit
     _check(lib().nlt_barron_loss(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(ws), _ptr(loss),
                                  _ptr(dunit), _stream()), 'nlt_barron_loss')
     return loss, dunit

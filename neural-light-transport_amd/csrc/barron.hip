@@ -107,8 +107,11 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // band [n*3 planes][count]: loss[f] += sum rho(w) * inv_total ; band <- rho'(w) * inv_total (in place)
 // rho(w) = sqrt((w/c)^2 + 1) - 1, rho'(w) = (w/c^2) / sqrt((w/c)^2 + 1).   blockIdx.y = frame.
-__global__ __launch_bounds__(256) void charbonnier_kernel(float* band, long per_frame, float inv_total, int want_grad,
-                                                          float* loss) {
+// DET (deterministic mode): `loss` is the launch's block of partial-sum slots, [frame][slots_per_frame] floats, and the
+// workgroup's sum goes to slot (frame, workgroup) instead of into a float atomic; loss_from_slots_kernel adds them in order.
+template <bool DET>
+__device__ __forceinline__ void charbonnier_body(float* band, long per_frame, float inv_total, int want_grad,
+                                                 float* loss, int slots_per_frame) {
   __shared__ float ws[4];
   const int f = blockIdx.y;
   float* w = band + (long)f * per_frame;
@@ -122,7 +125,19 @@ __global__ __launch_bounds__(256) void charbonnier_kernel(float* band, long per_
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss + f, (ws[0] + ws[1] + ws[2] + ws[3]) * inv_total);
+  if (threadIdx.x == 0) {
+    const float part = (ws[0] + ws[1] + ws[2] + ws[3]) * inv_total;
+    if (DET) loss[(long)f * slots_per_frame + blockIdx.x] = part; else atomicAdd(loss + f, part);
+  }
+}
+
+__global__ __launch_bounds__(256) void charbonnier_kernel(float* band, long per_frame, float inv_total, int want_grad,
+                                                          float* loss) {
+  charbonnier_body<false>(band, per_frame, inv_total, want_grad, loss, 0);
+}
+__global__ __launch_bounds__(256) void charb_det_kernel(float* band, long per_frame, float inv_total, int want_grad,
+                                                        float* slots, int slots_per_frame) {
+  charbonnier_body<true>(band, per_frame, inv_total, want_grad, slots, slots_per_frame);
 }
 
 __global__ void add_const_kernel(float* loss, int n, float c) {
@@ -148,9 +163,11 @@ __global__ __launch_bounds__(256) void grad_finish_kernel(const float* __restric
 // is final fused in: blockIdx.z = 0: rows of `lo` -> (LL, LH), 1: rows of `hi` -> (HL, HH); blockIdx.y = frame.
 // LH / HL / HH are final at every level, LL only at the last one (`ll_final`).  Same sums, same order as dwt_axis_kernel +
 // charbonnier_kernel (the per-frame loss is accumulated with float atomics there as well).
-__global__ __launch_bounds__(256) void dwt_cols_charb_kernel(const float* __restrict__ lo_rows, const float* __restrict__ hi_rows,
-                                                             int hl, int hh, int w, float* LL, float* LH, float* HL, float* HH,
-                                                             int ll_final, float inv_total, int want_grad, float* loss) {
+template <bool DET>
+__device__ __forceinline__ void dwt_cols_charb_body(const float* __restrict__ lo_rows, const float* __restrict__ hi_rows,
+                                                    int hl, int hh, int w, float* LL, float* LH, float* HL, float* HH,
+                                                    int ll_final, float inv_total, int want_grad, float* loss,
+                                                    int slots_per_frame) {
   __shared__ float red[4];
   const int z = blockIdx.z, f = blockIdx.y;
   const int A = z == 0 ? hl : hh;
@@ -191,7 +208,63 @@ __global__ __launch_bounds__(256) void dwt_cols_charb_kernel(const float* __rest
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss + f, (red[0] + red[1] + red[2] + red[3]) * inv_total);
+  if (threadIdx.x == 0) {
+    const float part = (red[0] + red[1] + red[2] + red[3]) * inv_total;
+    if (DET) loss[(long)f * slots_per_frame + blockIdx.z * gridDim.x + blockIdx.x] = part; else atomicAdd(loss + f, part);
+  }
+}
+
+__global__ __launch_bounds__(256) void dwt_cols_charb_kernel(const float* __restrict__ lo_rows, const float* __restrict__ hi_rows,
+                                                             int hl, int hh, int w, float* LL, float* LH, float* HL, float* HH,
+                                                             int ll_final, float inv_total, int want_grad, float* loss) {
+  dwt_cols_charb_body<false>(lo_rows, hi_rows, hl, hh, w, LL, LH, HL, HH, ll_final, inv_total, want_grad, loss, 0);
+}
+__global__ __launch_bounds__(256) void dwt_cols_det_kernel(const float* __restrict__ lo_rows, const float* __restrict__ hi_rows,
+                                                           int hl, int hh, int w, float* LL, float* LH, float* HL, float* HH,
+                                                           int ll_final, float inv_total, int want_grad, float* slots,
+                                                           int slots_per_frame) {
+  dwt_cols_charb_body<true>(lo_rows, hi_rows, hl, hh, w, LL, LH, HL, HH, ll_final, inv_total, want_grad, slots, slots_per_frame);
+}
+
+// Deterministic mode: loss[f] = c + slot 0 + slot 1 + ... of the frame, in slot order = launch order, then workgroup order
+__global__ void loss_from_slots_kernel(const float* __restrict__ slots, int n, int slots_per_frame, float c, float* loss) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= n) return;
+  float s = c;
+  for (int i = 0; i < slots_per_frame; ++i) s += slots[(long)f * slots_per_frame + i];
+  loss[f] = s;
+}
+
+// Deterministic mode, axes shorter than 6 (where dwt_T_gather's at-most-one-reflection argument does not hold): the adjoint of
+// dwt_axis_kernel in gather form by brute force -- one thread per INPUT element walks every output and tap of its line in a
+// fixed order and keeps those whose reflected position is its own.  Such axes are a few elements long.
+__global__ __launch_bounds__(256) void dwt_axis_T_gather_kernel(const float* __restrict__ dlo, const float* __restrict__ dhi,
+                                                                int A, int B, int axis, long total, float* __restrict__ din) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int n = axis == 0 ? A : B;
+  const int nl = n_lo(n), nh = n_hi(n);
+  const int b = idx % B;
+  const int a = (idx / B) % A;
+  const long pl = idx / ((long)A * B);
+  const int i = axis == 0 ? a : b;
+  const int oA = axis == 0 ? nl : A, oB = axis == 0 ? B : nl;
+  const int hA = axis == 0 ? nh : A, hB = axis == 0 ? B : nh;
+  const long lo_stride = axis == 0 ? oB : 1, hi_stride = axis == 0 ? hB : 1;
+  const float* glo = dlo + pl * (long)oA * oB + (axis == 0 ? b : (long)a * oB);
+  const float* ghi = dhi + pl * (long)hA * hB + (axis == 0 ? b : (long)a * hB);
+  float s = 0.f;
+  for (int j = 0; j < nl; ++j) {
+    const float gl = glo[(long)j * lo_stride];
+    for (int t = 0; t < 9; ++t)
+      if (reflect(2 * j + t - 4, n) == i) s += kLO[t] * gl;
+  }
+  for (int j = 0; j < nh; ++j) {
+    const float gh = ghi[(long)j * hi_stride];
+    for (int t = 0; t < 7; ++t)
+      if (reflect(2 * j + 1 + t - 3, n) == i) s += kHI[t] * gh;
+  }
+  din[idx] = s;
 }
 
 // Adjoint of one analysis pass in GATHER form: one thread per element of the pass's INPUT adds the (tap, coefficient) pairs
@@ -285,8 +358,29 @@ extern "C" long nlt_barron_workspace_floats(int n, int h, int w) {
   return layout(n, h, w, lv, &x0);
 }
 
-extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h, int w, float* workspace,
-                               float* loss, float* dpred_unit, void* stream) {
+namespace {
+
+inline unsigned charb_blocks(long per_frame) { long bx = (per_frame + 255) / 256; return (unsigned)(bx > 48 ? 48 : bx); }
+
+// partial-sum slots per frame of the deterministic form: one per workgroup of every launch that adds to the loss, in launch order
+int det_slots_per_frame(const Level* lv) {
+  int slots = 0;
+  for (int l = 0; l < kLevels; ++l) {
+    const Level& L = lv[l];
+    const bool last = l == kLevels - 1;
+    if (L.hh > 0) {
+      slots += 2 * (int)charb_blocks(3l * L.hl * L.wl);
+    } else {
+      if ((long)L.hl * L.wh > 0) slots += (int)charb_blocks(3l * L.hl * L.wh);
+      if (last) slots += (int)charb_blocks(3l * L.hl * L.wl);
+    }
+  }
+  return slots;
+}
+
+// slots == nullptr: the float-atomic form (nlt_barron_loss); otherwise the deterministic one (nlt_barron_loss_det)
+int barron_impl(const float* pred, const float* gt, int n, int h, int w, float* workspace, float* loss, float* dpred_unit,
+                float* slots, void* stream) {
   if (!pred || !gt || !workspace || !loss || n <= 0) return NLT_ERR_BAD_ARG;
   // wavelet.get_max_num_levels: ceil(log2(min size)) >= 5 levels
   int mn = h < w ? h : w;
@@ -298,17 +392,27 @@ extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h,
   const long P = (long)n * 3;
   const int want_grad = dpred_unit != nullptr;
   const float inv_total = 1.f / ((float)h * (float)w * 3.f);
+  const bool det = slots != nullptr;
+  const int spf = det ? det_slots_per_frame(lv) : 0;
+  int slot = 0;                                                        // first slot (within a frame) of the next loss-adding launch
+  const float nll_const = (float)(log((double)kScale) + kLogZ1);
   // the NLL's constant first (every later pass adds its Charbonnier sums to it): no zero-fill + add-constant pair
-  hipLaunchKernelGGL(init_loss_kernel, dim3((n + 63) / 64), dim3(64), 0, s, loss, n, (float)(log((double)kScale) + kLogZ1));
+  if (!det) hipLaunchKernelGGL(init_loss_kernel, dim3((n + 63) / 64), dim3(64), 0, s, loss, n, nll_const);
   {
     const long total = (long)n * h * w;
     hipLaunchKernelGGL(residual_syuv_kernel, dim3(blocks_for(total)), dim3(256), 0, s, pred, gt, h * w, total, ws + x0);
   }
   auto charb = [&](long off, long per_plane) {
     const long per_frame = per_plane * 3;
-    long bx = (per_frame + 255) / 256; if (bx > 48) bx = 48;
-    hipLaunchKernelGGL(charbonnier_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, s, ws + off, per_frame,
-                       inv_total, want_grad, loss);
+    const unsigned bx = charb_blocks(per_frame);
+    if (det) {
+      hipLaunchKernelGGL(charb_det_kernel, dim3(bx, (unsigned)n), dim3(256), 0, s, ws + off, per_frame,
+                         inv_total, want_grad, slots + slot, spf);
+      slot += (int)bx;
+    } else {
+      hipLaunchKernelGGL(charbonnier_kernel, dim3(bx, (unsigned)n), dim3(256), 0, s, ws + off, per_frame,
+                         inv_total, want_grad, loss);
+    }
   };
   long xin = x0;
   for (int l = 0; l < kLevels; ++l) {
@@ -319,10 +423,15 @@ extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h,
     if (L.hh > 0) {
       // rows of `lo` -> (LL, LH), rows of `hi` -> (HL, HH), Charbonnier of the final bands: one launch
       const long per_frame = 3l * L.hl * L.wl;                         // hl >= hh: the z = 1 half exits early
-      unsigned bx = blocks_for(per_frame);
-      if (bx > 48) bx = 48;
-      hipLaunchKernelGGL(dwt_cols_charb_kernel, dim3(bx, (unsigned)n, 2), dim3(256), 0, s, ws + L.lo, ws + L.hi,
-                         L.hl, L.hh, L.w, ws + L.LL, ws + L.LH, ws + L.HL, ws + L.HH, last ? 1 : 0, inv_total, want_grad, loss);
+      const unsigned bx = charb_blocks(per_frame);
+      if (det) {
+        hipLaunchKernelGGL(dwt_cols_det_kernel, dim3(bx, (unsigned)n, 2), dim3(256), 0, s, ws + L.lo, ws + L.hi, L.hl, L.hh,
+                           L.w, ws + L.LL, ws + L.LH, ws + L.HL, ws + L.HH, last ? 1 : 0, inv_total, want_grad, slots + slot, spf);
+        slot += 2 * (int)bx;
+      } else {
+        hipLaunchKernelGGL(dwt_cols_charb_kernel, dim3(bx, (unsigned)n, 2), dim3(256), 0, s, ws + L.lo, ws + L.hi, L.hl, L.hh,
+                           L.w, ws + L.LL, ws + L.LH, ws + L.HL, ws + L.HH, last ? 1 : 0, inv_total, want_grad, loss);
+      }
     } else {
       hipLaunchKernelGGL(dwt_axis_kernel, dim3(blocks_for(P * L.hl * L.wl)), dim3(256), 0, s, ws + L.lo, L.hl, L.w, 1,
                          P * L.hl * L.wl, ws + L.LL, ws + L.LH);
@@ -331,6 +440,7 @@ extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h,
     }
     xin = L.LL;
   }
+  if (det) hipLaunchKernelGGL(loss_from_slots_kernel, dim3((n + 63) / 64), dim3(64), 0, s, slots, n, spf, nll_const, loss);
   NLT_CHECK_LAUNCH();
   if (!want_grad) return NLT_OK;
 
@@ -341,6 +451,12 @@ extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h,
     if (L.w >= 6 && L.hh > 0) {
       hipLaunchKernelGGL(dwt_cols_T_kernel, dim3(blocks_for(P * L.hl * L.w), 1, 2), dim3(256), 0, s, ws + L.LL, ws + L.LH,
                          ws + L.HL, ws + L.HH, L.hl, L.hh, L.w, P, ws + L.lo, ws + L.hi);
+    } else if (det) {
+      hipLaunchKernelGGL(dwt_axis_T_gather_kernel, dim3(blocks_for(P * L.hl * L.w)), dim3(256), 0, s, ws + L.LL, ws + L.LH,
+                         L.hl, L.w, 1, P * L.hl * L.w, ws + L.lo);
+      if (L.hh > 0)
+        hipLaunchKernelGGL(dwt_axis_T_gather_kernel, dim3(blocks_for(P * L.hh * L.w)), dim3(256), 0, s, ws + L.HL, ws + L.HH,
+                           L.hh, L.w, 1, P * L.hh * L.w, ws + L.hi);
     } else {
       if (hipMemsetAsync(ws + L.lo, 0, (size_t)P * L.hl * L.w * sizeof(float), s) != hipSuccess) return NLT_ERR_LAUNCH;
       if (hipMemsetAsync(ws + L.hi, 0, (size_t)P * L.hh * L.w * sizeof(float), s) != hipSuccess) return NLT_ERR_LAUNCH;
@@ -353,6 +469,9 @@ extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h,
     if (L.h >= 6) {
       hipLaunchKernelGGL(dwt_rows_T_kernel, dim3(blocks_for(P * L.h * L.w)), dim3(256), 0, s, ws + L.lo, ws + L.hi, L.h, L.w, P,
                          ws + dst);
+    } else if (det) {
+      hipLaunchKernelGGL(dwt_axis_T_gather_kernel, dim3(blocks_for(P * L.h * L.w)), dim3(256), 0, s, ws + L.lo, ws + L.hi,
+                         L.h, L.w, 0, P * L.h * L.w, ws + dst);
     } else {
       if (hipMemsetAsync(ws + dst, 0, (size_t)P * L.h * L.w * sizeof(float), s) != hipSuccess) return NLT_ERR_LAUNCH;
       hipLaunchKernelGGL(dwt_axis_T_kernel, dim3(blocks_for(P * L.hl * L.w)), dim3(256), 0, s, ws + L.lo, ws + L.hi,
@@ -365,4 +484,26 @@ extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h,
   }
   NLT_CHECK_LAUNCH();
   return NLT_OK;
+}
+
+}  // namespace
+
+extern "C" int nlt_barron_loss(const float* pred, const float* gt, int n, int h, int w, float* workspace,
+                               float* loss, float* dpred_unit, void* stream) {
+  return barron_impl(pred, gt, n, h, w, workspace, loss, dpred_unit, nullptr, stream);
+}
+
+// Deterministic form: per-workgroup Charbonnier sums in `slots` ([n][nlt_barron_det_slots_floats / n] floats) added in a fixed
+// order, and the adjoint of axes shorter than 6 in gather form.  Same workspace as nlt_barron_loss.
+extern "C" long nlt_barron_det_slots_floats(int n, int h, int w) {
+  if (n <= 0 || h < 2 || w < 2) return -1;
+  Level lv[kLevels]; long x0;
+  layout(n, h, w, lv, &x0);
+  return (long)n * det_slots_per_frame(lv);
+}
+
+extern "C" int nlt_barron_loss_det(const float* pred, const float* gt, int n, int h, int w, float* workspace,
+                                   float* loss, float* dpred_unit, float* slots, long slots_floats, void* stream) {
+  if (!slots || slots_floats < nlt_barron_det_slots_floats(n, h, w) || nlt_barron_det_slots_floats(n, h, w) <= 0) return NLT_ERR_BAD_ARG;
+  return barron_impl(pred, gt, n, h, w, workspace, loss, dpred_unit, slots, stream);
 }

@@ -255,8 +255,10 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 // loss[f] = mean_{h,w,c} (gt - pred)^2   (blockIdx.y = frame); loss zeroed by the launcher
-__global__ __launch_bounds__(256) void l2_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                     long per, float* loss) {
+// DET (deterministic mode): the workgroup's partial goes to slot (frame, blockIdx.x) of `loss` = a workspace instead of into one
+// float atomic per frame; loss_slots_kernel adds the slots in order.  Same for the two kernels below.
+template <bool DET>
+__device__ __forceinline__ void l2_fwd_body(const float* __restrict__ pred, const float* __restrict__ gt, long per, float* loss) {
   __shared__ float ws[4];
   const int f = blockIdx.y;
   float s = 0.f;
@@ -267,13 +269,26 @@ __global__ __launch_bounds__(256) void l2_fwd_kernel(const float* __restrict__ p
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss + f, (ws[0] + ws[1] + ws[2] + ws[3]) / (float)per);
+  if (threadIdx.x == 0) {
+    const float part = (ws[0] + ws[1] + ws[2] + ws[3]) / (float)per;
+    if (DET) loss[f * gridDim.x + blockIdx.x] = part; else atomicAdd(loss + f, part);
+  }
 }
 
 // Keras `sample_weight` on MeanSquaredError(reduction='none') (nlt/losses.py:42-43): the [N,H,W] per-texel loss (mean over the
 // c channels) times the weight map wt [N,H,W], then the mean over H,W: loss[f] = sum_px wt[px] * (sum_c d^2 / c) / hw
-__global__ __launch_bounds__(256) void l2w_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                      const float* __restrict__ wt, long hw, int c, float* loss) {
+__global__ __launch_bounds__(256) void l2_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                     long per, float* loss) {
+  l2_fwd_body<false>(pred, gt, per, loss);
+}
+__global__ __launch_bounds__(256) void l2_fwd_det_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                         long per, float* slots) {
+  l2_fwd_body<true>(pred, gt, per, slots);
+}
+
+template <bool DET>
+__device__ __forceinline__ void l2w_fwd_body(const float* __restrict__ pred, const float* __restrict__ gt,
+                                             const float* __restrict__ wt, long hw, int c, float* loss) {
   __shared__ float ws[4];
   const int f = blockIdx.y;
   float s = 0.f;
@@ -289,7 +304,19 @@ __global__ __launch_bounds__(256) void l2w_fwd_kernel(const float* __restrict__ 
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss + f, (ws[0] + ws[1] + ws[2] + ws[3]) / (float)hw);
+  if (threadIdx.x == 0) {
+    const float part = (ws[0] + ws[1] + ws[2] + ws[3]) / (float)hw;
+    if (DET) loss[f * gridDim.x + blockIdx.x] = part; else atomicAdd(loss + f, part);
+  }
+}
+
+__global__ __launch_bounds__(256) void l2w_fwd_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                      const float* __restrict__ wt, long hw, int c, float* loss) {
+  l2w_fwd_body<false>(pred, gt, wt, hw, c, loss);
+}
+__global__ __launch_bounds__(256) void l2w_fwd_det_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                          const float* __restrict__ wt, long hw, int c, float* slots) {
+  l2w_fwd_body<true>(pred, gt, wt, hw, c, slots);
 }
 
 // dpred = gloss[f] * wt[px] * 2 (pred - gt) / (c hw)
@@ -314,9 +341,10 @@ __global__ __launch_bounds__(256) void l2_bwd_kernel(const float* __restrict__ p
 // The l2 train step's loss glue in one pass (gt = rgb * fg; per-example mean square; sum over examples / global batch; its
 // gradient): replaces mul + l2 forward + sum + divide + their autograd mirror + l2 backward = 12 launches between the
 // resampler and the first backward kernel.  blockIdx.y = frame; loss (one float, zeroed by the launcher) += sum_f mean_f / gbs.
-__global__ __launch_bounds__(256) void l2_step_kernel(const float* __restrict__ pred, const float* __restrict__ rgb,
-                                                      const float* __restrict__ fg, long per, float inv_gbs,
-                                                      float* __restrict__ gt, float* __restrict__ dpred, float* loss) {
+template <bool DET>
+__device__ __forceinline__ void l2_step_body(const float* __restrict__ pred, const float* __restrict__ rgb,
+                                             const float* __restrict__ fg, long per, float inv_gbs,
+                                             float* __restrict__ gt, float* __restrict__ dpred, float* loss) {
   __shared__ float ws[4];
   const int f = blockIdx.y;
   float s = 0.f;
@@ -359,8 +387,33 @@ __global__ __launch_bounds__(256) void l2_step_kernel(const float* __restrict__ 
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(loss, (ws[0] + ws[1] + ws[2] + ws[3]) / (float)per * inv_gbs);
+  if (threadIdx.x == 0) {
+    const float part = (ws[0] + ws[1] + ws[2] + ws[3]) / (float)per * inv_gbs;
+    if (DET) loss[f * gridDim.x + blockIdx.x] = part; else atomicAdd(loss, part);
+  }
 }
+
+__global__ __launch_bounds__(256) void l2_step_kernel(const float* __restrict__ pred, const float* __restrict__ rgb,
+                                                      const float* __restrict__ fg, long per, float inv_gbs,
+                                                      float* __restrict__ gt, float* __restrict__ dpred, float* loss) {
+  l2_step_body<false>(pred, rgb, fg, per, inv_gbs, gt, dpred, loss);
+}
+__global__ __launch_bounds__(256) void l2_step_det_kernel(const float* __restrict__ pred, const float* __restrict__ rgb,
+                                                          const float* __restrict__ fg, long per, float inv_gbs,
+                                                          float* __restrict__ gt, float* __restrict__ dpred, float* slots) {
+  l2_step_body<true>(pred, rgb, fg, per, inv_gbs, gt, dpred, slots);
+}
+
+// Deterministic mode: out[r] = slots[r][0] + slots[r][1] + ... in slot order (one thread per row; rows are a few dozen long)
+__global__ __launch_bounds__(64) void loss_slots_kernel(const float* __restrict__ slots, int rows, int per_row, float* out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  float s = 0.f;
+  for (int i = 0; i < per_row; ++i) s += slots[(long)r * per_row + i];
+  out[r] = s;
+}
+
+constexpr int LOSS_DET_SLOTS = 48;          // workgroups per frame of the three loss kernels (their launchers' cap)
 
 // x[f, :] *= s[f]
 __global__ __launch_bounds__(256) void scale_rows_kernel(const float* __restrict__ x, const float* __restrict__ s,
@@ -587,6 +640,49 @@ extern "C" int nlt_adam_amsgrad_step(float* param, const float* grad, float* m, 
   if (!param || !grad || !m || !v || !vhat || count <= 0) return NLT_ERR_BAD_ARG;
   hipLaunchKernelGGL(adam_amsgrad_kernel, dim3(blocks_for(count)), dim3(256), 0, static_cast<hipStream_t>(stream),
                      param, grad, m, v, vhat, count, lr_t, beta1, beta2, eps);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+// ---- deterministic mode: the three L2 sums with workgroup partials in workspace slots (frame, workgroup) and one ordered pass
+extern "C" long nlt_loss_det_workspace_floats(int n) { return n > 0 ? (long)n * LOSS_DET_SLOTS : -1; }
+
+extern "C" int nlt_l2_loss_forward_det(const float* pred, const float* gt, int n, long per_example, float* loss,
+                                       float* workspace, long workspace_floats, void* stream) {
+  if (!pred || !gt || !loss || !workspace || n <= 0 || per_example <= 0 || workspace_floats < (long)n * LOSS_DET_SLOTS) return NLT_ERR_BAD_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  long bx = (per_example + 255) / 256;
+  if (bx > LOSS_DET_SLOTS) bx = LOSS_DET_SLOTS;
+  hipLaunchKernelGGL(l2_fwd_det_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, s, pred, gt, per_example, workspace);
+  hipLaunchKernelGGL(loss_slots_kernel, dim3((n + 63) / 64), dim3(64), 0, s, workspace, n, (int)bx, loss);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_l2_loss_weighted_forward_det(const float* pred, const float* gt, const float* weights, int n, long hw, int c,
+                                                float* loss, float* workspace, long workspace_floats, void* stream) {
+  if (!pred || !gt || !weights || !loss || !workspace || n <= 0 || hw <= 0 || c <= 0 || workspace_floats < (long)n * LOSS_DET_SLOTS)
+    return NLT_ERR_BAD_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  long bx = (hw + 255) / 256;
+  if (bx > LOSS_DET_SLOTS) bx = LOSS_DET_SLOTS;
+  hipLaunchKernelGGL(l2w_fwd_det_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, s, pred, gt, weights, hw, c, workspace);
+  hipLaunchKernelGGL(loss_slots_kernel, dim3((n + 63) / 64), dim3(64), 0, s, workspace, n, (int)bx, loss);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_l2_train_loss_det(const float* pred, const float* rgb, const float* fg, int n, long per_example, float inv_global_bs,
+                                     float* gt, float* dpred, float* loss, float* workspace, long workspace_floats, void* stream) {
+  if (!pred || !rgb || !fg || !gt || !dpred || !loss || !workspace || n <= 0 || per_example <= 0 ||
+      workspace_floats < (long)n * LOSS_DET_SLOTS) return NLT_ERR_BAD_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  long bx = (per_example + 255) / 256;
+  if (bx > LOSS_DET_SLOTS) bx = LOSS_DET_SLOTS;
+  hipLaunchKernelGGL(l2_step_det_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, s, pred, rgb, fg, per_example, inv_global_bs,
+                     gt, dpred, workspace);
+  // one row of n * bx slots, frame-major: the scalar is the ordered sum over frames and workgroups
+  hipLaunchKernelGGL(loss_slots_kernel, dim3(1), dim3(64), 0, s, workspace, 1, (int)(n * bx), loss);
   NLT_CHECK_LAUNCH();
   return NLT_OK;
 }

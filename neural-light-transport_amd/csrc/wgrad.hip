@@ -29,8 +29,10 @@ struct WgradP {
   int rows_per_split; // multiple of 4
 };
 
-template <int MODE, int KT, int NT>
-__global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradP w, int kgroups, int ngroups, int msplits) {
+// DET (deterministic mode): w.dw / w.db point at a workspace of `msplits` slices ([kw] weight and [N] bias-column partials each);
+// a wave STORES its partial sums into its row slice's copy and wgrad_det_reduce_kernel adds the slices in order.
+template <int MODE, int KT, int NT, bool DET>
+__device__ __forceinline__ void wgrad_mfma_body(const WgradP& w, int kgroups, int ngroups, int msplits, int kw) {
   constexpr int TAPS = ConvTraits<MODE>::TAPS;
   const ConvP& p = w.c;
   const int lane = threadIdx.x & 63;
@@ -134,7 +136,8 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradP w, int kgroups, 
       for (int r = 0; r < 4; ++r) {
         const int cl = cbase + r;
         if (cl >= cs) continue;
-        atomicAdd(w.dw + keras_widx<MODE>(t, (s1 ? p.c0 : 0) + cl, nt_col[nt], cin, p.cout), acc[kt][nt][r]);
+        const int wi = keras_widx<MODE>(t, (s1 ? p.c0 : 0) + cl, nt_col[nt], cin, p.cout);
+        if (DET) w.dw[(size_t)ms * kw + wi] = acc[kt][nt][r]; else atomicAdd(w.dw + wi, acc[kt][nt][r]);
       }
     }
   }
@@ -144,27 +147,72 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradP w, int kgroups, 
       float s = bsum[nt];
       s += __shfl_xor(s, 16);
       s += __shfl_xor(s, 32);
-      if (mm == 0 && nt_ok[nt]) atomicAdd(w.db + nt_oc[nt], s);
+      if (mm == 0 && nt_ok[nt]) {
+        if (DET) w.db[(size_t)ms * p.N + nt_col[nt]] = s; else atomicAdd(w.db + nt_oc[nt], s);
+      }
     }
   }
 }
 
 template <int MODE, int KT, int NT>
-int launch_tile(WgradP& w, hipStream_t s) {
+__global__ __launch_bounds__(256) void wgrad_mfma_kernel(WgradP w, int kgroups, int ngroups, int msplits) {
+  wgrad_mfma_body<MODE, KT, NT, false>(w, kgroups, ngroups, msplits, 0);
+}
+template <int MODE, int KT, int NT>
+__global__ __launch_bounds__(256) void wgrad_det_slices_kernel(WgradP w, int kgroups, int ngroups, int msplits, int kw) {
+  wgrad_mfma_body<MODE, KT, NT, true>(w, kgroups, ngroups, msplits, kw);
+}
+
+// row slices of a launch: enough for ~4 waves per SIMD, at least 64 rows (16 MFMA steps) per slice
+inline int wgrad_row_slices(int M, int kgroups, int ngroups, int* rows_per_split) {
+  long want = 4096 / ((long)kgroups * ngroups);
+  if (want < 1) want = 1;
+  long rows = (M + want - 1) / want;
+  if (rows < 64) rows = 64;
+  rows = (rows + 3) & ~3L;
+  *rows_per_split = (int)rows;
+  return (int)((M + rows - 1) / rows);
+}
+
+inline int wgrad_tile_of(int tiles) { return tiles >= 4 ? 4 : (tiles >= 2 ? 2 : 1); }
+
+// Deterministic mode: dw[i] += slice 0 + slice 1 + ... ; db[o] += the same over slices and (transposed k2s2) the 4 columns of o
+__global__ __launch_bounds__(256) void wgrad_det_reduce_kernel(const float* __restrict__ ws_w, const float* __restrict__ ws_b,
+                                                               int msplits, int kw, int N, int cout, float* dw, float* db) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < kw) {
+    float s = 0.f;
+    for (int ms = 0; ms < msplits; ++ms) s += ws_w[(size_t)ms * kw + i];
+    dw[i] += s;
+  } else if (db && i - kw < cout) {
+    const int o = i - kw;
+    float s = 0.f;
+    for (int ms = 0; ms < msplits; ++ms)
+      for (int col = o; col < N; col += cout) s += ws_b[(size_t)ms * N + col];
+    db[o] += s;
+  }
+}
+
+template <int MODE, int KT, int NT>
+int launch_tile(WgradP& w, hipStream_t s, float* det_ws) {
   const ConvP& p = w.c;
   const int ktiles = ConvTraits<MODE>::TAPS * (chunks16(p.c0) + chunks16(p.c1));
   const int ntiles = (p.N + 15) >> 4;
   const int kgroups = (ktiles + KT - 1) / KT;
   const int ngroups = (ntiles + NT - 1) / NT;
-  // enough row slices for ~4 waves per SIMD, at least 64 rows (16 MFMA steps) per slice
-  long want = 4096 / ((long)kgroups * ngroups);
-  if (want < 1) want = 1;
-  long rows = (p.M + want - 1) / want;
-  if (rows < 64) rows = 64;
-  rows = (rows + 3) & ~3L;
-  const int msplits = (int)((p.M + rows - 1) / rows);
-  w.rows_per_split = (int)rows;
+  const int msplits = wgrad_row_slices(p.M, kgroups, ngroups, &w.rows_per_split);
   const long waves = (long)kgroups * ngroups * msplits;
+  if (det_ws) {
+    const int kw = ConvTraits<MODE>::TAPS * (p.c0 + p.c1) * p.N;
+    float *dw = w.dw, *db = w.db;
+    w.dw = det_ws; w.db = db ? det_ws + (size_t)msplits * kw : nullptr;
+    hipLaunchKernelGGL((wgrad_det_slices_kernel<MODE, KT, NT>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
+                       w, kgroups, ngroups, msplits, kw);
+    hipLaunchKernelGGL(wgrad_det_reduce_kernel, dim3((unsigned)((kw + p.cout + 255) / 256)), dim3(256), 0, s, w.dw, w.db, msplits,
+                       kw, p.N, p.cout, dw, db);
+    NLT_CHECK_LAUNCH();
+    return NLT_OK;
+  }
   hipLaunchKernelGGL((wgrad_mfma_kernel<MODE, KT, NT>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s,
                      w, kgroups, ngroups, msplits);
   NLT_CHECK_LAUNCH();
@@ -172,13 +220,13 @@ int launch_tile(WgradP& w, hipStream_t s) {
 }
 
 template <int MODE>
-int launch_mode(WgradP& w, hipStream_t s) {
+int launch_mode(WgradP& w, hipStream_t s, float* det_ws = nullptr) {
   const ConvP& p = w.c;
   const int ktiles = ConvTraits<MODE>::TAPS * (chunks16(p.c0) + chunks16(p.c1));
   const int ntiles = (p.N + 15) >> 4;
-  const int KT = ktiles >= 4 ? 4 : (ktiles >= 2 ? 2 : 1);
-  const int NT = ntiles >= 4 ? 4 : (ntiles >= 2 ? 2 : 1);
-#define NLT_WT(K, N) if (KT == K && NT == N) return launch_tile<MODE, K, N>(w, s);
+  const int KT = wgrad_tile_of(ktiles);
+  const int NT = wgrad_tile_of(ntiles);
+#define NLT_WT(K, N) if (KT == K && NT == N) return launch_tile<MODE, K, N>(w, s, det_ws);
   NLT_WT(4, 4) NLT_WT(4, 2) NLT_WT(4, 1) NLT_WT(2, 4) NLT_WT(2, 2) NLT_WT(2, 1) NLT_WT(1, 4) NLT_WT(1, 2) NLT_WT(1, 1)
 #undef NLT_WT
   return NLT_ERR_UNSUPPORTED;
@@ -236,7 +284,123 @@ int launch_direct(WgradP& w, hipStream_t s) {
   return NLT_OK;
 }
 
+// Deterministic form of the direct fallback: one workgroup per weight-gradient element (and per bias element); its threads
+// walk the rows with a stride of 256, the 256 partial sums meet in a fixed tree, the single writer adds the result.
+template <int MODE>
+__global__ __launch_bounds__(256) void wgrad_direct_det_kernel(WgradP w, int KN) {
+  __shared__ float part[256];
+  const ConvP& p = w.c;
+  const int cin = p.c0 + p.c1;
+  const int e = blockIdx.x;
+  const bool is_bias = e >= KN;
+  int t = 0, c = 0, ncol = 0;
+  if (!is_bias) {
+    if (MODE == NLT_DECONV_K2S2) { c = e % cin; ncol = e / cin; }
+    else if (MODE == NLT_DECONV_K2S1) { c = e % cin; ncol = (e / cin) % p.cout; t = e / (cin * p.cout); }
+    else { ncol = e % p.cout; c = (e / p.cout) % cin; t = e / (p.cout * cin); }
+  }
+  const int col0 = is_bias ? e - KN : ncol, col_step = is_bias ? p.cout : p.N;    // bias o: its columns o, o + cout, ... (k2s2: 4)
+  float s = 0.f;
+  for (int m = threadIdx.x; m < p.M; m += 256) {
+    const int x = m % p.gw;
+    const int y = (m / p.gw) % p.gh;
+    const int f = m / (p.gw * p.gh);
+    for (int col = col0; col < p.N; col += col_step) {
+      size_t otex = (size_t)m;
+      int oc = col;
+      if (MODE == NLT_DECONV_K2S2) {
+        const int ab = col / p.cout; oc = col - ab * p.cout;
+        otex = ((size_t)f * p.oh + 2 * y + (ab >> 1)) * p.ow + 2 * x + (ab & 1);
+      }
+      const float g = w.dp[otex * w.ldp + oc];
+      if (is_bias) { s += g; continue; }
+      const int tex = conv_tap_texel<MODE>(p, f, y, x, t);
+      if (tex < 0) continue;
+      const float xv = c < p.c0 ? p.src0[(size_t)tex * p.ld0 + c] : p.src1[(size_t)tex * p.ld1 + (c - p.c0)];
+      s += xv * g;
+    }
+  }
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    if (!is_bias) w.dw[e] += part[0];
+    else w.db[e - KN] += part[0];
+  }
+}
+
+template <int MODE>
+int launch_direct_det(WgradP& w, hipStream_t s) {
+  const ConvP& p = w.c;
+  const int KN = ConvTraits<MODE>::TAPS * (p.c0 + p.c1) * p.N;
+  if (KN + p.N > 8192) return NLT_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(wgrad_direct_det_kernel<MODE>, dim3((unsigned)(KN + (w.db ? p.cout : 0))), dim3(256), 0, s, w, KN);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+int wgrad_taps(int mode) { return (mode == NLT_CONV1X1 || mode == NLT_DECONV_K2S2) ? 1 : 4; }
+
 }  // namespace
+
+// Deterministic sibling of nlt_conv_backward_weights (same arguments + a workspace): no float atomics, the row slices of the
+// MFMA form meet in slice order, the direct form has one writer per element.
+extern "C" long nlt_conv_backward_weights_det_workspace_floats(int mode, int c0, int c1, int n, int h, int w, int cout) {
+  if (mode < NLT_CONV1X1 || mode > NLT_DECONV_K2S1 || n <= 0 || h <= 0 || w <= 0 || c0 <= 0 || c1 < 0 || cout <= 0) return -1;
+  if ((c0 & 3) || (c1 & 3) || (cout & 3)) return 1;                    // direct form: no partial sums outside the launch
+  const int taps = wgrad_taps(mode);
+  const int N = mode == NLT_DECONV_K2S2 ? 4 * cout : cout;
+  const long M = mode == NLT_CONV_K2S2 ? (long)n * (h / 2) * (w / 2) : (long)n * h * w;
+  if (M >= (1l << 31)) return -1;
+  const int ktiles = taps * (chunks16(c0) + chunks16(c1)), ntiles = (N + 15) >> 4;
+  const int KT = wgrad_tile_of(ktiles), NT = wgrad_tile_of(ntiles);
+  int rows;
+  const int msplits = wgrad_row_slices((int)M, (ktiles + KT - 1) / KT, (ntiles + NT - 1) / NT, &rows);
+  return (long)msplits * ((long)taps * (c0 + c1) * N + N);
+}
+
+extern "C" int nlt_conv_backward_weights_det(int mode, int algo,
+                                             const float* src0, int ld0, int c0,
+                                             const float* src1, int ld1, int c1,
+                                             int n, int h, int w,
+                                             const float* dpre, int ldp, int cout,
+                                             float* dw_keras, float* dbias, float* workspace, long workspace_floats,
+                                             void* stream) {
+  if (!dpre || !dw_keras || !workspace) return NLT_ERR_BAD_ARG;
+  WgradP wp;
+  const int st = nlt_fill_conv_params(wp.c, mode, src0, ld0, c0, src1, ld1, c1, n, h, w, dw_keras, dw_keras, cout,
+                                      dw_keras, cout, 0, 0.f, nullptr, 0, 0);
+  if (st != NLT_OK) return st;
+  if (ldp < cout) return NLT_ERR_BAD_ARG;
+  const long need = nlt_conv_backward_weights_det_workspace_floats(mode, c0, c1, n, h, w, cout);
+  if (need <= 0 || workspace_floats < need) return NLT_ERR_BAD_ARG;
+  wp.dp = dpre; wp.ldp = ldp; wp.dw = dw_keras; wp.db = dbias; wp.rows_per_split = 0;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool mfma_ok = !(c0 & 3) && !(c1 & 3) && !(cout & 3);
+  if (algo == NLT_ALGO_AUTO) algo = mfma_ok ? NLT_ALGO_MFMA : NLT_ALGO_DIRECT;
+  if (algo == NLT_ALGO_MFMA) {
+    if (!mfma_ok) return NLT_ERR_UNSUPPORTED;
+    switch (mode) {
+      case NLT_CONV1X1: return launch_mode<NLT_CONV1X1>(wp, s, workspace);
+      case NLT_CONV_K2S2: return launch_mode<NLT_CONV_K2S2>(wp, s, workspace);
+      case NLT_CONV_K2S1: return launch_mode<NLT_CONV_K2S1>(wp, s, workspace);
+      case NLT_DECONV_K2S2: return launch_mode<NLT_DECONV_K2S2>(wp, s, workspace);
+      case NLT_DECONV_K2S1: return launch_mode<NLT_DECONV_K2S1>(wp, s, workspace);
+    }
+  } else if (algo == NLT_ALGO_DIRECT) {
+    switch (mode) {
+      case NLT_CONV1X1: return launch_direct_det<NLT_CONV1X1>(wp, s);
+      case NLT_CONV_K2S2: return launch_direct_det<NLT_CONV_K2S2>(wp, s);
+      case NLT_CONV_K2S1: return launch_direct_det<NLT_CONV_K2S1>(wp, s);
+      case NLT_DECONV_K2S2: return launch_direct_det<NLT_DECONV_K2S2>(wp, s);
+      case NLT_DECONV_K2S1: return launch_direct_det<NLT_DECONV_K2S1>(wp, s);
+    }
+  }
+  return NLT_ERR_BAD_ARG;
+}
 
 extern "C" int nlt_conv_backward_weights(int mode, int algo,
                                          const float* src0, int ld0, int c0,

@@ -1046,7 +1046,7 @@ class RenderPlan(OverrideMixin):
         if (self._tape_ok(reg, dpred.is_cuda) and obs_weights is None
                 and all(t.is_contiguous() for t in (dpred, base, cvis, lvis, nn_rgb, nn_base))):
             tkey = ('bwd', dpred.data_ptr(), base.data_ptr(), cvis.data_ptr(), lvis.data_ptr(), nn_rgb.data_ptr(),
-                    nn_base.data_ptr(), bool(b.get('train_fused')), self.bwd_streams, C._stream())
+                    nn_base.data_ptr(), bool(b.get('train_fused')), self.bwd_streams, C._stream(), C.deterministic())
         self._run_taped(b, reg, tkey, run, valid=lambda b, ent, reg: C.tape_valid(ent, reg.version), finish=lambda b: None)
 
     def _backward_streams(self, dpred, base, cvis, lvis, nn_rgb, nn_base, obs_weights, b, g, n, h, w, k):

@@ -49,12 +49,13 @@ class _GenericFn(torch.autograd.Function):
         n, hc, wc, _ = warp.shape
         m.flat_grads.zero_()
         if d_pred_c is not None:
-            d_pred_c = d_pred_c.contiguous()
-            if (hc, wc) != (m.imh, m.imw):
-                d_pred_c = C.resize_bilinear_backward(d_pred_c, hc, wc)
-            dpred = torch.empty((n, m.uvh, m.uvw, 3), device=base.device, dtype=torch.float32)
-            C.warp_backward(d_pred_c, warp, n, m.uvh, m.uvw, hc, wc, dpred)
-            ctx.tape.backward(ctx.out_node, dpred)          # (+ base and the corner zero are constants / masks of pred's warp)
+            with C.deterministic_scope(m.deterministic):
+                d_pred_c = d_pred_c.contiguous()
+                if (hc, wc) != (m.imh, m.imw):
+                    d_pred_c = C.resize_bilinear_backward(d_pred_c, hc, wc)
+                dpred = torch.empty((n, m.uvh, m.uvw, 3), device=base.device, dtype=torch.float32)
+                C.warp_backward(d_pred_c, warp, n, m.uvh, m.uvw, hc, wc, dpred)
+                ctx.tape.backward(ctx.out_node, dpred)      # (+ base and the corner zero are constants / masks of pred's warp)
         return m.flat_grads, None, None, None
 
 
@@ -116,6 +117,24 @@ class Model(BaseModel):
         self.use_graphs = os.environ.get('NLT_GRAPH', '0') == '1'
         self._graph = None              # {'key', 'hits', 'graph', 'out'}: the entry of `_graphs` used last
         self._graphs = {}               # input addresses (+ weights version ...) -> entry; a few staging slots' worth
+        # `deterministic = true` (not a reference key) / NLT_DETERMINISTIC=1 / model.deterministic = True before the first step:
+        # every sum of a train step in an order fixed by shapes and launch geometry -- the atomic-free siblings of the resampler
+        # / resize adjoints, the loss sums and the first-generation weight gradients (csrc/deterministic.hip), no plan-time
+        # timing trials.  A train step then repeats bit for bit, run to run and process to process.
+        self.deterministic = (config.getboolean('DEFAULT', 'deterministic', fallback=False)
+                              or os.environ.get('NLT_DETERMINISTIC', '0') == '1')
+
+    @property
+    def deterministic(self):
+        return self._deterministic
+
+    @deterministic.setter
+    def deterministic(self, on):
+        self._deterministic = bool(on)
+        if self._deterministic:
+            # the trials pick kernels and split-K forms by the clock, and a different choice rounds differently; choices
+            # loaded with plan.import_tuning / load_tuning stay honoured
+            self.plan.autotune = False
 
     def _init_loss(self):
         wloss = []
@@ -359,6 +378,10 @@ class Model(BaseModel):
         """Fills the flat gradient bucket from dL/d(pred_camspc): resize / warp (TFA resampler) adjoints, then the
         hand-ordered backward plan over the activations the last inference=False forward left behind."""
         base, cvis, lvis, warp, nn_rgb, nn_base, obs_weights = inputs
+        with C.deterministic_scope(self.deterministic):
+            self._render_backward_now(d_pred_c, base, cvis, lvis, warp, nn_rgb, nn_base, obs_weights, generation)
+
+    def _render_backward_now(self, d_pred_c, base, cvis, lvis, warp, nn_rgb, nn_base, obs_weights, generation):
         n, hc, wc, _ = warp.shape
         self.flat_grads.zero_()
         if d_pred_c is not None:
@@ -376,6 +399,10 @@ class Model(BaseModel):
         is differentiated, with autograd.grad -- no AccumulateGrad node, so the whole thing can be captured in a
         hipGraph): returns (loss summed over this rank's examples / global_bs, to_vis) and leaves the gradients in
         `flat_grads`.  Same arithmetic as `call(batch, 'train')` + `compute_loss` + `.backward()`."""
+        with C.deterministic_scope(self.deterministic):
+            return self._train_forward_backward(batch, global_bs)
+
+    def _train_forward_backward(self, batch, global_bs):
         id_, base, cvis, lvis, warp, rgb, rgb_camspc, nn_id, nn_base, nn_rgb, nn_rgb_camspc = batch
         if isinstance(base, ResidentTexels):                     # load_batch(resident=True): training reads the float buffers
             m = base.materialize()
@@ -544,8 +571,9 @@ class Model(BaseModel):
 
     def compute_loss(self, pred, gt, **kwargs):
         loss = 0
-        for weight, loss_func in self.wloss:
-            loss = loss + weight * loss_func(gt, pred, **kwargs)
+        with C.deterministic_scope(self.deterministic):         # (the loss kernels run in the forward; their backward has no sums)
+            for weight, loss_func in self.wloss:
+                loss = loss + weight * loss_func(gt, pred, **kwargs)
         return loss
 
     def vis_batch(self, data_dict, outdir, mode, dump_raw_to=None,
