@@ -204,8 +204,6 @@ def _load():
 _tls = threading.local()
 _alloc_epoch = [0]          # bumped whenever a cached device buffer the C calls point into is re-allocated
 
-
-
 # int-returning entry points that answer a question instead of launching: a 0 from them is "no", not "launched"
 _NOT_LAUNCHES = frozenset(('nlt_conv_c32_supported',))
 
@@ -380,7 +378,7 @@ class LightEvent:
 
     def __init__(self):
         h = ctypes.c_void_p()
-        _check(_load().nlt_event_create(1, ctypes.byref(h)), 'nlt_event_create')
+        _check(_load().nlt_event_create(1, ctypes.byref(h)), 'nlt_event_create')     # (no stream: an event belongs to the device)
         self.handle = h.value
 
     def __del__(self):
@@ -419,7 +417,7 @@ def new_event():
 
 def record_event(ev, stream):
     if isinstance(ev, LightEvent):
-        _check(lib().nlt_event_record(ev.handle, stream.cuda_stream), 'nlt_event_record')
+        _check(lib().nlt_event_record(ev.handle, stream.cuda_stream), 'nlt_event_record')     # (the caller's stream, not the current one)
         return
     ev.record(stream)
     t = getattr(_tls, 'tape', None)
@@ -429,7 +427,7 @@ def record_event(ev, stream):
 
 def wait_event(stream, ev):
     if isinstance(ev, LightEvent):
-        _check(lib().nlt_stream_wait_event(stream.cuda_stream, ev.handle), 'nlt_stream_wait_event')
+        _check(lib().nlt_stream_wait_event(stream.cuda_stream, ev.handle), 'nlt_stream_wait_event')     # (the stream comes first)
         return
     stream.wait_event(ev)
     t = getattr(_tls, 'tape', None)
@@ -449,8 +447,8 @@ def set_workspace_scope(token):
 
 def drop_workspace_scope(token):
     """Forgets the scratch cached for a plan that is gone (RenderPlan.__del__: the lanes of a closed pipeline)."""
-    for key in [k for k in _splitk_ws if len(k) > 2 and k[2] == token]:
-        del _splitk_ws[key]
+    for key in [k for k in _ws_cache if len(k) > 2 and k[2] == token]:      # (device, stream, token): the split-K keys of `_workspace`
+        del _ws_cache[key]
 
 
 def set_thread_native_replay(on):
@@ -495,50 +493,86 @@ def _dense(t, what):
     return t
 
 
+def _call(name, *args):
+    """Launches entry point `name` with `args` + the current stream; a non-zero status raises NLTError under that name.  (Looked up
+    on `lib()`, so an open tape records the call.)"""
+    _check(getattr(lib(), name)(*args, _stream()), name)
+
+
+def _size(name, *args, what=None):
+    """Answer of a `*_workspace_floats` / `*_workspace_bytes` / `*_packed_floats` / `*_packed_elems` query; <= 0 ("these shapes are
+    not implemented") raises NLTError with the query and its arguments."""
+    n = getattr(lib(), name)(*args)                     # (a query: no stream, never taped)
+    if n <= 0:
+        raise NLTError("%s%r: unsupported%s" % (name, args, ' (%s)' % what if what else ''))
+    return n
+
+
+_ws_cache = {}
+_splitk_ws = _ws_cache      # (the split-K entries are this cache's 3-tuples; the host bookkeeping test reaches them under this name)
+
+
+def _workspace(key, device, need, zero=False):
+    """Scratch floats cached under (device, *key), grown on demand; the address is stable until then (launch tapes and captured
+    graphs point at it).  A string names a family with one buffer per device ('front_bwd'; `_per_stream` adds the stream); the
+    one tuple key is split-K's (stream, plan token), which `drop_workspace_scope` recognises by its length."""
+    key = (str(device),) + key if isinstance(key, tuple) else (str(device), key)
+    ws = _ws_cache.get(key)
+    if ws is None or ws.numel() < need:
+        ws = (torch.zeros if zero else torch.empty)(need, device=device, dtype=torch.float32)
+        _ws_cache[key] = ws
+        _alloc_epoch[0] += 1                            # recorded launch tapes point into the old buffer
+    return ws
+
+
+def _per_stream(family):
+    """Key of a family whose launches may run on two streams at once (the plan deals weight gradients to two streams)."""
+    return '%s.%d' % (family, _stream())
+
+
+def _pack(size_name, size_args, pack_name, pack_args, dtype, device):
+    """Packed weights: asks `size_name` for the length, allocates it, launches `pack_name`(*pack_args, out) and returns out."""
+    out = torch.empty(_size(size_name, *size_args), device=device, dtype=dtype)
+    _call(pack_name, *pack_args, out.data_ptr())
+    return out
+
+
 def packed_weight_floats(mode, c0, c1, cout):
-    return lib().nlt_packed_weight_floats(mode, c0, c1, cout)
+    return lib().nlt_packed_weight_floats(mode, c0, c1, cout)       # (a query: no stream; -1 = unsupported, for the caller to read)
 
 
 def pack_conv_weights(mode, w_keras, c0, c1, cout):
-    n = packed_weight_floats(mode, c0, c1, cout)
-    out = torch.empty(n, device=w_keras.device, dtype=torch.float32)
-    _check(lib().nlt_pack_conv_weights(mode, _ptr(_dense(w_keras, 'w_keras')), c0, c1, cout, _ptr(out), _stream()),
-           'nlt_pack_conv_weights')
-    return out
+    return _pack('nlt_packed_weight_floats', (mode, c0, c1, cout),
+                 'nlt_pack_conv_weights', (mode, _ptr(_dense(w_keras, 'w_keras')), c0, c1, cout), torch.float32, w_keras.device)
 
 
 def conv_forward(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, w_keras, w_packed, bias, cout, out, ldo,
                  act=True, alpha=0.3, algo=ALGO_AUTO, tile_hint=0, mask_src=None, ldm=0, accumulate=False):
     """src*/out/mask_src may be views INTO wider tensors: pass the (already offset) tensor whose
     data_ptr() is the first element of the channel slice, and the per-texel stride ld*."""
-    _check(lib().nlt_conv_forward(mode, algo, tile_hint, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
-                                  _ptr(w_keras), _ptr(w_packed), _ptr(bias), cout, _ptr(out), ldo,
-                                  1 if act else 0, float(alpha), _ptr(mask_src), ldm, 1 if accumulate else 0,
-                                  _stream()), 'nlt_conv_forward')
+    _call('nlt_conv_forward', mode, algo, tile_hint, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(w_keras),
+          _ptr(w_packed), _ptr(bias), cout, _ptr(out), ldo, 1 if act else 0, float(alpha), _ptr(mask_src), ldm,
+          1 if accumulate else 0)
 
 
 def stem_forward(base, cvis, lvis, nn_rgb, nn_base, obs_weights, n, k, h, w, c, wq, bq, wo, bo, fm0, obs0):
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (nn_rgb, 'nn_rgb'), (nn_base, 'nn_base')):
         _dense(t, nm)
-    _check(lib().nlt_stem_forward(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base),
-                                  _ptr(obs_weights), n, k, h, w, c, _ptr(wq), _ptr(bq), _ptr(wo), _ptr(bo),
-                                  _ptr(fm0), _ptr(obs0), _stream()), 'nlt_stem_forward')
+    _call('nlt_stem_forward', _ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), _ptr(obs_weights), n, k, h, w, c,
+          _ptr(wq), _ptr(bq), _ptr(wo), _ptr(bo), _ptr(fm0), _ptr(obs0))
 
 
 def obs_mean_forward(obs, obs_weights, n, k, hw, c, out, ldo):
-    _check(lib().nlt_obs_mean_forward(_ptr(_dense(obs, 'obs')), _ptr(obs_weights), n, k, hw, c, _ptr(out), ldo,
-                                      _stream()), 'nlt_obs_mean_forward')
+    _call('nlt_obs_mean_forward', _ptr(_dense(obs, 'obs')), _ptr(obs_weights), n, k, hw, c, _ptr(out), ldo)
 
 
 def head_forward(dec, ldd, cd, skip, lds, cs, w_keras, bias, base, n, h, w, pred):
-    _check(lib().nlt_head_forward(_ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(bias), _ptr(base),
-                                  n, h, w, _ptr(pred), _stream()), 'nlt_head_forward')
+    _call('nlt_head_forward', _ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(bias), _ptr(base), n, h, w, _ptr(pred))
 
 
 def warp_forward(pred, base, warp, n, uvh, uvw, hc, wc, pred_cam, base_cam, fg_cam, idx_out=None):
-    _check(lib().nlt_warp_forward(_ptr(pred), _ptr(base), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc,
-                                  _ptr(pred_cam), _ptr(base_cam), _ptr(fg_cam), _ptr(idx_out), _stream()),
-           'nlt_warp_forward')
+    _call('nlt_warp_forward', _ptr(pred), _ptr(base), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc, _ptr(pred_cam),
+          _ptr(base_cam), _ptr(fg_cam), _ptr(idx_out))
 
 
 def warp_forward_store(pred, diffuse_store, uv2cam_store, ids, n, uvh, uvw, hc, wc, pred_cam, base_cam, fg_cam, idx_out=None):
@@ -546,10 +580,9 @@ def warp_forward_store(pred, diffuse_store, uv2cam_store, ids, n, uvh, uvw, hc, 
     if tuple(diffuse_store.shape[1:]) != (uvh, uvw, 3) or tuple(uv2cam_store.shape[1:]) != (hc, wc, 2):
         raise NLTError("stores %s / %s do not match uv %dx%d, camera %dx%d"
                        % (tuple(diffuse_store.shape), tuple(uv2cam_store.shape), uvh, uvw, hc, wc))
-    _check(lib().nlt_warp_forward_store(_ptr(pred), _tptr(diffuse_store, torch.uint8, 'diffuse store'),
-                                        _tptr(uv2cam_store, torch.float16, 'uv2cam store'), _tptr(ids, torch.int32, 'ids'),
-                                        n, uvh, uvw, hc, wc, _ptr(pred_cam), _ptr(base_cam), _ptr(fg_cam), _ptr(idx_out),
-                                        _stream()), 'nlt_warp_forward_store')
+    _call('nlt_warp_forward_store', _ptr(pred), _tptr(diffuse_store, torch.uint8, 'diffuse store'),
+          _tptr(uv2cam_store, torch.float16, 'uv2cam store'), _tptr(ids, torch.int32, 'ids'), n, uvh, uvw, hc, wc, _ptr(pred_cam),
+          _ptr(base_cam), _ptr(fg_cam), _ptr(idx_out))
 
 
 def resample_forward(data, warp_px):
@@ -557,16 +590,14 @@ def resample_forward(data, warp_px):
     n, h, w, c = data.shape
     hc, wc = warp_px.shape[1:3]
     out = torch.empty((n, hc, wc, c), device=data.device, dtype=torch.float32)
-    _check(lib().nlt_resample_forward(_ptr(_dense(data, 'data')), _ptr(_dense(warp_px, 'warp_px')), n, h, w, c, hc, wc, _ptr(out),
-                                      _stream()), 'nlt_resample_forward')
+    _call('nlt_resample_forward', _ptr(_dense(data, 'data')), _ptr(_dense(warp_px, 'warp_px')), n, h, w, c, hc, wc, _ptr(out))
     return out
 
 
 def resize_bilinear_forward(x, oh, ow):
     n, h, w, c = x.shape
     out = torch.empty((n, oh, ow, c), device=x.device, dtype=torch.float32)
-    _check(lib().nlt_resize_bilinear_forward(_ptr(_dense(x, 'x')), n, h, w, c, oh, ow, _ptr(out), _stream()),
-           'nlt_resize_bilinear_forward')
+    _call('nlt_resize_bilinear_forward', _ptr(_dense(x, 'x')), n, h, w, c, oh, ow, _ptr(out))
     return out
 
 
@@ -578,14 +609,13 @@ def _same_shape(a, b, what):
 def mul_forward(a, b):
     _same_shape(a, b, 'mul_forward')
     out = torch.empty_like(a)
-    _check(lib().nlt_mul_forward(_ptr(_dense(a, 'a')), _ptr(_dense(b, 'b')), a.numel(), _ptr(out), _stream()),
-           'nlt_mul_forward')
+    _call('nlt_mul_forward', _ptr(_dense(a, 'a')), _ptr(_dense(b, 'b')), a.numel(), _ptr(out))
     return out
 
 
 # ---------------------------------------------------------------- train step
 # Deterministic mode (`deterministic = true`, models/nlt.py): while it is on for this thread, the adapters below whose kernels end
-# in float atomics hand their arguments to the atomic-free `_det` / `_gather` siblings instead (+ a workspace from `_det_ws`).
+# in float atomics hand their arguments to the atomic-free `_det` / `_gather` siblings instead (`_call_det`).
 # A case with no sibling raises NotImplementedError and names the kernel: nothing falls back to atomics silently.
 class deterministic_scope:
     """`with deterministic_scope(on):` -- the mode of this thread's calls inside the block (nesting restores the outer value)."""
@@ -607,82 +637,57 @@ def deterministic():
     return getattr(_tls, 'det', False)
 
 
-def _det_ws(name, device, floats):
-    """Workspace of a deterministic entry point: cached per (kernel family, stream, device) like the other two-pass
-    reductions' scratch -- a stable address (launch tapes and captured graphs point at it), sized from shapes."""
-    return _workspace('det.%s.%d' % (name, _stream()), device, max(int(floats), 1))
+def _call_det(name, args, family, device, size, kernel=None, in_bytes=False):
+    """`name`(*args), or in deterministic mode `name`_det(*args, workspace, its size): the C ABI gives every `_det` entry its plain
+    twin's parameters + those two.  The workspace is cached per (family, stream, device) and sized by the query `size` = (entry
+    name, *arguments), in floats or (in_bytes) in bytes.  `kernel`: the float-atomic kernel to name in the NotImplementedError
+    when the query knows no atomic-free form for these shapes; without one, every shape has a form and a refusal is an NLTError."""
+    if not deterministic():
+        return _call(name, *args)
+    if kernel is None:
+        need = _size(*size)
+    else:
+        need = getattr(lib(), size[0])(*size[1:])       # (a query: no stream, never taped)
+        if need <= 0:
+            raise NotImplementedError("deterministic mode: %s (%s) has no atomic-free form: %s%r is not implemented"
+                                      % (kernel, name, size[0], tuple(size[1:])))
+    unit = 4 if in_bytes else 1
+    ws = _workspace(_per_stream('det.' + family), device, (need + unit - 1) // unit)
+    _call(name + '_det', *args, _ptr(ws), unit * ws.numel())
 
 
 def conv_backward_weights(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, dpre, ldp, cout, dw, db, algo=ALGO_AUTO):
-    if deterministic():
-        need = lib().nlt_conv_backward_weights_det_workspace_floats(mode, c0, c1, n, h, w, cout)
-        if need <= 0:
-            raise NotImplementedError("deterministic mode: wgrad_mfma_kernel / wgrad_direct_kernel (nlt_conv_backward_weights) has no "
-                                      "atomic-free form for mode %d, c0 %d, c1 %d, cout %d" % (mode, c0, c1, cout))
-        ws = _det_ws('wgrad', dpre.device, need)
-        _check(lib().nlt_conv_backward_weights_det(mode, algo, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
-                                                   _ptr(dpre), ldp, cout, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-               'nlt_conv_backward_weights_det')
-        return
-    _check(lib().nlt_conv_backward_weights(mode, algo, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
-                                           _ptr(dpre), ldp, cout, _ptr(dw), _ptr(db), _stream()),
-           'nlt_conv_backward_weights')
-
-
-_wgrad_ws = {}
-_named_ws = {}
-
-
-def _workspace(name, device, need):
-    """Scratch floats for the two-pass (deterministic) reductions, cached per (kernel family, device), grown on demand."""
-    key = (name, str(device))
-    ws = _named_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=device, dtype=torch.float32)
-        _named_ws[key] = ws
-        _alloc_epoch[0] += 1                         # recorded launch tapes point into the old buffer
-    return ws
+    _call_det('nlt_conv_backward_weights', (mode, algo, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(dpre), ldp, cout,
+                                            _ptr(dw), _ptr(db)),
+              'wgrad', dpre.device, ('nlt_conv_backward_weights_det_workspace_floats', mode, c0, c1, n, h, w, cout),
+              kernel='wgrad_mfma_kernel / wgrad_direct_kernel')
 
 
 def conv_backward_weights_tiled(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, dpre, ldp, cout, dw, db):
-    """Second-generation weight gradient (deterministic two-pass); the slice workspace is cached per device."""
-    need = lib().nlt_wgrad_workspace_floats(mode, c0, c1, n, h, w, cout)
-    if need <= 0:
-        raise NLTError("nlt_wgrad_workspace_floats: unsupported (mode %d, c0 %d, c1 %d, cout %d)" % (mode, c0, c1, cout))
-    key = (str(src0.device), _stream())                 # per stream: the plan may deal weight gradients to two streams
-    ws = _wgrad_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, device=src0.device, dtype=torch.float32)
-        _wgrad_ws[key] = ws
-        _alloc_epoch[0] += 1
-    _check(lib().nlt_conv_backward_weights_tiled(mode, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(dpre), ldp,
-                                                 cout, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-           'nlt_conv_backward_weights_tiled')
+    """Second-generation weight gradient (deterministic two-pass); the slice workspace is cached per device and stream."""
+    ws = _workspace(_per_stream('wgrad_tiled'), src0.device, _size('nlt_wgrad_workspace_floats', mode, c0, c1, n, h, w, cout))
+    _call('nlt_conv_backward_weights_tiled', mode, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(dpre), ldp, cout,
+          _ptr(dw), _ptr(db), _ptr(ws), ws.numel())
 
 
 def wgrad_narrow_supported(mode, c0, c1, n, h, w, cout):
-    return lib().nlt_wgrad_narrow_workspace_floats(mode, c0, c1, n, h, w, cout) > 0
+    return lib().nlt_wgrad_narrow_workspace_floats(mode, c0, c1, n, h, w, cout) > 0      # (a query: no stream)
 
 
 def conv_backward_weights_narrow(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, dpre, ldp, cout, dw, db):
     """Weight gradient of a narrow layer (<= 32 output columns, K <= 128): MFMA tile matched to the layer."""
-    need = lib().nlt_wgrad_narrow_workspace_floats(mode, c0, c1, n, h, w, cout)
-    if need <= 0:
-        raise NLTError("nlt_wgrad_narrow_workspace_floats: unsupported (mode %d, c0 %d, c1 %d, cout %d)" % (mode, c0, c1, cout))
-    ws = _workspace('wgrad_narrow.%d' % _stream(), src0.device, need)
-    _check(lib().nlt_conv_backward_weights_narrow(mode, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(dpre), ldp,
-                                                  cout, _ptr(dw), _ptr(db), _ptr(ws), ws.numel(), _stream()),
-           'nlt_conv_backward_weights_narrow')
+    ws = _workspace(_per_stream('wgrad_narrow'), src0.device, _size('nlt_wgrad_narrow_workspace_floats', mode, c0, c1, n, h, w, cout))
+    _call('nlt_conv_backward_weights_narrow', mode, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(dpre), ldp, cout,
+          _ptr(dw), _ptr(db), _ptr(ws), ws.numel())
 
 
 def lrelu_backward(g, ldg, y, ldy, c, texels, alpha, out, ldo):
-    _check(lib().nlt_lrelu_backward(_ptr(g), ldg, _ptr(y), ldy, c, texels, float(alpha), _ptr(out), ldo, _stream()),
-           'nlt_lrelu_backward')
+    _call('nlt_lrelu_backward', _ptr(g), ldg, _ptr(y), ldy, c, texels, float(alpha), _ptr(out), ldo)
 
 
 def obs_mean_backward(dmean, ldm, obs_y, obs_weights, dobs_partial, n, k, hw, c, alpha, dpre_obs):
-    _check(lib().nlt_obs_mean_backward(_ptr(dmean), ldm, _ptr(obs_y), _ptr(obs_weights), _ptr(dobs_partial),
-                                       n, k, hw, c, float(alpha), _ptr(dpre_obs), _stream()), 'nlt_obs_mean_backward')
+    _call('nlt_obs_mean_backward', _ptr(dmean), ldm, _ptr(obs_y), _ptr(obs_weights), _ptr(dobs_partial), n, k, hw, c, float(alpha),
+          _ptr(dpre_obs))
 
 
 def resize_cv_linear(src, oh, ow, out=None):
@@ -695,89 +700,60 @@ def resize_cv_linear(src, oh, ow, out=None):
     n, h, w, c = src.shape
     if out is None:
         out = torch.empty((n, oh, ow, c), device=src.device, dtype=torch.float32)
-    _check(lib().nlt_resize_cv_linear(_tptr(src, src.dtype, 'src'), kind, n, h, w, c, oh, ow, _ptr(out), _stream()), 'nlt_resize_cv_linear')
+    _call('nlt_resize_cv_linear', _tptr(src, src.dtype, 'src'), kind, n, h, w, c, oh, ow, _ptr(out))
     return out
 
 
 def level_split_backward(dfm, fm_y, ld, obs_y, obs_weights, dobs_partial, n, k, hw, c, alpha_q, alpha_o, dpre_obs):
     """lrelu_backward on the query half (in place) + obs_mean_backward on the observation half of dfm [n,hw,ld], one launch."""
-    _check(lib().nlt_level_split_backward(_ptr(dfm), _ptr(fm_y), ld, _ptr(obs_y), _ptr(obs_weights), _ptr(dobs_partial),
-                                          n, k, hw, c, float(alpha_q), float(alpha_o), _ptr(dpre_obs), _stream()),
-           'nlt_level_split_backward')
+    _call('nlt_level_split_backward', _ptr(dfm), _ptr(fm_y), ld, _ptr(obs_y), _ptr(obs_weights), _ptr(dobs_partial), n, k, hw, c,
+          float(alpha_q), float(alpha_o), _ptr(dpre_obs))
 
 
 def stem_backward(base, cvis, lvis, nn_rgb, nn_base, obs_weights, n, k, h, w, c, dfm0, dobs0, dwq, dbq, dwo, dbo):
-    if deterministic():
-        need = lib().nlt_stem_backward_det_workspace_floats(n, h, w, c)
-        if need <= 0:
-            raise NotImplementedError("deterministic mode: stem_bwd_kernel (nlt_stem_backward) has no atomic-free form for c = %d" % c)
-        ws = _det_ws('stem', dfm0.device, need)
-        _check(lib().nlt_stem_backward_det(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), _ptr(obs_weights),
-                                           n, k, h, w, c, _ptr(dfm0), _ptr(dobs0), _ptr(dwq), _ptr(dbq), _ptr(dwo), _ptr(dbo),
-                                           _ptr(ws), ws.numel(), _stream()), 'nlt_stem_backward_det')
-        return
-    _check(lib().nlt_stem_backward(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), _ptr(obs_weights),
-                                   n, k, h, w, c, _ptr(dfm0), _ptr(dobs0), _ptr(dwq), _ptr(dbq), _ptr(dwo), _ptr(dbo),
-                                   _stream()), 'nlt_stem_backward')
+    _call_det('nlt_stem_backward', (_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), _ptr(obs_weights), n, k, h, w, c,
+                                    _ptr(dfm0), _ptr(dobs0), _ptr(dwq), _ptr(dbq), _ptr(dwo), _ptr(dbo)),
+              'stem', dfm0.device, ('nlt_stem_backward_det_workspace_floats', n, h, w, c), kernel='stem_bwd_kernel')
 
 
 def head_backward(dec, ldd, cd, skip, lds, cs, w_keras, dpred, n, h, w, d_dec, ldgd, d_skip, ldgs, dw, db):
-    if deterministic():
-        need = lib().nlt_head_backward_det_workspace_floats(n, h, w, cd, cs)
-        if need <= 0:
-            raise NotImplementedError("deterministic mode: head_bwd_kernel (nlt_head_backward) has no atomic-free form for "
-                                      "cd = %d, cs = %d" % (cd, cs))
-        ws = _det_ws('head', dpred.device, need)
-        _check(lib().nlt_head_backward_det(_ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(_dense(dpred, 'dpred')),
-                                           n, h, w, _ptr(d_dec), ldgd, _ptr(d_skip), ldgs, _ptr(dw), _ptr(db),
-                                           _ptr(ws), ws.numel(), _stream()), 'nlt_head_backward_det')
-        return
-    _check(lib().nlt_head_backward(_ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(_dense(dpred, 'dpred')),
-                                   n, h, w, _ptr(d_dec), ldgd, _ptr(d_skip), ldgs, _ptr(dw), _ptr(db), _stream()),
-           'nlt_head_backward')
+    _call_det('nlt_head_backward', (_ptr(dec), ldd, cd, _ptr(skip), lds, cs, _ptr(w_keras), _ptr(_dense(dpred, 'dpred')), n, h, w,
+                                    _ptr(d_dec), ldgd, _ptr(d_skip), ldgs, _ptr(dw), _ptr(db)),
+              'head', dpred.device, ('nlt_head_backward_det_workspace_floats', n, h, w, cd, cs), kernel='head_bwd_kernel')
+
+
+def warp_backward(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred):
+    # (irregular: the `_det` form sizes its workspace in BYTES, and refuses >= 2^29 camera pixels)
+    _call_det('nlt_warp_backward', (_ptr(_dense(dpred_cam, 'dpred_cam')), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc, _ptr(dpred)),
+              'warp', dpred.device, ('nlt_warp_backward_det_workspace_bytes', n, uvh, uvw, hc, wc), kernel='warp_bwd_kernel',
+              in_bytes=True)
 
 
 def warp_backward_det(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred):
     """nlt_warp_backward with each texel's contributions added in ascending (camera pixel, corner) order: bit-repeatable."""
-    need = lib().nlt_warp_backward_det_workspace_bytes(n, uvh, uvw, hc, wc)
-    if need <= 0:
-        raise NotImplementedError("deterministic mode: warp_bwd_kernel (nlt_warp_backward) has no atomic-free form for %d x %d x %d "
-                                  "camera pixels (>= 2^29)" % (n, hc, wc))
-    ws = _det_ws('warp', dpred.device, (need + 3) // 4)
-    _check(lib().nlt_warp_backward_det(_ptr(_dense(dpred_cam, 'dpred_cam')), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc,
-                                       _ptr(dpred), _ptr(ws), 4 * ws.numel(), _stream()), 'nlt_warp_backward_det')
-
-
-def warp_backward(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred):
-    if deterministic():
-        return warp_backward_det(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred)
-    _check(lib().nlt_warp_backward(_ptr(_dense(dpred_cam, 'dpred_cam')), _ptr(_dense(warp, 'warp')), n, uvh, uvw, hc, wc,
-                                   _ptr(dpred), _stream()), 'nlt_warp_backward')
+    with deterministic_scope(True):
+        warp_backward(dpred_cam, warp, n, uvh, uvw, hc, wc, dpred)
 
 
 def resize_bilinear_backward(dout, h, w):
     n, oh, ow, c = dout.shape
     dx = torch.empty((n, h, w, c), device=dout.device, dtype=torch.float32)
-    if deterministic():
-        _check(lib().nlt_resize_bilinear_backward_gather(_ptr(_dense(dout, 'dout')), n, h, w, c, oh, ow, _ptr(dx), _stream()),
-               'nlt_resize_bilinear_backward_gather')
-        return dx
-    _check(lib().nlt_resize_bilinear_backward(_ptr(_dense(dout, 'dout')), n, h, w, c, oh, ow, _ptr(dx), _stream()),
-           'nlt_resize_bilinear_backward')
+    # (irregular: the atomic-free sibling is a gather -- its own suffix, no workspace)
+    _call('nlt_resize_bilinear_backward' + ('_gather' if deterministic() else ''), _ptr(_dense(dout, 'dout')), n, h, w, c, oh, ow,
+          _ptr(dx))
     return dx
+
+
+def _loss_det_size(n):
+    return ('nlt_loss_det_workspace_floats', n)         # the three L2 losses share the family 'loss' and this query
 
 
 def l2_loss_forward(pred, gt):
     _same_shape(pred, gt, 'l2_loss_forward')
     n = pred.shape[0]
     loss = torch.empty(n, device=pred.device, dtype=torch.float32)
-    if deterministic():
-        ws = _det_ws('loss', pred.device, lib().nlt_loss_det_workspace_floats(n))
-        _check(lib().nlt_l2_loss_forward_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, pred[0].numel(),
-                                             _ptr(loss), _ptr(ws), ws.numel(), _stream()), 'nlt_l2_loss_forward_det')
-        return loss
-    _check(lib().nlt_l2_loss_forward(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, pred[0].numel(),
-                                     _ptr(loss), _stream()), 'nlt_l2_loss_forward')
+    _call_det('nlt_l2_loss_forward', (_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, pred[0].numel(), _ptr(loss)),
+              'loss', pred.device, _loss_det_size(n))
     return loss
 
 
@@ -786,15 +762,9 @@ def l2_train_loss(pred, rgb, fg, global_bs):
     _same_shape(pred, rgb, 'l2_train_loss'); _same_shape(pred, fg, 'l2_train_loss')
     gt, dpred = torch.empty_like(pred), torch.empty_like(pred)
     loss = torch.empty((), device=pred.device, dtype=torch.float32)
-    if deterministic():
-        ws = _det_ws('loss', pred.device, lib().nlt_loss_det_workspace_floats(pred.shape[0]))
-        _check(lib().nlt_l2_train_loss_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(rgb, 'rgb')), _ptr(_dense(fg, 'fg')), pred.shape[0],
-                                           pred[0].numel(), 1.0 / float(global_bs), _ptr(gt), _ptr(dpred), _ptr(loss),
-                                           _ptr(ws), ws.numel(), _stream()), 'nlt_l2_train_loss_det')
-        return loss, gt, dpred
-    _check(lib().nlt_l2_train_loss(_ptr(_dense(pred, 'pred')), _ptr(_dense(rgb, 'rgb')), _ptr(_dense(fg, 'fg')), pred.shape[0],
-                                   pred[0].numel(), 1.0 / float(global_bs), _ptr(gt), _ptr(dpred), _ptr(loss), _stream()),
-           'nlt_l2_train_loss')
+    _call_det('nlt_l2_train_loss', (_ptr(_dense(pred, 'pred')), _ptr(_dense(rgb, 'rgb')), _ptr(_dense(fg, 'fg')), pred.shape[0],
+                                    pred[0].numel(), 1.0 / float(global_bs), _ptr(gt), _ptr(dpred), _ptr(loss)),
+              'loss', pred.device, _loss_det_size(pred.shape[0]))
     return loss, gt, dpred
 
 
@@ -803,8 +773,7 @@ def l2_loss_backward(pred, gt, gloss):
     if gloss.numel() != pred.shape[0]:
         raise NLTError("l2_loss_backward: %d loss gradients for %d examples" % (gloss.numel(), pred.shape[0]))
     dpred = torch.empty_like(pred)
-    _check(lib().nlt_l2_loss_backward(_ptr(pred), _ptr(gt), _ptr(_dense(gloss, 'gloss')), pred.shape[0],
-                                      pred[0].numel(), _ptr(dpred), _stream()), 'nlt_l2_loss_backward')
+    _call('nlt_l2_loss_backward', _ptr(pred), _ptr(gt), _ptr(_dense(gloss, 'gloss')), pred.shape[0], pred[0].numel(), _ptr(dpred))
     return dpred
 
 
@@ -816,14 +785,9 @@ def l2_loss_weighted_forward(pred, gt, weights):
     if weights.numel() != n * hw:
         raise NLTError("l2_loss_weighted_forward: %d weights for %d texels" % (weights.numel(), n * hw))
     loss = torch.empty(n, device=pred.device, dtype=torch.float32)
-    if deterministic():
-        ws = _det_ws('loss', pred.device, lib().nlt_loss_det_workspace_floats(n))
-        _check(lib().nlt_l2_loss_weighted_forward_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')),
-                                                      _ptr(_dense(weights, 'weights')), n, hw, c, _ptr(loss), _ptr(ws), ws.numel(),
-                                                      _stream()), 'nlt_l2_loss_weighted_forward_det')
-        return loss
-    _check(lib().nlt_l2_loss_weighted_forward(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), _ptr(_dense(weights, 'weights')),
-                                              n, hw, c, _ptr(loss), _stream()), 'nlt_l2_loss_weighted_forward')
+    _call_det('nlt_l2_loss_weighted_forward', (_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), _ptr(_dense(weights, 'weights')),
+                                               n, hw, c, _ptr(loss)),
+              'loss', pred.device, _loss_det_size(n))
     return loss
 
 
@@ -835,9 +799,8 @@ def l2_loss_weighted_backward(pred, gt, weights, gloss):
         raise NLTError("l2_loss_weighted_backward: %d loss gradients, %d weights for %d examples of %d texels"
                        % (gloss.numel(), weights.numel(), n, hw))
     dpred = torch.empty_like(pred)
-    _check(lib().nlt_l2_loss_weighted_backward(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), _ptr(_dense(weights, 'weights')),
-                                               _ptr(_dense(gloss, 'gloss')), n, hw, c, _ptr(dpred), _stream()),
-           'nlt_l2_loss_weighted_backward')
+    _call('nlt_l2_loss_weighted_backward', _ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), _ptr(_dense(weights, 'weights')),
+          _ptr(_dense(gloss, 'gloss')), n, hw, c, _ptr(dpred))
     return dpred
 
 
@@ -845,19 +808,13 @@ def barron_loss(pred, gt, want_grad):
     _same_shape(pred, gt, 'barron_loss')
     n, h, w, c = pred.shape
     assert c == 3
-    nws = lib().nlt_barron_workspace_floats(n, h, w)
-    if nws <= 0:
-        raise NLTError("nlt_barron_workspace_floats(%d,%d,%d) failed" % (n, h, w))
-    ws = torch.empty(nws, device=pred.device, dtype=torch.float32)
+    ws = torch.empty(_size('nlt_barron_workspace_floats', n, h, w), device=pred.device, dtype=torch.float32)
     loss = torch.empty(n, device=pred.device, dtype=torch.float32)
     dunit = torch.empty_like(pred) if want_grad else None
-    if deterministic():
-        slots = _det_ws('barron', pred.device, lib().nlt_barron_det_slots_floats(n, h, w))
-        _check(lib().nlt_barron_loss_det(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(ws), _ptr(loss),
-                                         _ptr(dunit), _ptr(slots), slots.numel(), _stream()), 'nlt_barron_loss_det')
-        return loss, dunit
-    _check(lib().nlt_barron_loss(_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(ws), _ptr(loss),
-                                 _ptr(dunit), _stream()), 'nlt_barron_loss')
+    # (irregular: `ws` is the ordinary per-call scratch of both forms; what the `_det` form appends is its `slots`, sized by a query
+    # named after them)
+    _call_det('nlt_barron_loss', (_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(ws), _ptr(loss), _ptr(dunit)),
+              'barron', pred.device, ('nlt_barron_det_slots_floats', n, h, w))
     return loss, dunit
 
 
@@ -865,8 +822,7 @@ def scale_rows(x, scale):
     if scale.numel() != x.shape[0]:
         raise NLTError("scale_rows: %d scales for %d rows" % (scale.numel(), x.shape[0]))
     out = torch.empty_like(x)
-    _check(lib().nlt_scale_rows(_ptr(_dense(x, 'x')), _ptr(_dense(scale, 'scale')), x.shape[0], x[0].numel(),
-                                _ptr(out), _stream()), 'nlt_scale_rows')
+    _call('nlt_scale_rows', _ptr(_dense(x, 'x')), _ptr(_dense(scale, 'scale')), x.shape[0], x[0].numel(), _ptr(out))
     return out
 
 
@@ -878,7 +834,7 @@ POOL_MAX, POOL_AVG = 0, 1
 def sub_forward(a, b):
     _same_shape(a, b, 'sub_forward')
     out = torch.empty_like(a)
-    _check(lib().nlt_sub_forward(_ptr(_dense(a, 'a')), _ptr(_dense(b, 'b')), a.numel(), _ptr(out), _stream()), 'nlt_sub_forward')
+    _call('nlt_sub_forward', _ptr(_dense(a, 'a')), _ptr(_dense(b, 'b')), a.numel(), _ptr(out))
     return out
 
 
@@ -886,27 +842,26 @@ def finish_pred(y, base, pred):
     n, h, w, c = y.shape
     if c != 3 or (base is not None and tuple(base.shape) != tuple(y.shape)) or tuple(pred.shape) != tuple(y.shape):
         raise NLTError("finish_pred: y / base / pred must be [n,h,w,3] of one shape")
-    _check(lib().nlt_finish_pred(_ptr(_dense(y, 'y')), _ptr(base), n, h, w, _ptr(pred), _stream()), 'nlt_finish_pred')
+    _call('nlt_finish_pred', _ptr(_dense(y, 'y')), _ptr(base), n, h, w, _ptr(pred))
 
 
 def act_forward(x, kind, alpha):
     y = torch.empty_like(x)
-    _check(lib().nlt_act_forward(_ptr(_dense(x, 'x')), x.numel(), kind, float(alpha), _ptr(y), _stream()), 'nlt_act_forward')
+    _call('nlt_act_forward', _ptr(_dense(x, 'x')), x.numel(), kind, float(alpha), _ptr(y))
     return y
 
 
 def act_backward(g, y, kind, alpha):
     _same_shape(g, y, 'act_backward')
     dx = torch.empty_like(y)
-    _check(lib().nlt_act_backward(_ptr(_dense(g, 'g')), _ptr(_dense(y, 'y')), y.numel(), kind, float(alpha), _ptr(dx), _stream()),
-           'nlt_act_backward')
+    _call('nlt_act_backward', _ptr(_dense(g, 'g')), _ptr(_dense(y, 'y')), y.numel(), kind, float(alpha), _ptr(dx))
     return dx
 
 
 def pixelnorm_forward(x, eps=1e-8):
     y = torch.empty_like(x)
     c = x.shape[-1]
-    _check(lib().nlt_pixelnorm_forward(_ptr(_dense(x, 'x')), x.numel() // c, c, float(eps), _ptr(y), _stream()), 'nlt_pixelnorm_forward')
+    _call('nlt_pixelnorm_forward', _ptr(_dense(x, 'x')), x.numel() // c, c, float(eps), _ptr(y))
     return y
 
 
@@ -914,8 +869,7 @@ def pixelnorm_backward(g, x, eps=1e-8):
     _same_shape(g, x, 'pixelnorm_backward')
     dx = torch.empty_like(x)
     c = x.shape[-1]
-    _check(lib().nlt_pixelnorm_backward(_ptr(_dense(g, 'g')), _ptr(_dense(x, 'x')), x.numel() // c, c, float(eps), _ptr(dx), _stream()),
-           'nlt_pixelnorm_backward')
+    _call('nlt_pixelnorm_backward', _ptr(_dense(g, 'g')), _ptr(_dense(x, 'x')), x.numel() // c, c, float(eps), _ptr(dx))
     return dx
 
 
@@ -926,8 +880,8 @@ def norm_forward(kind, x, gamma, beta, mean, var, eps):
     """LayerNormalization (kind 0) / inference-mode BatchNormalization (kind 1) over the channel axis of x [..., c]."""
     c = x.shape[-1]
     y = torch.empty_like(x)
-    _check(lib().nlt_norm_forward(kind, _ptr(_dense(x, 'x')), x.numel() // c, c, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var),
-                                  float(eps), _ptr(y), _stream()), 'nlt_norm_forward')
+    _call('nlt_norm_forward', kind, _ptr(_dense(x, 'x')), x.numel() // c, c, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var),
+          float(eps), _ptr(y))
     return y
 
 
@@ -936,20 +890,17 @@ def norm_backward(kind, g, x, gamma, mean, var, eps, dgamma, dbeta):
     _same_shape(g, x, 'norm_backward')
     c = x.shape[-1]
     texels = x.numel() // c
-    need = lib().nlt_norm_workspace_floats(texels, c)
-    if need < 0:
-        raise NLTError("norm over %d channels (the kernel takes c <= 1024)" % c)
-    ws = _workspace('norm', x.device, need)
+    ws = _workspace('norm', x.device, _size('nlt_norm_workspace_floats', texels, c, what='the kernel takes c <= 1024'))
     dx = torch.empty_like(x)
-    _check(lib().nlt_norm_backward(kind, _ptr(_dense(g, 'g')), _ptr(_dense(x, 'x')), texels, c, _ptr(gamma), _ptr(mean), _ptr(var),
-                                   float(eps), _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(ws), _stream()), 'nlt_norm_backward')
+    _call('nlt_norm_backward', kind, _ptr(_dense(g, 'g')), _ptr(_dense(x, 'x')), texels, c, _ptr(gamma), _ptr(mean), _ptr(var),
+          float(eps), _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(ws))
     return dx
 
 
 def pool2x2_forward(x, kind):
     n, h, w, c = x.shape
     y = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.float32)
-    _check(lib().nlt_pool2x2_forward(_ptr(_dense(x, 'x')), n, h, w, c, kind, _ptr(y), _stream()), 'nlt_pool2x2_forward')
+    _call('nlt_pool2x2_forward', _ptr(_dense(x, 'x')), n, h, w, c, kind, _ptr(y))
     return y
 
 
@@ -958,36 +909,29 @@ def pool2x2_backward(g, x, kind):
     if tuple(g.shape) != (n, h // 2, w // 2, c):
         raise NLTError("pool2x2_backward: gradient %s for input %s" % (tuple(g.shape), tuple(x.shape)))
     dx = torch.empty_like(x)
-    _check(lib().nlt_pool2x2_backward(_ptr(_dense(g, 'g')), _ptr(_dense(x, 'x')), n, h, w, c, kind, _ptr(dx), _stream()),
-           'nlt_pool2x2_backward')
+    _call('nlt_pool2x2_backward', _ptr(_dense(g, 'g')), _ptr(_dense(x, 'x')), n, h, w, c, kind, _ptr(dx))
     return dx
 
 
 def clip_by_norm_slots(grad, slots, clipnorm):
     """grad: flat fp32 bucket; slots: int64 [n,2] (offset, count) on the same device; in place."""
-    _check(lib().nlt_clip_by_norm_slots(_ptr(grad), _tptr(slots, torch.int64, 'slots'), slots.shape[0], float(clipnorm),
-                                        _stream()), 'nlt_clip_by_norm_slots')
+    _call('nlt_clip_by_norm_slots', _ptr(grad), _tptr(slots, torch.int64, 'slots'), slots.shape[0], float(clipnorm))
 
 
 def adam_amsgrad_step(param, grad, m, v, vhat, lr_t, beta1, beta2, eps):
-    _check(lib().nlt_adam_amsgrad_step(_ptr(param), _ptr(grad), _ptr(m), _ptr(v), _ptr(vhat), param.numel(),
-                                       float(lr_t), float(beta1), float(beta2), float(eps), _stream()),
-           'nlt_adam_amsgrad_step')
+    _call('nlt_adam_amsgrad_step', _ptr(param), _ptr(grad), _ptr(m), _ptr(v), _ptr(vhat), param.numel(), float(lr_t), float(beta1),
+          float(beta2), float(eps))
 
 
-_splitk_ws = {}
-
-
-def _splitk_workspace(need, device):
-    """The split-K scratch of the current (device, stream, plan): cached, grown on demand, ZEROED when allocated -- its first words are
-    the tiles' ticket counters, which every launch leaves at zero (include/nlt_hip.h: nlt_conv_splitk_workspace_floats)."""
-    key = (str(device), _stream(), getattr(_tls, 'scope', 0))   # per stream (the query and observation paths run concurrently) and per plan (see set_workspace_scope)
-    ws = _splitk_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.zeros(need, device=device, dtype=torch.float32)
-        _splitk_ws[key] = ws
-        _alloc_epoch[0] += 1
-    return ws
+def _splitk_workspace(mode, n, h, w, cout, ksplit, device, always=False):
+    """The split-K scratch of the current (device, stream, plan) for |ksplit| > 1 (`always`: for any ksplit), else None: cached,
+    grown on demand, ZEROED when allocated -- its first words are the tiles' ticket counters, which every launch leaves at zero
+    (include/nlt_hip.h: nlt_conv_splitk_workspace_floats).  Per stream: the query and observation paths run concurrently; per
+    plan: see set_workspace_scope."""
+    if abs(ksplit) <= 1 and not always:
+        return None
+    need = _size('nlt_conv_splitk_workspace_floats', mode, n, h, w, cout, ksplit)
+    return _workspace((_stream(), getattr(_tls, 'scope', 0)), device, need, zero=True)
 
 
 def conv_forward_splitk(mode, ksplit, src0, c0, ld0, src1, c1, ld1, n, h, w, w_packed, bias, cout, out, ldo,
@@ -995,13 +939,10 @@ def conv_forward_splitk(mode, ksplit, src0, c0, ld0, src1, c1, ld1, n, h, w, w_p
     """nlt_conv_forward (MFMA path) with the K loop split over |ksplit| wave slices (ksplit > 0: one launch, the last workgroup
     to arrive at a tile adds the groups' partial tiles; ksplit < 0: the two-launch form of rounds 2-5); the partial-sum
     workspace is cached per device and grown on demand."""
-    need = lib().nlt_conv_splitk_workspace_floats(mode, n, h, w, cout, ksplit)
-    if need <= 0:
-        raise NLTError("nlt_conv_splitk_workspace_floats failed")
-    ws = _splitk_workspace(need, src0.device)
-    _check(lib().nlt_conv_forward_splitk(mode, tile_hint, ksplit, _ptr(ws), _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
-                                         _ptr(w_packed), _ptr(bias), cout, _ptr(out), ldo, 1 if act else 0, float(alpha),
-                                         _ptr(mask_src), ldm, 1 if accumulate else 0, _stream()), 'nlt_conv_forward_splitk')
+    ws = _splitk_workspace(mode, n, h, w, cout, ksplit, src0.device, always=True)
+    _call('nlt_conv_forward_splitk', mode, tile_hint, ksplit, _ptr(ws), _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
+          _ptr(w_packed), _ptr(bias), cout, _ptr(out), ldo, 1 if act else 0, float(alpha), _ptr(mask_src), ldm,
+          1 if accumulate else 0)
 
 
 def conv_forward_map(mode, ksplit, src0, c0, ld0, src1, c1, ld1, n, h, w, w_packed, bias, cout, out, ldo, bias_map,
@@ -1009,15 +950,10 @@ def conv_forward_map(mode, ksplit, src0, c0, ld0, src1, c1, ld1, n, h, w, w_pack
     """out = act(conv(src0 | src1) + bias + bias_map): the per-frame half of a conv over concat(q, given observation map)
     (include/nlt_hip.h: nlt_conv_forward_map).  bias_map [1 or n, oh, ow, cout] dense.  (w_keras is not read here; the host
     tests' CPU emulation of this adapter computes from it.)"""
-    ws = None
-    if abs(ksplit) > 1:
-        need = lib().nlt_conv_splitk_workspace_floats(mode, n, h, w, cout, ksplit)
-        if need <= 0:
-            raise NLTError("nlt_conv_splitk_workspace_floats failed")
-        ws = _splitk_workspace(need, src0.device)
-    _check(lib().nlt_conv_forward_map(mode, tile_hint, ksplit, _ptr(ws), _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
-                                      _ptr(w_packed), _ptr(bias), cout, _ptr(out), ldo, 1 if act else 0, float(alpha),
-                                      _ptr(_dense(bias_map, 'bias_map')), bias_map.shape[0], _stream()), 'nlt_conv_forward_map')
+    ws = _splitk_workspace(mode, n, h, w, cout, ksplit, src0.device)
+    _call('nlt_conv_forward_map', mode, tile_hint, ksplit, _ptr(ws), _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w,
+          _ptr(w_packed), _ptr(bias), cout, _ptr(out), ldo, 1 if act else 0, float(alpha), _ptr(_dense(bias_map, 'bias_map')),
+          bias_map.shape[0])
 
 
 def conv_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, w_packed, zero_bias, cout, out, ldo, mask_src=None, ldm=0,
@@ -1026,17 +962,11 @@ def conv_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, w_packed, zero_bias, 
     alpha_o, has_partial): the target is dfm[l] with one observation per frame; its observation half goes, finished, to dobs.
     (w_keras -- the Keras-layout slice the fragments were packed from -- is not read here; the host tests' CPU emulation of
     this adapter computes from it.)"""
-    ws = None
-    if abs(ksplit) > 1:
-        need = lib().nlt_conv_splitk_workspace_floats(adj_mode, n, h, w, cout, ksplit)
-        if need <= 0:
-            raise NLTError("nlt_conv_splitk_workspace_floats failed")
-        ws = _splitk_workspace(need, dpre.device)
+    ws = _splitk_workspace(adj_mode, n, h, w, cout, ksplit, dpre.device)
     sc, sy, sd, sa, sp = split if split is not None else (0, None, None, 0.0, False)
-    _check(lib().nlt_conv_backward_data(adj_mode, tile_hint, ksplit, _ptr(ws), _ptr(dpre), ldp, cpre, n, h, w, _ptr(w_packed),
-                                        _ptr(zero_bias), cout, _ptr(out), ldo, _ptr(mask_src), ldm, float(mask_alpha),
-                                        1 if accumulate else 0, sc, _ptr(sy), _ptr(sd), float(sa), 1 if sp else 0, _stream()),
-           'nlt_conv_backward_data')
+    _call('nlt_conv_backward_data', adj_mode, tile_hint, ksplit, _ptr(ws), _ptr(dpre), ldp, cpre, n, h, w, _ptr(w_packed),
+          _ptr(zero_bias), cout, _ptr(out), ldo, _ptr(mask_src), ldm, float(mask_alpha), 1 if accumulate else 0, sc, _ptr(sy),
+          _ptr(sd), float(sa), 1 if sp else 0)
 
 
 # ---------------------------------------------------------------- one-launch refresh of all packed weights
@@ -1061,88 +991,30 @@ def repack_table(entries, device):
 
 
 def repack_weights(table, n_desc, total_blocks):
-    _check(lib().nlt_repack_weights(_tptr(table, torch.uint8, 'repack table'), n_desc, total_blocks, _stream()),
-           'nlt_repack_weights')
+    _call('nlt_repack_weights', _tptr(table, torch.uint8, 'repack table'), n_desc, total_blocks)
 
 
 # ---------------------------------------------------------------- LDS-tiled encoder convs
 def conv_tile_supported(mode, cin, cout, tn):
-    return lib().nlt_conv_tile_packed_floats(mode, cin, cout, tn) > 0
+    return lib().nlt_conv_tile_packed_floats(mode, cin, cout, tn) > 0       # (a query: no stream)
 
 
 def pack_conv_tile_weights(mode, w_keras, cin, cout, tn):
-    n = lib().nlt_conv_tile_packed_floats(mode, cin, cout, tn)
-    if n <= 0:
-        raise NLTError("conv_tile: unsupported (mode %d, cin %d, cout %d, tn %d)" % (mode, cin, cout, tn))
-    out = torch.empty(n, device=w_keras.device, dtype=torch.float32)
-    _check(lib().nlt_pack_conv_tile_weights(mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn, _ptr(out), _stream()),
-           'nlt_pack_conv_tile_weights')
-    return out
+    return _pack('nlt_conv_tile_packed_floats', (mode, cin, cout, tn),
+                 'nlt_pack_conv_tile_weights', (mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn), torch.float32, w_keras.device)
 
 
 def conv_tile_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm,
                       act=True, alpha=0.3):
-    _check(lib().nlt_conv_tile_forward(mode, _ptr(src), ld, cin, frames, kobs, h, w, _ptr(packed), _ptr(bias), cout, tn,
-                                       _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), _stream()),
-           'nlt_conv_tile_forward')
+    _call('nlt_conv_tile_forward', mode, _ptr(src), ld, cin, frames, kobs, h, w, _ptr(packed), _ptr(bias), cout, tn, _ptr(out), ldo,
+          _ptr(mean_out), ldm, 1 if act else 0, float(alpha))
 
 
-def conv_c32_supported(mode, cin, cout):
-    return lib().nlt_conv_c32_supported(mode, cin, cout) > 0
-
-
-def conv_c32_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, out, ldo, mean_out, ldm, act=True, alpha=0.3):
-    """Narrow stride-1 conv (cin 16 | 32 -> 32) with LDS-resident weights; packed = pack_conv_tile_weights(mode, w, cin, 32, 32)."""
-    _check(lib().nlt_conv_c32_forward(mode, _ptr(src), ld, cin, frames, kobs, h, w, _ptr(packed), _ptr(bias), cout,
-                                      _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), _stream()),
-           'nlt_conv_c32_forward')
-
-
-# ---------------------------------------------------------------- Winograd stride-1 k2 convs (csrc/conv_wino.hip)
-def conv_wino_supported(mode, cin, cout, tn):
-    return lib().nlt_conv_wino_packed_floats(mode, cin, cout, tn) > 0
-
-
-def pack_conv_wino_weights(mode, w_keras, cin, cout, tn, full=None, lo=0):
-    """G g G^T fragments of a stride-1 k2 kernel; full / lo: the ADJOINT family read from a layer's own array (columns = that
-    layer's input channels [lo, lo + cout) of `full`)."""
-    n = lib().nlt_conv_wino_packed_floats(mode, cin, cout, tn)
-    if n <= 0:
-        raise NLTError("conv_wino: unsupported (mode %d, cin %d, cout %d, tn %d)" % (mode, cin, cout, tn))
-    out = torch.empty(n, device=w_keras.device, dtype=torch.float32)
-    if full is None:
-        _check(lib().nlt_pack_conv_wino_weights(mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn, _ptr(out), _stream()),
-               'nlt_pack_conv_wino_weights')
-    else:
-        _check(lib().nlt_pack_conv_wino_weights_adjoint(mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn, full, lo, _ptr(out),
-                                                        _stream()), 'nlt_pack_conv_wino_weights_adjoint')
-    return out
-
-
-def conv_wino_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm, act=True, alpha=0.3):
-    _check(lib().nlt_conv_wino_forward(mode, _ptr(src), ld, cin, frames, kobs, h, w, _ptr(packed), _ptr(bias), cout, tn,
-                                       _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), _stream()),
-           'nlt_conv_wino_forward')
-
-
-def conv_wino_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, packed, cout, tn, out, ldo, mask_src=None, ldm=0, mask_alpha=0.3,
-                            accumulate=False):
-    _check(lib().nlt_conv_wino_backward_data(adj_mode, _ptr(dpre), ldp, cpre, n, h, w, _ptr(packed), cout, tn, _ptr(out), ldo,
-                                             _ptr(mask_src), ldm, float(mask_alpha), 1 if accumulate else 0, _stream()),
-           'nlt_conv_wino_backward_data')
-
-
-# ---------------------------------------------------------------- bf16 middle of the network
 def pack_conv_tile_weights_adjoint(adj_mode, w_keras, cpre, cout, tn, full, lo):
     """Tile fragments of the ADJOINT conv family read from the layer's own (contiguous) Keras array: output columns = the layer's
     input channels [lo, lo + cout) of `full`."""
-    n = lib().nlt_conv_tile_packed_floats(adj_mode, cpre, cout, tn)
-    if n <= 0:
-        raise NLTError("nlt_conv_tile_packed_floats: unsupported (mode %d, cpre %d, cout %d, tn %d)" % (adj_mode, cpre, cout, tn))
-    out = torch.empty(n, device=w_keras.device, dtype=torch.float32)
-    _check(lib().nlt_pack_conv_tile_weights_adjoint(adj_mode, _ptr(_dense(w_keras, 'w_keras')), cpre, cout, tn, full, lo, _ptr(out),
-                                                    _stream()), 'nlt_pack_conv_tile_weights_adjoint')
-    return out
+    return _pack('nlt_conv_tile_packed_floats', (adj_mode, cpre, cout, tn), 'nlt_pack_conv_tile_weights_adjoint',
+                 (adj_mode, _ptr(_dense(w_keras, 'w_keras')), cpre, cout, tn, full, lo), torch.float32, w_keras.device)
 
 
 def conv_tile_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, packed, cout, tn, out, ldo, mask_src=None, ldm=0, mask_alpha=0.3,
@@ -1150,37 +1022,63 @@ def conv_tile_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, packed, cout, tn
     """Backward-data on the LDS-tiled kernel (include/nlt_hip.h: nlt_conv_tile_backward_data); split as conv_backward_data's
     (transposed k2s2 mode only)."""
     sc, sy, sd, sa, sp = split if split is not None else (0, None, None, 0.0, False)
-    _check(lib().nlt_conv_tile_backward_data(adj_mode, _ptr(dpre), ldp, cpre, n, h, w, _ptr(packed), cout, tn, _ptr(out), ldo,
-                                             _ptr(mask_src), ldm, float(mask_alpha), 1 if accumulate else 0,
-                                             sc, _ptr(sy), _ptr(sd), float(sa), 1 if sp else 0, _stream()),
-           'nlt_conv_tile_backward_data')
+    _call('nlt_conv_tile_backward_data', adj_mode, _ptr(dpre), ldp, cpre, n, h, w, _ptr(packed), cout, tn, _ptr(out), ldo,
+          _ptr(mask_src), ldm, float(mask_alpha), 1 if accumulate else 0, sc, _ptr(sy), _ptr(sd), float(sa), 1 if sp else 0)
 
 
+def conv_c32_supported(mode, cin, cout):
+    return lib().nlt_conv_c32_supported(mode, cin, cout) > 0        # (a query: no stream)
+
+
+def conv_c32_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, out, ldo, mean_out, ldm, act=True, alpha=0.3):
+    """Narrow stride-1 conv (cin 16 | 32 -> 32) with LDS-resident weights; packed = pack_conv_tile_weights(mode, w, cin, 32, 32)."""
+    _call('nlt_conv_c32_forward', mode, _ptr(src), ld, cin, frames, kobs, h, w, _ptr(packed), _ptr(bias), cout, _ptr(out), ldo,
+          _ptr(mean_out), ldm, 1 if act else 0, float(alpha))
+
+
+# ---------------------------------------------------------------- Winograd stride-1 k2 convs (csrc/conv_wino.hip)
+def conv_wino_supported(mode, cin, cout, tn):
+    return lib().nlt_conv_wino_packed_floats(mode, cin, cout, tn) > 0       # (a query: no stream)
+
+
+def pack_conv_wino_weights(mode, w_keras, cin, cout, tn, full=None, lo=0):
+    """G g G^T fragments of a stride-1 k2 kernel; full / lo: the ADJOINT family read from a layer's own array (columns = that
+    layer's input channels [lo, lo + cout) of `full`)."""
+    src = (mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn)
+    if full is None:
+        name, args = 'nlt_pack_conv_wino_weights', src
+    else:
+        name, args = 'nlt_pack_conv_wino_weights_adjoint', src + (full, lo)
+    return _pack('nlt_conv_wino_packed_floats', (mode, cin, cout, tn), name, args, torch.float32, w_keras.device)
+
+
+def conv_wino_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm, act=True, alpha=0.3):
+    _call('nlt_conv_wino_forward', mode, _ptr(src), ld, cin, frames, kobs, h, w, _ptr(packed), _ptr(bias), cout, tn, _ptr(out), ldo,
+          _ptr(mean_out), ldm, 1 if act else 0, float(alpha))
+
+
+def conv_wino_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, packed, cout, tn, out, ldo, mask_src=None, ldm=0, mask_alpha=0.3,
+                            accumulate=False):
+    _call('nlt_conv_wino_backward_data', adj_mode, _ptr(dpre), ldp, cpre, n, h, w, _ptr(packed), cout, tn, _ptr(out), ldo,
+          _ptr(mask_src), ldm, float(mask_alpha), 1 if accumulate else 0)
+
+
+# ---------------------------------------------------------------- bf16 middle of the network
 def pack_conv_tile3_weights(mode, w_keras, cin, cout, tn):
-    n = lib().nlt_conv_tile3_packed_elems(mode, cin, cout, tn)
-    if n <= 0:
-        raise NLTError("nlt_conv_tile3_packed_elems: unsupported (mode %d, cin %d, cout %d, tn %d)" % (mode, cin, cout, tn))
-    out = torch.empty(n, device=w_keras.device, dtype=torch.int16)
-    _check(lib().nlt_pack_conv_tile3_weights(mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn, out.data_ptr(), _stream()),
-           'nlt_pack_conv_tile3_weights')
-    return out
+    return _pack('nlt_conv_tile3_packed_elems', (mode, cin, cout, tn),
+                 'nlt_pack_conv_tile3_weights', (mode, _ptr(_dense(w_keras, 'w_keras')), cin, cout, tn), torch.int16, w_keras.device)
 
 
 def conv_tile3_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm,
                        act=True, alpha=0.3, nprod=6):
     """conv_tile_forward with fp32 operands split into three bf16 terms (precision = f32x3; nprod = 6 or 9 term products)."""
-    _check(lib().nlt_conv_tile3_forward(mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
-                                        _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), _stream()),
-           'nlt_conv_tile3_forward')
+    _call('nlt_conv_tile3_forward', mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
+          _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha))
 
 
 def conv_bf16_pack(mode, w_keras, c0, c1, cout):
-    n = lib().nlt_conv_bf16_packed_elems(mode, c0, c1, cout)
-    if n <= 0:
-        raise NLTError("conv_bf16: unsupported (mode %d, c0 %d, c1 %d, cout %d)" % (mode, c0, c1, cout))
-    out = torch.empty(n, device=w_keras.device, dtype=torch.bfloat16)
-    _check(lib().nlt_conv_bf16_pack(mode, _ptr(_dense(w_keras, 'w_keras')), c0, c1, cout, out.data_ptr(), _stream()), 'nlt_conv_bf16_pack')
-    return out
+    return _pack('nlt_conv_bf16_packed_elems', (mode, c0, c1, cout),
+                 'nlt_conv_bf16_pack', (mode, _ptr(_dense(w_keras, 'w_keras')), c0, c1, cout), torch.bfloat16, w_keras.device)
 
 
 def _any_ptr(t, what):
@@ -1197,36 +1095,30 @@ def conv_bf16_forward(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, w_packed, bia
     p0, f0 = _any_ptr(src0, 'src0')
     p1, f1 = _any_ptr(src1, 'src1')
     po, fo = _any_ptr(out, 'out')
-    _check(lib().nlt_conv_bf16_forward(mode, tile_hint, p0, ld0, c0, f0, p1, ld1, c1, f1, n, h, w,
-                                       _tptr(w_packed, torch.bfloat16, 'w_packed'), _ptr(bias), cout, po, ldo, fo,
-                                       1 if act else 0, float(alpha), _stream()), 'nlt_conv_bf16_forward')
+    _call('nlt_conv_bf16_forward', mode, tile_hint, p0, ld0, c0, f0, p1, ld1, c1, f1, n, h, w,
+          _tptr(w_packed, torch.bfloat16, 'w_packed'), _ptr(bias), cout, po, ldo, fo, 1 if act else 0, float(alpha))
 
 
 def obs_mean_bf16(obs, n, k, hw, c, out, ldo):
     if obs.dtype != torch.bfloat16 or out.dtype != torch.bfloat16:
         raise NLTError("obs_mean_bf16: bfloat16 tensors expected")
-    _check(lib().nlt_obs_mean_bf16(obs.data_ptr(), n, k, hw, c, out.data_ptr(), ldo, _stream()), 'nlt_obs_mean_bf16')
+    _call('nlt_obs_mean_bf16', obs.data_ptr(), n, k, hw, c, out.data_ptr(), ldo)
 
 
 # ---------------------------------------------------------------- bf16 channel mix
 def chmix_bf16_pack(w_keras):
     """Keras (1,1,cin,cout) fp32 kernel -> bf16 MFMA fragments."""
     cin, cout = w_keras.shape[2], w_keras.shape[3]
-    n = lib().nlt_chmix_bf16_packed_elems(cin, cout)
-    if n <= 0:
-        raise NLTError("chmix_bf16: unsupported channel counts %d -> %d" % (cin, cout))
-    out = torch.empty(n, device=w_keras.device, dtype=torch.bfloat16)
-    _check(lib().nlt_chmix_bf16_pack(_ptr(_dense(w_keras, 'w_keras')), cin, cout, out.data_ptr(), _stream()), 'nlt_chmix_bf16_pack')
-    return out
+    return _pack('nlt_chmix_bf16_packed_elems', (cin, cout),
+                 'nlt_chmix_bf16_pack', (_ptr(_dense(w_keras, 'w_keras')), cin, cout), torch.bfloat16, w_keras.device)
 
 
 def chmix_bf16_forward(x, packed, bias, cout, act=True, alpha=0.3):
     """x [..., cin] bf16 (dense NHWC) -> [..., cout] bf16."""
     cin = x.shape[-1]
     out = torch.empty(tuple(x.shape[:-1]) + (cout,), device=x.device, dtype=torch.bfloat16)
-    _check(lib().nlt_chmix_bf16_forward(_tptr(x, torch.bfloat16, 'x'), x.numel() // cin, cin,
-                                        _tptr(packed, torch.bfloat16, 'packed'), _ptr(bias), cout, 1 if act else 0, float(alpha),
-                                        out.data_ptr(), _stream()), 'nlt_chmix_bf16_forward')
+    _call('nlt_chmix_bf16_forward', _tptr(x, torch.bfloat16, 'x'), x.numel() // cin, cin, _tptr(packed, torch.bfloat16, 'packed'),
+          _ptr(bias), cout, 1 if act else 0, float(alpha), out.data_ptr())
     return out
 
 
@@ -1234,34 +1126,31 @@ def chmix_bf16_forward(x, packed, bias, cout, act=True, alpha=0.3):
 def front_pack_weights(wq0, bq0, wo0, bo0, wqa, bqa, wqb, bqb, woa, boa, wob, bob, wh, bh, out=None):
     """out: a blob from an earlier call to refill in place (keeps its address: launch tapes, hipGraphs)."""
     if out is None:
-        out = torch.empty(lib().nlt_front_packed_floats(), device=wq0.device, dtype=torch.float32)
+        out = torch.empty(_size('nlt_front_packed_floats'), device=wq0.device, dtype=torch.float32)
     args = [_ptr(_dense(t, 'weight')) for t in (wq0, bq0, wo0, bo0, wqa, bqa, wqb, bqb, woa, boa, wob, bob, wh, bh)]
-    _check(lib().nlt_front_pack_weights(*args, _ptr(out), _stream()), 'nlt_front_pack_weights')
+    _call('nlt_front_pack_weights', *args, _ptr(out))
     return out
 
 
 def front_forward(base, cvis, lvis, nn_rgb, nn_base, n, k, h, w, packed, add_base, alpha, fm1, obs1, skip3):
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (nn_rgb, 'nn_rgb'), (nn_base, 'nn_base')):
         _dense(t, nm)
-    _check(lib().nlt_front_forward(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w,
-                                   _ptr(packed), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(obs1), _ptr(skip3),
-                                   _stream()), 'nlt_front_forward')
+    _call('nlt_front_forward', _ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w, _ptr(packed),
+          1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(obs1), _ptr(skip3))
 
 
 def front_pack_l2_weights(wq, bq, wo, bo, out=None):
     if out is None:
-        out = torch.empty(lib().nlt_front_l2_packed_floats(), device=wq.device, dtype=torch.float32)
-    _check(lib().nlt_front_pack_l2_weights(_ptr(_dense(wq, 'wq')), _ptr(bq), _ptr(_dense(wo, 'wo')), _ptr(bo), _ptr(out),
-                                           _stream()), 'nlt_front_pack_l2_weights')
+        out = torch.empty(_size('nlt_front_l2_packed_floats'), device=wq.device, dtype=torch.float32)
+    _call('nlt_front_pack_l2_weights', _ptr(_dense(wq, 'wq')), _ptr(bq), _ptr(_dense(wo, 'wo')), _ptr(bo), _ptr(out))
     return out
 
 
 def front2_forward(base, cvis, lvis, nn_rgb, nn_base, n, k, h, w, packed, packed_l2, add_base, alpha, fm1, skip3, qtmp2, otmp2):
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (nn_rgb, 'nn_rgb'), (nn_base, 'nn_base')):
         _dense(t, nm)
-    _check(lib().nlt_front2_forward(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w,
-                                    _ptr(packed), _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(skip3),
-                                    _ptr(qtmp2), _ptr(otmp2), _stream()), 'nlt_front2_forward')
+    _call('nlt_front2_forward', _ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w, _ptr(packed),
+          _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(skip3), _ptr(qtmp2), _ptr(otmp2))
 
 
 def front4_supported(*tensors):
@@ -1273,37 +1162,34 @@ def front4_forward(base, cvis, lvis, nn_rgb, nn_base, n, k, h, w, packed, packed
                    waves_per_simd=0):
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (nn_rgb, 'nn_rgb'), (nn_base, 'nn_base')):
         _dense(t, nm)
-    _check(lib().nlt_front4_forward(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w,
-                                    _ptr(packed), _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(skip3),
-                                    _ptr(qtmp2), _ptr(otmp2), int(waves_per_simd), _stream()), 'nlt_front4_forward')
+    _call('nlt_front4_forward', _ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w, _ptr(packed),
+          _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(skip3), _ptr(qtmp2), _ptr(otmp2),
+          int(waves_per_simd))
 
 
 def front4_forward_u8(diffuse_store, rgb_store, cvis_store, lvis_store, ids, nn_ids, n, k, h, w, packed, packed_l2, add_base,
                       alpha, fm1, skip3, qtmp2, otmp2, waves_per_simd=0):
     u8 = torch.uint8
-    _check(lib().nlt_front4_forward_u8(_tptr(diffuse_store, u8, 'diffuse_store'), _tptr(rgb_store, u8, 'rgb_store'),
-                                       _tptr(cvis_store, u8, 'cvis_store'), _tptr(lvis_store, u8, 'lvis_store'),
-                                       _tptr(ids, torch.int32, 'ids'), _tptr(nn_ids, torch.int32, 'nn_ids'), n, k, h, w,
-                                       _ptr(packed), _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1),
-                                       _ptr(skip3), _ptr(qtmp2), _ptr(otmp2), int(waves_per_simd), _stream()),
-           'nlt_front4_forward_u8')
+    _call('nlt_front4_forward_u8', _tptr(diffuse_store, u8, 'diffuse_store'), _tptr(rgb_store, u8, 'rgb_store'),
+          _tptr(cvis_store, u8, 'cvis_store'), _tptr(lvis_store, u8, 'lvis_store'), _tptr(ids, torch.int32, 'ids'),
+          _tptr(nn_ids, torch.int32, 'nn_ids'), n, k, h, w, _ptr(packed), _ptr(packed_l2), 1 if add_base else 0, float(alpha),
+          _ptr(fm1), _ptr(skip3), _ptr(qtmp2), _ptr(otmp2), int(waves_per_simd))
 
 
 def front4_forward_train(base, cvis, lvis, nn_rgb, nn_base, n, k, h, w, packed, packed_l2, add_base, alpha, fm1, skip3, qtmp2, otmp2,
                          obs1, qtmp1, otmp1):
     """front4_forward that also keeps the level-1 maps the backward pass reads (train mode)."""
-    _check(lib().nlt_front4_forward_train(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w, _ptr(packed),
-                                          _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(skip3), _ptr(qtmp2),
-                                          _ptr(otmp2), _ptr(obs1), _ptr(qtmp1), _ptr(otmp1), _stream()), 'nlt_front4_forward_train')
+    _call('nlt_front4_forward_train', _ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w, _ptr(packed),
+          _ptr(packed_l2), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(skip3), _ptr(qtmp2), _ptr(otmp2), _ptr(obs1),
+          _ptr(qtmp1), _ptr(otmp1))
 
 
 def front_ovr_forward(base, cvis, lvis, n, h, w, packed, packed_l2, p1, s0, p2, add_base, alpha, q1, ldq, skip3, qtmp2):
     """The query-only front launch of the reference's inference mode (include/nlt_hip.h: nlt_front_ovr_forward)."""
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (p1, 'p1'), (s0, 's0'), (p2, 'p2')):
         _dense(t, nm)
-    _check(lib().nlt_front_ovr_forward(_ptr(base), _ptr(cvis), _ptr(lvis), n, h, w, _ptr(packed), _ptr(packed_l2), _ptr(p1),
-                                       _ptr(s0), _ptr(p2), 1 if add_base else 0, float(alpha), _ptr(q1), ldq, _ptr(skip3),
-                                       _ptr(qtmp2), _stream()), 'nlt_front_ovr_forward')
+    _call('nlt_front_ovr_forward', _ptr(base), _ptr(cvis), _ptr(lvis), n, h, w, _ptr(packed), _ptr(packed_l2), _ptr(p1), _ptr(s0),
+          _ptr(p2), 1 if add_base else 0, float(alpha), _ptr(q1), ldq, _ptr(skip3), _ptr(qtmp2))
 
 
 def front_ovr_forward_u8(diffuse_store, cvis_store, lvis_store, ids, n, h, w, packed, packed_l2, p1, s0, p2, add_base, alpha, q1, ldq,
@@ -1312,81 +1198,68 @@ def front_ovr_forward_u8(diffuse_store, cvis_store, lvis_store, ids, n, h, w, pa
     u8 = torch.uint8
     for t, nm in ((p1, 'p1'), (s0, 's0'), (p2, 'p2')):
         _dense(t, nm)
-    _check(lib().nlt_front_ovr_forward_u8(_tptr(diffuse_store, u8, 'diffuse_store'), _tptr(cvis_store, u8, 'cvis_store'),
-                                          _tptr(lvis_store, u8, 'lvis_store'), _tptr(ids, torch.int32, 'ids'), n, h, w,
-                                          _ptr(packed), _ptr(packed_l2), _ptr(p1), _ptr(s0), _ptr(p2), 1 if add_base else 0,
-                                          float(alpha), _ptr(q1), ldq, _ptr(skip3), _ptr(qtmp2), _stream()),
-           'nlt_front_ovr_forward_u8')
+    _call('nlt_front_ovr_forward_u8', _tptr(diffuse_store, u8, 'diffuse_store'), _tptr(cvis_store, u8, 'cvis_store'),
+          _tptr(lvis_store, u8, 'lvis_store'), _tptr(ids, torch.int32, 'ids'), n, h, w, _ptr(packed), _ptr(packed_l2), _ptr(p1),
+          _ptr(s0), _ptr(p2), 1 if add_base else 0, float(alpha), _ptr(q1), ldq, _ptr(skip3), _ptr(qtmp2))
 
 
 def dec_block_forward_map(x, skip, lds, n, h, w, w_s2q, w_s1, b_s1, c, alpha, bias_map, out):
     """One expanding block of the inference mode: [x 2c | query half 4c of `skip`] + bias map (include/nlt_hip.h)."""
-    _check(lib().nlt_dec_block_forward_map(_ptr(_dense(x, 'x')), _ptr(skip), lds, n, h, w, _ptr(_dense(w_s2q, 'w_s2q')),
-                                           _ptr(_dense(w_s1, 'w_s1')), _ptr(b_s1), c, float(alpha), _ptr(_dense(bias_map, 'bias_map')),
-                                           _ptr(_dense(out, 'out')), _stream()), 'nlt_dec_block_forward_map')
+    _call('nlt_dec_block_forward_map', _ptr(_dense(x, 'x')), _ptr(skip), lds, n, h, w, _ptr(_dense(w_s2q, 'w_s2q')),
+          _ptr(_dense(w_s1, 'w_s1')), _ptr(b_s1), c, float(alpha), _ptr(_dense(bias_map, 'bias_map')), _ptr(_dense(out, 'out')))
 
 
 def back_forward_map(x, q1, ldq, skip3, n, h2, w2, w_s2q, w_s1, b_s1, w_head, alpha, bias_map, pred):
     """Last expanding block + head of the inference mode: [x 8 | 16 query channels of the level-1 map] + bias map."""
-    _check(lib().nlt_back_forward_map(_ptr(_dense(x, 'x')), _ptr(q1), ldq, _ptr(_dense(skip3, 'skip3')), n, h2, w2,
-                                      _ptr(_dense(w_s2q, 'w_s2q')), _ptr(_dense(w_s1, 'w_s1')), _ptr(b_s1), _ptr(_dense(w_head, 'w_head')),
-                                      float(alpha), _ptr(_dense(bias_map, 'bias_map')), _ptr(_dense(pred, 'pred')), _stream()),
-           'nlt_back_forward_map')
+    _call('nlt_back_forward_map', _ptr(_dense(x, 'x')), _ptr(q1), ldq, _ptr(_dense(skip3, 'skip3')), n, h2, w2,
+          _ptr(_dense(w_s2q, 'w_s2q')), _ptr(_dense(w_s1, 'w_s1')), _ptr(b_s1), _ptr(_dense(w_head, 'w_head')), float(alpha),
+          _ptr(_dense(bias_map, 'bias_map')), _ptr(_dense(pred, 'pred')))
 
 
 def dec_block_forward(x, cx, skip, cs, n, h, w, w_s2, b_s2, w_s1, b_s1, c, alpha, out):
     """One expanding block (deconv k2s2 + LeakyReLU + deconv k2s1 + LeakyReLU), c = 8 or 16, intermediate in LDS."""
-    _check(lib().nlt_dec_block_forward(_ptr(_dense(x, 'x')), cx, _ptr(_dense(skip, 'skip')), cs, n, h, w, _ptr(w_s2), _ptr(b_s2),
-                                       _ptr(w_s1), _ptr(b_s1), c, float(alpha), _ptr(out), _stream()), 'nlt_dec_block_forward')
+    _call('nlt_dec_block_forward', _ptr(_dense(x, 'x')), cx, _ptr(_dense(skip, 'skip')), cs, n, h, w, _ptr(w_s2), _ptr(b_s2),
+          _ptr(w_s1), _ptr(b_s1), c, float(alpha), _ptr(out))
 
 
 def back_forward(x, fm1, skip3, n, h2, w2, w_s2, b_s2, w_s1, b_s1, w_head, alpha, pred):
-    _check(lib().nlt_back_forward(_ptr(_dense(x, 'x')), _ptr(_dense(fm1, 'fm1')), _ptr(_dense(skip3, 'skip3')), n, h2, w2,
-                                  _ptr(w_s2), _ptr(b_s2), _ptr(w_s1), _ptr(b_s1), _ptr(w_head), float(alpha), _ptr(pred),
-                                  _stream()), 'nlt_back_forward')
+    _call('nlt_back_forward', _ptr(_dense(x, 'x')), _ptr(_dense(fm1, 'fm1')), _ptr(_dense(skip3, 'skip3')), n, h2, w2, _ptr(w_s2),
+          _ptr(b_s2), _ptr(w_s1), _ptr(b_s1), _ptr(w_head), float(alpha), _ptr(pred))
 
 
 def front_forward_train(base, cvis, lvis, nn_rgb, nn_base, n, k, h, w, packed, add_base, alpha, fm1, obs1, skip3, qtmp1, otmp1):
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (nn_rgb, 'nn_rgb'), (nn_base, 'nn_base')):
         _dense(t, nm)
-    _check(lib().nlt_front_forward_train(_ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w,
-                                         _ptr(packed), 1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(obs1),
-                                         _ptr(skip3), _ptr(_dense(qtmp1, 'qtmp1')), _ptr(_dense(otmp1, 'otmp1')),
-                                         _stream()), 'nlt_front_forward_train')
+    _call('nlt_front_forward_train', _ptr(base), _ptr(cvis), _ptr(lvis), _ptr(nn_rgb), _ptr(nn_base), n, k, h, w, _ptr(packed),
+          1 if add_base else 0, float(alpha), _ptr(fm1), _ptr(obs1), _ptr(skip3), _ptr(_dense(qtmp1, 'qtmp1')),
+          _ptr(_dense(otmp1, 'otmp1')))
 
 
 def back_forward_train(x, fm1, skip3, n, h2, w2, w_s2, b_s2, w_s1, b_s1, w_head, alpha, pred, u, v):
-    _check(lib().nlt_back_forward_train(_ptr(_dense(x, 'x')), _ptr(_dense(fm1, 'fm1')), _ptr(_dense(skip3, 'skip3')),
-                                        n, h2, w2, _ptr(w_s2), _ptr(b_s2), _ptr(w_s1), _ptr(b_s1), _ptr(w_head),
-                                        float(alpha), _ptr(pred), _ptr(_dense(u, 'u')), _ptr(_dense(v, 'v')), _stream()),
-           'nlt_back_forward_train')
+    _call('nlt_back_forward_train', _ptr(_dense(x, 'x')), _ptr(_dense(fm1, 'fm1')), _ptr(_dense(skip3, 'skip3')), n, h2, w2,
+          _ptr(w_s2), _ptr(b_s2), _ptr(w_s1), _ptr(b_s1), _ptr(w_head), float(alpha), _ptr(pred), _ptr(_dense(u, 'u')),
+          _ptr(_dense(v, 'v')))
 
 
 def front_backward(base, cvis, lvis, nn_rgb, nn_base, n, k, h, w, dy1q, dy1o, dpred, weights, grads):
     """weights = (wq0, bq0, wo0, bo0, wqa, woa, wh); grads = (dwq0, dbq0, dwo0, dbo0, dwqa, dbqa, dwoa, dboa, dwh),
     accumulated in place (views of the flat gradient bucket)."""
-    need = lib().nlt_front_backward_workspace_floats(n, h, w)
-    if need < 0:
-        raise NLTError("nlt_front_backward: unsupported shape %dx%d" % (h, w))
-    ws = _workspace('front_bwd', base.device, need)
+    ws = _workspace('front_bwd', base.device, _size('nlt_front_backward_workspace_floats', n, h, w))
     for t, nm in ((base, 'base'), (cvis, 'cvis'), (lvis, 'lvis'), (nn_rgb, 'nn_rgb'), (nn_base, 'nn_base'),
                   (dy1q, 'dy1q'), (dy1o, 'dy1o'), (dpred, 'dpred')):
         _dense(t, nm)
     args = [_ptr(t) for t in (base, cvis, lvis, nn_rgb, nn_base)] + [n, k, h, w, _ptr(dy1q), _ptr(dy1o), _ptr(dpred)]
     args += [_ptr(_dense(t, 'weight')) for t in weights] + [_ptr(_dense(t, 'grad')) for t in grads]
-    _check(lib().nlt_front_backward(*args, _ptr(ws), _stream()), 'nlt_front_backward')
+    _call('nlt_front_backward', *args, _ptr(ws))
 
 
 def back_backward(x, fm1, u, v, dpred, n, h2, w2, w_s2, w_s1, w_head, alpha, dx, dfm1, dw_s2, db_s2, dw_s1, db_s1, dw_head, db_head):
     """Gradients of the last expanding block + head; dx / dfm1 written, weight gradients accumulated in place."""
-    need = lib().nlt_back_backward_workspace_floats(n, h2, w2)
-    if need <= 0:
-        raise NLTError("nlt_back_backward_workspace_floats(%d,%d,%d) failed" % (n, h2, w2))
-    ws = _workspace('back_bwd', x.device, need)
+    ws = _workspace('back_bwd', x.device, _size('nlt_back_backward_workspace_floats', n, h2, w2))
     ins = [_ptr(_dense(t, nm)) for t, nm in ((x, 'x'), (fm1, 'fm1'), (u, 'u'), (v, 'v'), (dpred, 'dpred'))]
     wts = [_ptr(_dense(t, 'weight')) for t in (w_s2, w_s1, w_head)]
     outs = [_ptr(_dense(t, 'grad')) for t in (dx, dfm1, dw_s2, db_s2, dw_s1, db_s1, dw_head, db_head)]
-    _check(lib().nlt_back_backward(*ins, n, h2, w2, *wts, float(alpha), *outs, _ptr(ws), _stream()), 'nlt_back_backward')
+    _call('nlt_back_backward', *ins, n, h2, w2, *wts, float(alpha), *outs, _ptr(ws))
 
 
 # ---------------------------------------------------------------- texel-buffer assembly
@@ -1400,10 +1273,9 @@ def cosine_map(locs, normals, valid, occluded, src_loc, want_float=True, want_u8
     cos = torch.empty(shape, device=valid.device, dtype=torch.float64) if want_float else None
     q = torch.empty(shape, device=valid.device, dtype=torch.uint8) if want_u8 else None
     sx, sy, sz = (float(x) for x in src_loc)
-    _check(lib().nlt_cosine_map(_tptr(locs, torch.float64, 'locs'), _tptr(normals, torch.float64, 'normals'),
-                                _tptr(valid, torch.uint8, 'valid'), _tptr(occluded, torch.uint8, 'occluded'),
-                                sx, sy, sz, pixels, _tptr(cos, torch.float64, 'cos'), _tptr(q, torch.uint8, 'q'),
-                                _stream()), 'nlt_cosine_map')
+    _call('nlt_cosine_map', _tptr(locs, torch.float64, 'locs'), _tptr(normals, torch.float64, 'normals'),
+          _tptr(valid, torch.uint8, 'valid'), _tptr(occluded, torch.uint8, 'occluded'), sx, sy, sz, pixels,
+          _tptr(cos, torch.float64, 'cos'), _tptr(q, torch.uint8, 'q'))
     return cos, q
 
 
@@ -1413,8 +1285,7 @@ def albedo(rgb_frames):
     elems = rgb_frames[0].numel()
     out = torch.empty(rgb_frames.shape[1:], device=rgb_frames.device, dtype=torch.float64)
     ws = torch.empty(1, device=rgb_frames.device, dtype=torch.int64)
-    _check(lib().nlt_albedo(_tptr(rgb_frames, torch.uint8, 'rgb_frames'), f, elems, out.data_ptr(), ws.data_ptr(),
-                            _stream()), 'nlt_albedo')
+    _call('nlt_albedo', _tptr(rgb_frames, torch.uint8, 'rgb_frames'), f, elems, out.data_ptr(), ws.data_ptr())
     return out
 
 
@@ -1423,8 +1294,7 @@ def diffuse_base(albedo_, lvis):
     f = lvis.shape[0]
     texels = lvis[0].numel()
     out = torch.empty(tuple(lvis.shape) + (3,), device=lvis.device, dtype=torch.uint8)
-    _check(lib().nlt_diffuse_base(_tptr(albedo_, torch.float64, 'albedo'), _tptr(lvis, torch.uint8, 'lvis'), f, texels,
-                                  out.data_ptr(), _stream()), 'nlt_diffuse_base')
+    _call('nlt_diffuse_base', _tptr(albedo_, torch.float64, 'albedo'), _tptr(lvis, torch.uint8, 'lvis'), f, texels, out.data_ptr())
     return out
 
 
@@ -1437,29 +1307,22 @@ def remap_bilinear(src, mapping, force_kbg=True):
     c = 1 if squeeze else src.shape[2]
     oh, ow, ldm = mapping.shape
     out = torch.empty((oh, ow) if squeeze else (oh, ow, c), device=src.device, dtype=src.dtype)
-    if src.dtype == torch.uint8:
-        fn, what = lib().nlt_remap_bilinear_u8, 'nlt_remap_bilinear_u8'
-    elif src.dtype == torch.float32:
-        fn, what = lib().nlt_remap_bilinear_f32, 'nlt_remap_bilinear_f32'
-    else:
+    name = {torch.uint8: 'nlt_remap_bilinear_u8', torch.float32: 'nlt_remap_bilinear_f32'}.get(src.dtype)
+    if name is None:
         raise NLTError("remap source dtype %s" % src.dtype)
-    _check(fn(_tptr(src, src.dtype, 'src'), h, w, c, _tptr(mapping, mapping.dtype, 'mapping'), _MAP_DTYPES[mapping.dtype],
-              ldm, oh, ow, 1 if force_kbg else 0, out.data_ptr(), _stream()), what)
+    _call(name, _tptr(src, src.dtype, 'src'), h, w, c, _tptr(mapping, mapping.dtype, 'mapping'), _MAP_DTYPES[mapping.dtype],
+          ldm, oh, ow, 1 if force_kbg else 0, out.data_ptr())
     return out
 
 
 def uv_index_map(uvs, values, h, w, max_l1=4, fill=0.0, want_index=False):
     """uvs [P,2], values [P,M] float64 -> grid [h,w,M] float64 (+ int32 sample-index map)."""
     p, m = values.shape
-    nbytes = lib().nlt_uv_index_map_workspace_bytes(h, w, p)
-    if nbytes <= 0:
-        raise NLTError("nlt_uv_index_map_workspace_bytes(%d,%d,%d) failed" % (h, w, p))
-    ws = torch.empty((nbytes + 3) // 4, device=uvs.device, dtype=torch.int32)
+    ws = torch.empty((_size('nlt_uv_index_map_workspace_bytes', h, w, p) + 3) // 4, device=uvs.device, dtype=torch.int32)
     out = torch.empty((h, w, m), device=uvs.device, dtype=torch.float64)
     idx = torch.empty((h, w), device=uvs.device, dtype=torch.int32) if want_index else None
-    _check(lib().nlt_uv_index_map(_tptr(uvs, torch.float64, 'uvs'), _tptr(values, torch.float64, 'values'), p, m, h, w,
-                                  int(max_l1), float(fill), ws.data_ptr(), out.data_ptr(),
-                                  _tptr(idx, torch.int32, 'index_out'), _stream()), 'nlt_uv_index_map')
+    _call('nlt_uv_index_map', _tptr(uvs, torch.float64, 'uvs'), _tptr(values, torch.float64, 'values'), p, m, h, w, int(max_l1),
+          float(fill), ws.data_ptr(), out.data_ptr(), _tptr(idx, torch.int32, 'index_out'))
     return (out, idx) if want_index else out
 
 
@@ -1467,8 +1330,8 @@ def knn_indices(ref_pos, cand_pos, k=1):
     """ref_pos [P,3], cand_pos [Q,3] float64 -> int32 [P,k]."""
     p, q = ref_pos.shape[0], cand_pos.shape[0]
     out = torch.empty((p, k), device=ref_pos.device, dtype=torch.int32)
-    _check(lib().nlt_knn_indices(_tptr(ref_pos, torch.float64, 'ref_pos'), p, _tptr(cand_pos, torch.float64, 'cand_pos'),
-                                 q, k, out.data_ptr(), _stream()), 'nlt_knn_indices')
+    _call('nlt_knn_indices', _tptr(ref_pos, torch.float64, 'ref_pos'), p, _tptr(cand_pos, torch.float64, 'cand_pos'), q, k,
+          out.data_ptr())
     return out
 
 
@@ -1482,8 +1345,8 @@ def psnr_sums(im1, im2, mask=None):
         raise NLTError("psnr_sums: mask has %d pixels, the images %d" % (mask.numel(), pixels))
     ws = torch.empty(512, device=im1.device, dtype=torch.float64)
     out = torch.empty(2, device=im1.device, dtype=torch.float64)
-    _check(lib().nlt_psnr_sums(_ptr(_dense(im1, 'im1')), _ptr(_dense(im2, 'im2')), _tptr(mask, torch.uint8, 'mask'), pixels, c,
-                               ws.data_ptr(), out.data_ptr(), _stream()), 'nlt_psnr_sums')
+    _call('nlt_psnr_sums', _ptr(_dense(im1, 'im1')), _ptr(_dense(im2, 'im2')), _tptr(mask, torch.uint8, 'mask'), pixels, c,
+          ws.data_ptr(), out.data_ptr())
     return out
 
 
@@ -1496,8 +1359,8 @@ def gather_frames_u8(store, ids, out=None):
         out = torch.empty(shape, device=store.device, dtype=torch.float32)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
         raise NLTError("gather_frames_u8: out must be a contiguous float32 tensor of shape %s" % (shape,))
-    _check(lib().nlt_gather_frames_u8(_tptr(store, torch.uint8, 'store'), _tptr(ids, torch.int32, 'ids'), n,
-                                      store[0].numel(), _ptr(out), _stream()), 'nlt_gather_frames_u8')
+    _call('nlt_gather_frames_u8', _tptr(store, torch.uint8, 'store'), _tptr(ids, torch.int32, 'ids'), n, store[0].numel(),
+          _ptr(out))
     return out
 
 
@@ -1515,9 +1378,8 @@ def assemble_batch(diffuse_store, rgb_store, cvis_store, lvis_store, ids, nn_ids
     elif tuple(out['base'].shape) != (n, h, w, 3) or (k and tuple(out['nn_rgb'].shape) != (n, k, h, w, 3)):
         raise NLTError("assemble_batch: `out` was made for another batch shape")
     u8 = torch.uint8
-    _check(lib().nlt_assemble_batch(_tptr(diffuse_store, u8, 'diffuse_store'), _tptr(rgb_store, u8, 'rgb_store'),
-                                    _tptr(cvis_store, u8, 'cvis_store'), _tptr(lvis_store, u8, 'lvis_store'),
-                                    _tptr(ids, torch.int32, 'ids'), _tptr(nn_ids, torch.int32, 'nn_ids'), n, k, h * w,
-                                    1 if test_mode else 0, *[_ptr(out[x]) for x in ('base', 'cvis', 'lvis', 'rgb', 'nn_base', 'nn_rgb')],
-                                    _stream()), 'nlt_assemble_batch')
+    _call('nlt_assemble_batch', _tptr(diffuse_store, u8, 'diffuse_store'), _tptr(rgb_store, u8, 'rgb_store'),
+          _tptr(cvis_store, u8, 'cvis_store'), _tptr(lvis_store, u8, 'lvis_store'), _tptr(ids, torch.int32, 'ids'),
+          _tptr(nn_ids, torch.int32, 'nn_ids'), n, k, h * w, 1 if test_mode else 0,
+          *[_ptr(out[x]) for x in ('base', 'cvis', 'lvis', 'rgb', 'nn_base', 'nn_rgb')])
     return out
