@@ -261,6 +261,25 @@ long nlt_barron_workspace_floats(int n, int h, int w);
 int nlt_barron_loss(const float* pred, const float* gt, int n, int h, int w, float* workspace,
                     float* loss, float* dpred_unit, void* stream);
 
+/* SSIM as tf.image.ssim(img1, img2, max_val) of TF 2.2 fixes it (filter_size 11, filter_sigma 1.5, k1 0.01, k2 0.03, 'VALID'
+ * filtering: one value per image, the mean over channels of the mean of lum * cs over the (h-10) x (w-10) positions).
+ * h, w >= 11 and c = 1 or 3, anything else is NLT_ERR_UNSUPPORTED (the query answers -1).  Float64 partial sums per workgroup
+ * in the workspace, added in workgroup order: no float atomics, the same bits every run, capturable.
+ * workspace: nlt_ssim_workspace_floats(n,h,w,c,want_grad) floats, 8-byte aligned (want_grad: room for the coefficient maps).
+ *
+ * nlt_ssim_loss: losses.SSIM with keep_batch=True -- loss[f] = (1 - ssim(gt_f, pred_f)) / 2 on the c channels as they are; if
+ * dunit != NULL also d loss[f] / d pred [n,h,w,c] (multiply by the upstream per-example gradient with nlt_scale_rows).
+ *   replaces: SSIM.__call__ (nlt/losses.py:75-87) as built by Model._init_loss (nlt/models/nlt.py:80-81). */
+long nlt_ssim_workspace_floats(int n, int h, int w, int c, int want_grad);
+int nlt_ssim_loss(const float* pred, const float* gt, int n, int h, int w, int c, float max_val, float* workspace,
+                  long workspace_floats, float* loss, float* dunit, void* stream);
+
+/* nlt_ssim_values: values[f] (float64) = SSIM of image pair f of im1 / im2 [n,h,w,c]; c = 3 goes to luma first
+ * (0.2126 r + 0.7152 g + 0.0722 b in float64, then float32) and SSIM is taken on that single channel.
+ *   replaces: xm.metric.SSIM(dtype)(im1, im2) (third_party/xiuminglib/xiuminglib/metric.py:154-184, img.py:600-611). */
+int nlt_ssim_values(const float* im1, const float* im2, int n, int h, int w, int c, float max_val, float* workspace,
+                    long workspace_floats, double* values, void* stream);
+
 /* out[f,:] = x[f,:] * scale[f] */
 int nlt_scale_rows(const float* x, const float* scale, int n, long per_row, float* out, void* stream);
 

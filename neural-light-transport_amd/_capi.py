@@ -70,6 +70,9 @@ SIGNATURES = {
     'nlt_barron_workspace_floats': (_c_long, [_c_int] * 3),
     'nlt_barron_loss': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
     'nlt_scale_rows': (_c_int, [_vp, _vp, _c_int, _c_long, _vp, _vp]),
+    'nlt_ssim_workspace_floats': (_c_long, [_c_int] * 5),
+    'nlt_ssim_loss': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _c_long, _vp, _vp, _vp]),
+    'nlt_ssim_values': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _c_long, _vp, _vp]),
     'nlt_sub_forward': (_c_int, [_vp, _vp, _c_long, _vp, _vp]),
     'nlt_finish_pred': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_act_forward': (_c_int, [_vp, _c_long, _c_int, _c_float, _vp, _vp]),
@@ -816,6 +819,36 @@ def barron_loss(pred, gt, want_grad):
     _call_det('nlt_barron_loss', (_ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(ws), _ptr(loss), _ptr(dunit)),
               'barron', pred.device, ('nlt_barron_det_slots_floats', n, h, w))
     return loss, dunit
+
+
+def ssim_loss(pred, gt, max_val, want_grad):
+    """pred, gt [n,h,w,c] (c = 1 or 3, h, w >= 11) -> (loss [n] = (1 - ssim(gt, pred)) / 2, d loss[f] / d pred or None).  One
+    form for both modes: its sums are ordered (csrc/ssim.hip), so `deterministic` has nothing to switch."""
+    _same_shape(pred, gt, 'ssim_loss')
+    if pred.dim() != 4:
+        raise NLTError("ssim_loss: [n,h,w,c] expected, got %s" % (tuple(pred.shape),))
+    n, h, w, c = pred.shape
+    ws = torch.empty(_size('nlt_ssim_workspace_floats', n, h, w, c, 1 if want_grad else 0, what='h, w >= 11 and 1 or 3 channels'),
+                     device=pred.device, dtype=torch.float32)
+    loss = torch.empty(n, device=pred.device, dtype=torch.float32)
+    dunit = torch.empty_like(pred) if want_grad else None
+    _call('nlt_ssim_loss', _ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, c, float(max_val), _ptr(ws), ws.numel(),
+          _ptr(loss), _ptr(dunit))
+    return loss, dunit
+
+
+def ssim_values(im1, im2, max_val):
+    """im1, im2 [n,h,w,c] float32 (c = 1, or 3: luma first) -> SSIM of every pair as a float64 CUDA tensor [n], one launch."""
+    _same_shape(im1, im2, 'ssim_values')
+    if im1.dim() != 4:
+        raise NLTError("ssim_values: [n,h,w,c] expected, got %s" % (tuple(im1.shape),))
+    n, h, w, c = im1.shape
+    ws = torch.empty(_size('nlt_ssim_workspace_floats', n, h, w, c, 0, what='h, w >= 11 and 1 or 3 channels'),
+                     device=im1.device, dtype=torch.float32)
+    out = torch.empty(n, device=im1.device, dtype=torch.float64)
+    _call('nlt_ssim_values', _ptr(_dense(im1, 'im1')), _ptr(_dense(im2, 'im2')), n, h, w, c, float(max_val), _ptr(ws), ws.numel(),
+          out.data_ptr())
+    return out
 
 
 def scale_rows(x, scale):

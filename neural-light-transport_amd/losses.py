@@ -1,5 +1,5 @@
-"""Losses with the reference's call signatures (nlt/losses.py:39-53,90-118) on HIP kernels
-(csrc/train_ops.hip, csrc/barron.hip); torch.autograd.Function is glue only."""
+"""Losses with the reference's call signatures (nlt/losses.py:39-53,75-87,90-118) on HIP kernels
+(csrc/train_ops.hip, csrc/barron.hip, csrc/ssim.hip); torch.autograd.Function is glue only."""
 import torch
 
 from . import _capi as C
@@ -28,6 +28,18 @@ class _BarronFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         return C.scale_rows(ctx.dunit, gloss.contiguous()), None
+
+
+class _SSIMFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, max_val):
+        loss, dunit = C.ssim_loss(pred.contiguous(), gt.contiguous(), max_val, bool(ctx.needs_input_grad[0]))
+        ctx.dunit = dunit
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        return C.scale_rows(ctx.dunit, gloss.contiguous()), None, None
 
 
 class _L2WeightedFn(torch.autograd.Function):
@@ -96,4 +108,21 @@ class Barron:
             gt, pred = _MulFn.apply(gt, alpha), _MulFn.apply(pred, alpha)
         assert tuple(pred.shape[1:3]) == (self.imh, self.imw), (tuple(pred.shape), self.imh, self.imw)
         per = _BarronFn.apply(pred, gt)
+        return per if keep_batch else per.mean()
+
+
+class SSIM:
+    """(1 - tf.image.ssim(gt, pred, dynamic_range)) / 2 on the RGB channels as they are (nlt/losses.py:75-87); `weights`
+    alpha-blends gt and pred against zeros first.  Scalar mean over the batch, the reference's only form; keep_batch=True
+    returns the per-example [N] vector instead -- the one addition to the reference's class, whose __call__ takes no
+    keep_batch and so cannot be called by its own train step (trainvali.py:275,299)."""
+
+    def __init__(self, dynamic_range):
+        self.dynamic_range = float(dynamic_range)       # i.e. max - min
+
+    def __call__(self, gt, pred, keep_batch=False, weights=None):
+        if weights is not None:
+            alpha = torch.as_tensor(weights, dtype=torch.float32, device=pred.device).expand(pred.shape).contiguous()
+            gt, pred = _MulFn.apply(gt, alpha), _MulFn.apply(pred, alpha)
+        per = _SSIMFn.apply(pred, gt, self.dynamic_range)
         return per if keep_batch else per.mean()

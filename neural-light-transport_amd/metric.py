@@ -16,10 +16,9 @@ def _on_device(x):
     return torch.from_numpy(np.ascontiguousarray(x)).to(DEVICE)
 
 
-class PSNR:
-    """xm.metric.PSNR (metric.py:105-151): Peak Signal-to-Noise Ratio in dB on luma (0.2126 r + 0.7152 g + 0.0722 b for
-    3-channel inputs), float64 arithmetic, optional H x W logical mask.  `dtype` fixes the dynamic range the way
-    metric.Base does: 1 for float types, max - min for unsigned integer types."""
+class Base:
+    """xm.metric.Base (metric.py:35-72): `dtype` fixes the dynamic range -- 1 for float types, max - min for unsigned integer
+    types."""
 
     def __init__(self, dtype):
         self.dtype = np.dtype(dtype)
@@ -30,6 +29,12 @@ class PSNR:
             self.drange = float(info.max - info.min)
         else:
             raise NotImplementedError(self.dtype.kind)
+
+
+class PSNR(Base):
+    """xm.metric.PSNR (metric.py:105-151): Peak Signal-to-Noise Ratio in dB on luma (0.2126 r + 0.7152 g + 0.0722 b for
+    3-channel inputs), float64 arithmetic, optional H x W logical mask.  `dtype` fixes the dynamic range the way
+    metric.Base does: 1 for float types, max - min for unsigned integer types."""
 
     def __call__(self, im1, im2, mask=None):
         """im1, im2: [H,W] / [H,W,1] / [H,W,3] torch CUDA tensors (float32 storage) in [0, drange] -> float dB.
@@ -47,3 +52,36 @@ class PSNR:
         se, n = C.psnr_sums(a, b, m).tolist()
         mse = se / n
         return 10 * math.log10((self.drange ** 2) / mse) if mse > 0 else float('inf')
+
+
+class SSIM(Base):
+    """xm.metric.SSIM (metric.py:154-184): tf.image.ssim(im1, im2, max_val=drange) of TF 2.2 on luma -- 3-channel inputs go to
+    0.2126 r + 0.7152 g + 0.0722 b in float64 and then to float32 (TF casts), SSIM is taken on that single channel
+    (csrc/ssim.hip).  `dtype` fixes the dynamic range exactly as for PSNR.  Parity-unpinned: no TensorFlow to run against;
+    the semantics are restated in tests/ssim_ref.py."""
+
+    def __call__(self, im1, im2):
+        """im1, im2: [H,W] / [H,W,1] / [H,W,3] in [0, drange], device tensors, host tensors or NumPy arrays -> float."""
+        im1, im2 = self._checked(im1, im2, 2)
+        return self._values(im1[None], im2[None])[0]
+
+    def batch(self, im1, im2):
+        """im1, im2 [N,H,W,C] (C = 1 or 3) -> N floats, one launch; each equals the per-image call bit for bit."""
+        im1, im2 = self._checked(im1, im2, 3)
+        return self._values(im1, im2)
+
+    @staticmethod
+    def _checked(im1, im2, channel_axis):
+        im1, im2 = _on_device(im1), _on_device(im2)
+        if tuple(im1.shape) != tuple(im2.shape):
+            raise AssertionError("The two images are not even of the same shape")
+        if im1.dim() == channel_axis:
+            im1, im2 = im1.unsqueeze(-1), im2.unsqueeze(-1)
+        if im1.dim() != channel_axis + 1:
+            raise ValueError("Input must be H-by-W or H-by-W-by-C (a batch: N-by-H-by-W-by-C), but is %dD" % im1.dim())
+        if im1.shape[-1] not in (1, 3):
+            raise NotImplementedError("%d-channel images" % im1.shape[-1])
+        return im1.float().contiguous(), im2.float().contiguous()
+
+    def _values(self, im1, im2):
+        return C.ssim_values(im1, im2, self.drange).tolist()

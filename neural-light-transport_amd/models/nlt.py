@@ -144,9 +144,13 @@ class Model(BaseModel):
                 loss = losses.L2()
             elif loss_name == 'barron':
                 loss = losses.Barron(self.imw, self.imh)
-            elif loss_name in ('lpips', 'l1', 'ssim'):
+            elif loss_name == 'ssim':
+                # the reference's SSIM.__call__ has no keep_batch and crashes its own train step;
+                # losses.SSIM here takes it (csrc/ssim.hip)
+                loss = losses.SSIM(1 - 0)                       # nlt/models/nlt.py:80-81
+            elif loss_name in ('lpips', 'l1'):
                 # lpips: the frozen AlexNet blob is not part of the reference tree
-                # (.MISSING_LARGE_BLOBS); l1/ssim have no keep_batch and crash the
+                # (.MISSING_LARGE_BLOBS); l1 has no keep_batch and crashes the
                 # reference's own train step
                 raise NotImplementedError(loss_name)
             else:
