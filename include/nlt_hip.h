@@ -37,7 +37,13 @@ typedef enum {
   NLT_CONV_K2S2 = 1,   /* Conv2D k2 s2: out (h/2,w/2), h,w even; W keras (2,2,Cin,Cout)            */
   NLT_CONV_K2S1 = 2,   /* Conv2D k2 s1: out (h,w), zero pad bottom/right; W keras (2,2,Cin,Cout)   */
   NLT_DECONV_K2S2 = 3, /* Conv2DTranspose k2 s2: out (2h,2w); W keras (2,2,Cout,Cin)               */
-  NLT_DECONV_K2S1 = 4  /* Conv2DTranspose k2 s1: out (h,w), zero pad top/left; W (2,2,Cout,Cin)    */
+  NLT_DECONV_K2S1 = 4, /* Conv2DTranspose k2 s1: out (h,w), zero pad top/left; W (2,2,Cout,Cin)    */
+  /* kernel = 3 (csrc/conv_k3.hip): served by the nlt_conv_k3_* entry points only; every other entry point that takes a
+   * mode answers these four with an error status. */
+  NLT_CONV_K3S1 = 5,   /* Conv2D k3 s1: out (h,w), zero pad 1 / 1; W keras (3,3,Cin,Cout)                     */
+  NLT_CONV_K3S2 = 6,   /* Conv2D k3 s2: out (h/2,w/2), h,w even, zero pad 0 / 1; W keras (3,3,Cin,Cout)       */
+  NLT_DECONV_K3S1 = 7, /* Conv2DTranspose k3 s1: out (h,w): the full transposed conv less its outer ring      */
+  NLT_DECONV_K3S2 = 8  /* Conv2DTranspose k3 s2: out (2h,2w): the first 2h x 2w of the full transposed conv   */
 } nlt_conv_mode;
 
 typedef enum {
@@ -928,6 +934,43 @@ long nlt_chmix_bf16_packed_elems(int cin, int cout);
 int nlt_chmix_bf16_pack(const float* w_keras, int cin, int cout, unsigned short* packed, void* stream);
 int nlt_chmix_bf16_forward(const unsigned short* x, long texels, int cin, const unsigned short* packed,
                            const float* bias, int cout, int act, float alpha, unsigned short* out, void* stream);
+
+/* ======================= 3x3 convs (csrc/conv_k3.hip) =======================
+ * Conv2D / Conv2DTranspose(n, 3, strides 1 | 2, padding='same') on dense NHWC fp32 tensors, exact fp32; x = 0 outside the image.
+ *   NLT_CONV_K3S1    y[i,j,o] = b[o] + sum_{a,b,c} x[i+a-1, j+b-1, c] W[a,b,c,o]
+ *   NLT_CONV_K3S2    y[i,j,o] = b[o] + sum_{a,b,c} x[2i+a, 2j+b, c]   W[a,b,c,o]
+ *   NLT_DECONV_K3S1  y[i,j,o] = b[o] + sum_{a,b,c} x[i+1-a, j+1-b, c] W[a,b,o,c]
+ *   NLT_DECONV_K3S2  y[m,n,o] = b[o] + sum over the taps with (m-a), (n-b) even of x[(m-a)/2, (n-b)/2, c] W[a,b,o,c]
+ * (h, w, cin) are the layer's INPUT dims in all four entry points; a stride-2 mode on an odd h or w is NLT_ERR_UNSUPPORTED
+ * (TF would pad; the network's resolutions are multiples of 2^levels).  act != 0 applies LeakyReLU(alpha).
+ * algo: NLT_ALGO_MFMA (cin % 4 == 0, cout % 4 == 0, 16-byte aligned x and w_keras: input tile + halo and the live taps'
+ * weights staged in LDS, v_mfma_f32_16x16x4_f32), NLT_ALGO_DIRECT (any channel count), NLT_ALGO_AUTO (MFMA when it can).
+ * No packed weights: the kernels read the Keras array.
+ *   replaces: tf.keras Conv2D / Conv2DTranspose (+ LeakyReLU / ReLU) as built by nlt/networks/elements.py:26-39,72-73 with
+ *             kernel = 3 (the layer stacks of nlt/networks/convnet.py:50-76).
+ */
+int nlt_conv_k3_forward(int mode, int algo, const float* x, int n, int h, int w, int cin,
+                        const float* w_keras, const float* bias, int cout, float* y,
+                        int act, float alpha, void* stream);
+
+/* Gradient w.r.t. the whole input of the layer `mode` from dpre [n,oh,ow,cout], the gradient w.r.t. its pre-activation
+ * output: the opposite family's forward (same stride) on the layer's own Keras array with the two channel axes swapped,
+ * no bias, no activation.  dx [n,h,w,cin] is overwritten.
+ *   replaces: the input-gradient half of tf.GradientTape.gradient through the layers of nlt/networks/elements.py:26-39
+ *             (nlt/trainvali.py:279). */
+int nlt_conv_k3_backward_data(int mode, int algo, const float* dpre, int n, int h, int w, int cin,
+                              const float* w_keras, int cout, float* dx, void* stream);
+
+/* dW += the weight gradient, db += sum dpre (db may be NULL), accumulated into the layer's Keras-layout buffers like
+ * nlt_conv_backward_weights (zero them first; an observation layer adds its k applications).  No float atomics: slices of
+ * the texel rows are summed into `workspace` (nlt_conv_k3_wgrad_workspace_floats() floats) and added in index order, so
+ * equal inputs give bit-identical results.
+ *   replaces: tape.gradient(loss, layer.kernel / layer.bias) for the layers of nlt/networks/elements.py:26-39 with
+ *             kernel = 3 (nlt/trainvali.py:279). */
+long nlt_conv_k3_wgrad_workspace_floats(int mode, int n, int h, int w, int cin, int cout);
+int nlt_conv_k3_backward_weights(int mode, const float* x, int n, int h, int w, int cin,
+                                 const float* dpre, int cout, float* dw_keras, float* dbias,
+                                 float* workspace, long workspace_floats, void* stream);
 
 #ifdef __cplusplus
 }

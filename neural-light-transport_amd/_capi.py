@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('NLT_HIP_LIB') or os.path.join(_HERE, 'libnlt_hip.so')   # NLT_HIP_LIB: A/B of two builds (tools/ab_front.py)
 
 CONV1X1, CONV_K2S2, CONV_K2S1, DECONV_K2S2, DECONV_K2S1 = range(5)
+CONV_K3S1, CONV_K3S2, DECONV_K3S1, DECONV_K3S2 = range(5, 9)       # kernel = 3: the nlt_conv_k3_* entry points only
 ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA = range(3)
 
 _c_int, _c_long, _c_float, _vp = ctypes.c_int, ctypes.c_long, ctypes.c_float, ctypes.c_void_p
@@ -174,6 +175,11 @@ SIGNATURES = {
     'nlt_conv_backward_weights_det_workspace_floats': (_c_long, [_c_int] * 7),
     'nlt_conv_backward_weights_det': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_int, _c_int,
                                                _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _c_long, _vp]),
+    # kernel = 3 (csrc/conv_k3.hip)
+    'nlt_conv_k3_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_float, _vp]),
+    'nlt_conv_k3_backward_data': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
+    'nlt_conv_k3_wgrad_workspace_floats': (_c_long, [_c_int] * 6),
+    'nlt_conv_k3_backward_weights': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_long, _vp]),
 }
 
 _real = None
@@ -682,6 +688,28 @@ def conv_backward_weights_narrow(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, dp
     ws = _workspace(_per_stream('wgrad_narrow'), src0.device, _size('nlt_wgrad_narrow_workspace_floats', mode, c0, c1, n, h, w, cout))
     _call('nlt_conv_backward_weights_narrow', mode, _ptr(src0), ld0, c0, _ptr(src1), ld1, c1, n, h, w, _ptr(dpre), ldp, cout,
           _ptr(dw), _ptr(db), _ptr(ws), ws.numel())
+
+
+def conv_k3_forward(mode, x, w_keras, bias, cout, out, act=False, alpha=0.3, algo=ALGO_AUTO):
+    """3x3 Conv2D / Conv2DTranspose (+ fused LeakyReLU / ReLU) on a dense [n,h,w,cin] tensor; reads the Keras array."""
+    n, h, w, cin = _dense(x, 'x').shape
+    _call('nlt_conv_k3_forward', mode, algo, _ptr(x), n, h, w, cin, _ptr(_dense(w_keras, 'w_keras')), _ptr(bias), cout,
+          _ptr(_dense(out, 'out')), 1 if act else 0, float(alpha))
+
+
+def conv_k3_backward_data(mode, dpre, w_keras, n, h, w, cin, cout, dx, algo=ALGO_AUTO):
+    """dx [n,h,w,cin] of the layer `mode` from dpre [n,oh,ow,cout]: the opposite family's forward on the layer's own array."""
+    _call('nlt_conv_k3_backward_data', mode, algo, _ptr(_dense(dpre, 'dpre')), n, h, w, cin, _ptr(_dense(w_keras, 'w_keras')), cout,
+          _ptr(_dense(dx, 'dx')))
+
+
+def conv_k3_backward_weights(mode, x, dpre, cout, dw, db):
+    """dw += weight gradient, db += bias gradient of a 3x3 layer: two passes through a cached workspace, no float atomics, so the
+    plain entry IS the deterministic one (`_call`, not `_call_det`)."""
+    n, h, w, cin = _dense(x, 'x').shape
+    ws = _workspace(_per_stream('wgrad_k3'), x.device, _size('nlt_conv_k3_wgrad_workspace_floats', mode, n, h, w, cin, cout))
+    _call('nlt_conv_k3_backward_weights', mode, _ptr(x), n, h, w, cin, _ptr(_dense(dpre, 'dpre')), cout, _ptr(dw), _ptr(db),
+          _ptr(ws), ws.numel())
 
 
 def lrelu_backward(g, ldg, y, ldy, c, texels, alpha, out, ldo):

@@ -1,6 +1,6 @@
 """Layer-by-layer execution of the two-path U-Net with a hand-rolled backward tape: the path for the config branches the
 fused RenderPlan does not cover (act = elu, norm = pixel / layer / batch, pool = max / avg and the `upconv` that comes with
-pooling -- nlt/networks/elements.py:42-56,69-94,103-121; nlt/networks/convnet.py:50-76).
+pooling, kernel = 3 -- nlt/networks/elements.py:26-56,69-94,103-121; nlt/networks/convnet.py:50-76).
 
 It follows Model._call statement for statement (nlt/models/nlt.py:141-199: per-layer observation maps, their mean,
 concat with the query map, the skip stack, the bottleneck self-concat) on the generic layer objects of
@@ -62,6 +62,13 @@ def conv(tape, layer, x, act=None):
         g = g.contiguous()
         if act is not None:
             g = act.backward(g, y)                                   # mask from the output: y > 0 <=> pre-activation > 0
+        if layer.kernel_size == 3:
+            C.conv_k3_backward_weights(layer.mode, xv, g, cout, layer.dkernel, layer.dbias)
+            if x.back is None and not x.parents:
+                return (None,)
+            dx = torch.empty_like(xv)
+            C.conv_k3_backward_data(layer.mode, g, layer.kernel.detach(), n, h, w, cin, cout, dx)
+            return (dx,)
         C.conv_backward_weights(layer.mode, xv, cin, cin, None, 0, 0, n, h, w, g, cout, cout, layer.dkernel, layer.dbias)
         if x.back is None and not x.parents:
             return (None,)

@@ -103,7 +103,7 @@ class Model(BaseModel):
         self.uvw = config.getint('DEFAULT', 'uvw')
         self.use_obs = config.getboolean('DEFAULT', 'use_obs')
         self.skip_connect_base = config.getboolean('DEFAULT', 'skip_connect_base')
-        # config branches the fused plan does not execute (act = elu, a norm, pooling + upconv) run layer by layer (generic.py)
+        # config branches the fused plan does not execute (act = elu, a norm, pooling + upconv, kernel = 3) run layer by layer (generic.py)
         self.generic = not all(l.is_plain() for net in self.net.values() for l in net.layers if hasattr(l, 'is_plain'))
         self.psnr = metric.PSNR(np.float32)                      # nlt/models/nlt.py:64
         self.plan = RenderPlan(self.net['query'], self.net['obs'], self.use_obs)
@@ -111,6 +111,9 @@ class Model(BaseModel):
         self.plan.precision = config.get('DEFAULT', 'precision', fallback=self.plan.precision)
         if self.plan.precision not in ('fp32', 'bf16', 'f32x3', 'f32x3_9'):
             raise NotImplementedError("precision = %s" % self.plan.precision)
+        if net_args[2] == 3 and self.plan.precision != 'fp32':
+            # the 3x3 kernels (csrc/conv_k3.hip) are exact fp32 and run layer by layer: there is no bf16 / split-bf16 form to pick
+            raise NotImplementedError("precision = %s with kernel = 3" % self.plan.precision)
         self.conv_algo = C.ALGO_AUTO
         # hipGraph replay of the inference forward (opt-in: NLT_GRAPH=1 or model.use_graphs = True).  The ~36 launches
         # of a step cost ~0.6 ms of host time; for small workloads (512^2, k = 1) that is the whole step.

@@ -7,6 +7,10 @@ The released-config branch (conv, deconv, leakyrelu / relu, iden, norm / pool 'n
 (generic.py; csrc/branches.hip), and so are norm = layer / batch (csrc/norms.hip), whose gamma / beta are two more
 slots per layer of the model's flat parameter bucket.  norm = instance raises NotImplementedError: it is tf.contrib,
 which TF 2.2 does not have -- the reference itself cannot run it.
+
+kernel = 3 (3x3 Conv2D / Conv2DTranspose, stride 1 or 2, 'same') also runs layer by layer: csrc/conv_k3.hip reads the Keras
+array as it is (no packed fragments), in exact fp32 only.  A block that holds a 3x3 conv is not `is_plain()`, so the fused
+plan, its tapes and graphs are never asked for one.  kernel >= 4 raises NotImplementedError.
 """
 import math
 
@@ -41,11 +45,16 @@ class Conv2D(Layer):
     """tf.keras.layers.Conv2D / Conv2DTranspose(n_ch_out, kernel_size, strides, padding='same')."""
 
     def __init__(self, n_ch_out, kernel_size, stride, transpose=False):
-        if kernel_size not in (1, 2) or stride not in (1, 2) or (kernel_size == 1 and (stride != 1 or transpose)):
+        if kernel_size not in (1, 2, 3) or stride not in (1, 2) or (kernel_size == 1 and (stride != 1 or transpose)):
             raise NotImplementedError("kernel %d stride %d" % (kernel_size, stride))
         self.n_ch_out, self.kernel_size, self.stride, self.transpose = n_ch_out, kernel_size, stride, transpose
         if kernel_size == 1:
             self.mode = C.CONV1X1
+        elif kernel_size == 3:
+            if transpose:
+                self.mode = C.DECONV_K3S2 if stride == 2 else C.DECONV_K3S1
+            else:
+                self.mode = C.CONV_K3S2 if stride == 2 else C.CONV_K3S1
         elif transpose:
             self.mode = C.DECONV_K2S2 if stride == 2 else C.DECONV_K2S1
         else:
@@ -178,7 +187,9 @@ class Conv2D(Layer):
         return ent[1]
 
     ADJOINT = {C.CONV_K2S2: C.DECONV_K2S2, C.CONV_K2S1: C.DECONV_K2S1,
-               C.DECONV_K2S2: C.CONV_K2S2, C.DECONV_K2S1: C.CONV_K2S1}
+               C.DECONV_K2S2: C.CONV_K2S2, C.DECONV_K2S1: C.CONV_K2S1,
+               C.CONV_K3S2: C.DECONV_K3S2, C.CONV_K3S1: C.DECONV_K3S1,
+               C.DECONV_K3S2: C.CONV_K3S2, C.DECONV_K3S1: C.CONV_K3S1}
 
     def packed_adjoint(self, lo, hi):
         """Fragments for backward-DATA w.r.t. forward input channels [lo, hi): the adjoint conv
@@ -202,11 +213,15 @@ class Conv2D(Layer):
                                  dict(kind=C.REPACK_TILE, mode=adj, c0=self.n_ch_out, c1=0, cout=hi - lo, tn=tn, lo=lo, full=self.cin))
 
     def out_hw(self, h, w):
-        if self.mode == C.CONV_K2S2:
+        if self.mode in (C.CONV_K2S2, C.CONV_K3S2):
             return h // 2, w // 2
-        if self.mode == C.DECONV_K2S2:
+        if self.mode in (C.DECONV_K2S2, C.DECONV_K3S2):
             return 2 * h, 2 * w
         return h, w
+
+    def is_plain(self):
+        """Can the fused RenderPlan execute this layer?  (Not a 3x3 one: those run layer by layer, csrc/conv_k3.hip.)"""
+        return self.kernel_size != 3
 
     def __call__(self, x, act=None):
         """x [N,H,W,Cin] dense -> [N,H',W',Cout]; `act` (an Act layer) is fused when given."""
@@ -215,6 +230,10 @@ class Conv2D(Layer):
         assert cin == self.cin, "layer built for %d input channels, got %d" % (self.cin, cin)
         oh, ow = self.out_hw(h, w)
         out = torch.empty((n, oh, ow, self.n_ch_out), device=x.device, dtype=torch.float32)
+        if self.kernel_size == 3:                   # reads the Keras array: no fragment pack to keep fresh
+            C.conv_k3_forward(self.mode, x.contiguous(), self.kernel.detach(), self.bias.detach(), self.n_ch_out, out,
+                              act=act is not None, alpha=act.alpha if act is not None else 0.0)
+            return out
         use_mfma = cin % 4 == 0 and self.n_ch_out % 4 == 0
         C.conv_forward(self.mode, x.contiguous(), cin, cin, None, 0, 0, n, h, w,
                        self.kernel.detach(), self.packed(cin, 0) if use_mfma else None, self.bias.detach(),
@@ -491,7 +510,8 @@ class Sequential(Layer):
 
     def is_plain(self):
         """Only convs, identities and fused-able LeakyReLU / ReLU activations (what RenderPlan executes)?"""
-        return all(isinstance(l, (Conv2D, Identity)) or (isinstance(l, Act) and l.kind == 'lrelu') for l in self.layers)
+        return all((isinstance(l, Conv2D) and l.is_plain()) or isinstance(l, Identity) or (isinstance(l, Act) and l.kind == 'lrelu')
+                   for l in self.layers)
 
     def convs(self):
         """[(Conv2D, Act or None)] in execution order."""
