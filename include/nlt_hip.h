@@ -920,6 +920,20 @@ int nlt_pack_conv_tile3_weights(int mode, const float* w_keras, int cin, int cou
 int nlt_conv_tile3_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
                            const unsigned short* packed, const float* bias, int cout, int tn,
                            float* out, int ldo, float* mean_out, int ldm, int act, float alpha, void* stream);
+/*
+ * The RESIDENT form of nlt_conv_tile3_forward (nprod = 6 / 9 only): persistent workgroups, each holding the split weights of one
+ * output-channel group (cin * tn / 16 * 384 bytes) in LDS for as long as it works on that group, so a stage moves only its texel
+ * slab.  Same arguments, same `packed`, and the same additions per output element in the same order: out / mean_out are
+ * bit-identical to nlt_conv_tile3_forward's.  Stride 1 at tn = 32: one 8-wave workgroup per CU, every wave with a 4 x 16 (2 x 16
+ * from cin = 128) tile and a texel staging region of its own, no workgroup barrier in the steady state.  Otherwise the streaming
+ * kernel's 8 x 16 tile and barrier per stage.  max_workgroups: 0 = sized from the device (two 4-wave workgroups per CU, or one
+ * 8-wave workgroup where two do not fit the CU's 160 KB of LDS); > 0 caps the grid (tests: several items per workgroup at tiny
+ * shapes).  NLT_ERR_UNSUPPORTED, nothing launched, when the group's weights + the texel staging exceed 160 KB, or for
+ * nprod = 1 / 3: the caller takes nlt_conv_tile3_forward.
+ */
+int nlt_conv_tile3r_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                            const unsigned short* packed, const float* bias, int cout, int tn,
+                            float* out, int ldo, float* mean_out, int ldm, int act, float alpha, int max_workgroups, void* stream);
 
 /* ======================= bf16 channel mix (csrc/chmix_bf16.hip) =======================
  * 1x1 conv with bf16 activations / weights and fp32 accumulation on v_mfma_f32_16x16x32_bf16: the literal dense GEMM

@@ -138,6 +138,8 @@ SIGNATURES = {
     'nlt_pack_conv_tile3_weights': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_conv_tile3_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int,
                                         _vp, _c_int, _vp, _c_int, _c_int, _c_float, _vp]),
+    'nlt_conv_tile3r_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int,
+                                         _vp, _c_int, _vp, _c_int, _c_int, _c_float, _c_int, _vp]),
     'nlt_conv_bf16_packed_elems': (_c_long, [_c_int] * 4),
     'nlt_conv_bf16_pack': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_conv_bf16_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int,
@@ -1135,6 +1137,31 @@ def conv_tile3_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cou
     """conv_tile_forward with fp32 operands split into three bf16 terms (precision = f32x3; nprod = 6 or 9 term products)."""
     _call('nlt_conv_tile3_forward', mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
           _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha))
+
+
+def conv_tile3r_plan(mode, cin, tn):
+    """The resident form's launch shape as csrc/conv_tile3.hip's launcher works it out: (LDS bytes of a workgroup, waves per
+    workgroup, workgroups per CU, output rows of a tile), or None where it refuses (the group's weights + the texel staging exceed
+    the CU's 160 KB).  Stride 1 at 32 channels per group: 8 waves with a 4 x 16 (else 2 x 16) tile and a staging region each;
+    otherwise the 8 x 16 tile of a workgroup and two shared texel stages."""
+    if mode not in (CONV_K2S1, CONV_K2S2) or cin % 16 or tn not in (32, 64):
+        return None
+    if mode == CONV_K2S1 and tn == 32:
+        for rows in (4, 2):
+            lds = cin * 768 + 8 * 6 * (((rows + 1) * 17 + 15) // 16 * 16) * 16
+            if lds <= 160 * 1024:
+                return (lds, 8, 1, rows)
+    lds = cin * (tn // 16) * 384 + 2 * 6 * (160 if mode == CONV_K2S1 else 272) * 16
+    if lds > 160 * 1024:
+        return None
+    return (lds, 8, 1, 8) if 2 * lds > 160 * 1024 else (lds, 4, 2, 8)
+
+
+def conv_tile3r_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm,
+                        act=True, alpha=0.3, nprod=6, max_workgroups=0):
+    """conv_tile3_forward by persistent workgroups with the group's split weights resident in LDS: the same bits."""
+    _call('nlt_conv_tile3r_forward', mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
+          _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), max_workgroups)
 
 
 def conv_bf16_pack(mode, w_keras, c0, c1, cout):

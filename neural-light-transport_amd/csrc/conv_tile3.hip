@@ -297,8 +297,475 @@ __global__ __launch_bounds__(256, 2) void conv_tile3_kernel(Tile3P p) {
   }
 }
 
+// RESIDENT form (stride 2, and 64 channels per group; the stride-1 conv at 32 channels per group: conv_tile3w_kernel below):
+// persistent workgroups, each with the split weights of ONE output-channel group in LDS for as long as it works on
+// that group (cin x TNT x 384 bytes, copied once), so a stage moves only its texel slab: load_a / store_a and their staging
+// registers leave the loop.  The (group, frame, tile) items are cut into one contiguous run per workgroup (runs of one XCD are
+// neighbours); the micro-stage sequence runs on across items as one software pipeline -- the first slab of the next item is in
+// flight under the last stage of the current one -- and every global load of the loop is unconditional (after the last stage it
+// re-reads a slab of the same tile and the value is dropped).  NWV = waves per workgroup: 4 (two workgroups per CU) or, where
+// two do not fit the CU's 160 KB, 8 waves on the same 8 x 16 tile (twice the wave rows, RT halved).  Per output element the
+// additions are those of conv_tile3_kernel in the same order: the two forms give the same bits.
+extern __shared__ u32x4 tile3r_lds[];
+
+template <int MODE, int TNT, int NPROD, int KO, int NWV>
+__global__ __launch_bounds__(64 * NWV, 2) void conv_tile3r_kernel(Tile3P p, int ngroups) {
+  using TT = T3<MODE>;
+  constexpr int NT = 64 * NWV;
+  constexpr int WN = TNT == 4 ? 2 : 1, WM = NWV / WN, RT = TH / WM, CT = 2;
+  constexpr int A_SLOTS = TT::PAIRS * TNT * 3 * 64;                    // 16-byte slots of one slab's weights
+  constexpr int NB = (TT::B_UNITS + NT - 1) / NT;
+  constexpr int BPL = MODE == NLT_CONV_K2S1 ? PL : QS2;
+  const int a_group = p.ncc * 2 * TNT * 3 * 64;                        // slots of a group's weights: [cc][pair][ct][term][lane]
+  u32x4* const lds_b = tile3r_lds + a_group;                           // [A of the group][B of micro-stage parity 0 | 1]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kk = lane >> 4, j = lane & 15;
+  const int wn = wave % WN, wm = wave / WN;
+  const int spf = (MODE == NLT_CONV_K2S1 ? 1 : 2) * p.ncc;             // slabs (stages) per frame
+  const int groups = p.kobs / KO;
+  const long in_frame = (long)p.h * p.w;
+  // this workgroup's items: item = g * tiles + (f * tiles_y + ty) * tiles_x + tx, run [it, it_end)
+  const int tiles = p.frames * p.tiles_y * p.tiles_x;
+  const long items = (long)tiles * ngroups;
+  const int rank = xcd_tile3(blockIdx.x, gridDim.x);
+  int it = (int)(rank * items / gridDim.x);
+  const int it_end = (int)((rank + 1) * items / gridDim.x);
+  if (it >= it_end) return;
+
+  int b_lds[NB], b_hf[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int u = tid + NT * i;
+    const int hf = (u >> 3) & 1, tx = (u >> 4) * 8 + (u & 7);
+    b_hf[i] = hf;
+    if (MODE == NLT_CONV_K2S1) {
+      b_st[i] = tx < 153;
+      b_lds[i] = hf * PL + tx;
+    } else {
+      const int y = tx >> 5, xx = tx & 31;
+      b_st[i] = tx < 256;
+      b_lds[i] = hf * QS2 + (xx & 1) * ODD2 + y * 16 + (xx >> 1);
+    }
+  }
+  int ng = 0, nf = 0, nty0 = 0, ntx0 = 0;                               // the item whose slabs are being LOADED
+  auto geom = [&](int item) {
+    ng = item / tiles;
+    int t = item - ng * tiles;
+    ntx0 = (t % p.tiles_x) * TW; t /= p.tiles_x;
+    nty0 = (t % p.tiles_y) * TH;
+    nf = t / p.tiles_y;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int u = tid + NT * i;
+      const int tx = (u >> 4) * 8 + (u & 7);
+      if (MODE == NLT_CONV_K2S1) {
+        const int gy = nty0 + tx / 17, gx = ntx0 + tx % 17;
+        b_ok[i] = b_st[i] && gy < p.h && gx < p.w;
+        b_tex[i] = (long)gy * p.w + gx;
+      } else {
+        const int y = tx >> 5, xx = tx & 31;
+        const int gy = 2 * (nty0 + y), gx = 2 * ntx0 + xx;
+        b_ok[i] = b_st[i] && (nty0 + y) < p.oh && gx < p.w;
+        b_tex[i] = (long)gy * p.w + gx;
+      }
+    }
+  };
+
+  f32x4 rb[NB][2];
+  auto load_b = [&](int s, int frame) {
+    const int cc = MODE == NLT_CONV_K2S1 ? s : (s >> 1);
+    const int a = MODE == NLT_CONV_K2S1 ? 0 : (s & 1);
+    const float* sp = p.src + ((long)(nf * p.kobs + frame) * in_frame + (long)a * p.w) * p.ld + cc * 16;
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      rb[n][0] = b_ok[n] ? v0 : z;
+      rb[n][1] = b_ok[n] ? v1 : z;
+    }
+  };
+  auto store_b = [&](int buf) {
+    u32x4* base = lds_b + buf * TT::B_SLOTS;
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      if (!b_st[n]) continue;
+      unsigned hi[4], mid[4], lo[4];
+      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
+      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
+      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
+      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
+      u32x4* bb = base + b_lds[n];
+      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
+      bb[2 * BPL] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
+      bb[4 * BPL] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
+    }
+  };
+  auto copy_a = [&](int grp) {                                          // the group's whole block, as it lies in `packed`
+    const u32x4* ap = reinterpret_cast<const u32x4*>(p.packed) + (long)grp * a_group;
+    for (int i = tid; i < a_group; i += NT) tile3r_lds[i] = ap[i];
+  };
+
+  f32x4 acc[KO][RT][CT], mean[RT][CT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int io = 0; io < KO; ++io) acc[io][rt][ct] = mean[rt][ct];
+    }
+
+  geom(it);
+  load_b(0, 0);
+  copy_a(ng);
+  store_b(0);
+  __syncthreads();
+  int q = 0;                                                            // micro-stage counter (its parity = B buffer)
+  for (; it < it_end; ++it) {
+    const int g = ng, f = nf, ty0 = nty0, tx0 = ntx0;                   // the item being COMPUTED
+    const bool last_item = it + 1 == it_end;
+    for (int gi = 0; gi < groups; ++gi) {
+      for (int s = 0; s < spf; ++s) {
+#pragma unroll
+        for (int io = 0; io < KO; ++io, ++q) {
+          // next micro-stage: (gi, s, io + 1), else (gi, s + 1, 0), else (gi + 1, 0, 0), else the first of the next item
+          const bool new_slab = io + 1 == KO;
+          int ns = s, ngi = gi;
+          if (new_slab) { if (++ns == spf) { ns = 0; ++ngi; } }
+          const bool item_end = ngi == groups;
+          if (item_end) {
+            ngi = 0;
+            if (!last_item) geom(it + 1);
+          }
+          load_b(ns, ngi * KO + (new_slab ? 0 : io + 1));
+          const u32x4* A = tile3r_lds + s * A_SLOTS;
+          const u32x4* B = lds_b + (q & 1) * TT::B_SLOTS;
+#pragma unroll
+          for (int pl = 0; pl < TT::PAIRS; ++pl) {
+            bf16x8 bt[3][RT], at[3][CT];
+#pragma unroll
+            for (int rt = 0; rt < RT; ++rt) {
+              const int y = wm * RT + rt;
+              const int slot = MODE == NLT_CONV_K2S1 ? (kk & 1) * PL + (y + pl) * 17 + j + (kk >> 1)
+                                                     : (kk & 1) * QS2 + (kk >> 1) * ODD2 + y * 16 + j;
+#pragma unroll
+              for (int t = 0; t < 3; ++t) bt[t][rt] = __builtin_bit_cast(bf16x8, B[t * 2 * BPL + slot]);
+            }
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+              for (int t = 0; t < 3; ++t)
+                at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * TNT + wn * CT + ct) * 3 + t) * 64 + lane]);
+            constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
+#pragma unroll
+            for (int pi = 9 - NPROD; pi < 9; ++pi)
+#pragma unroll
+              for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+                  acc[io][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][rt], acc[io][rt][ct], 0, 0, 0);
+          }
+          if (s == spf - 1 && io == KO - 1) {                           // the group's KO observation frames are complete
+#pragma unroll
+            for (int e = 0; e < KO; ++e) {
+              const int i = gi * KO + e;
+#pragma unroll
+              for (int ct = 0; ct < CT; ++ct) {
+                const int oc = (g * TNT + wn * CT + ct) * 16 + 4 * kk;
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + oc);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                  const int gy = ty0 + wm * RT + rt, gx = tx0 + j;
+                  f32x4 v = acc[e][rt][ct] + bv;
+                  if (p.act) {
+#pragma unroll
+                    for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
+                  }
+                  acc[e][rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                  mean[rt][ct] += v;
+                  if (gy < p.oh && gx < p.ow) {
+                    const long ot = ((long)(f * p.kobs + i) * p.oh + gy) * p.ow + gx;
+                    if (p.out) *reinterpret_cast<f32x4*>(p.out + ot * p.ldo + oc) = v;
+                    if (p.mean_out && i == p.kobs - 1) {
+                      const long mt = ((long)f * p.oh + gy) * p.ow + gx;
+                      *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[rt][ct] * (1.f / (float)p.kobs);
+                    }
+                  }
+                  if (i == p.kobs - 1) mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};     // the next item starts its own mean
+                }
+              }
+            }
+          }
+          if (!(item_end && last_item)) store_b((q + 1) & 1);
+          __syncthreads();
+        }
+      }
+    }
+    if (!last_item && ng != g) {                                        // the run crosses into the next group: its weights
+      copy_a(ng);
+      __syncthreads();
+    }
+  }
+}
+
+constexpr size_t TILE3R_LDS_CU = 160 * 1024;                           // LDS of a CU (gfx950)
+
+int tile3r_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    return v;
+  }();
+  return n;
+}
+
+// dynamic LDS above 64 KB needs the kernel's limit raised: once per device and kernel (`done`: the instantiation's largest size so far)
+int tile3r_allow_lds(const void* kernel, size_t lds, size_t (&done)[8]) {
+  int dev = 0;
+  if (lds <= 64 * 1024) return NLT_OK;
+  if (hipGetDevice(&dev) != hipSuccess) return NLT_ERR_LAUNCH;
+  if (dev >= 0 && dev < 8 && done[dev] >= lds) return NLT_OK;
+  if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return NLT_ERR_LAUNCH;
+  if (dev >= 0 && dev < 8) done[dev] = lds;
+  return NLT_OK;
+}
+
+template <int MODE, int TNT, int NPROD, int KO, int NWV>
+int launch3r_k(const Tile3P& p, size_t lds, int nwg, hipStream_t s) {
+  auto* k = conv_tile3r_kernel<MODE, TNT, NPROD, KO, NWV>;
+  static size_t done[8] = {};
+  if (tile3r_allow_lds(reinterpret_cast<const void*>(k), lds, done) != NLT_OK) return NLT_ERR_LAUNCH;
+  hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(64 * NWV), lds, s, p, p.cout / (16 * TNT));
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+// WAVE-PRIVATE texel staging, the resident form of the stride-1 conv at 32 channels per group: one 8-wave workgroup per CU shares
+// the group's resident weights, and every wave owns an RT x 16 output tile of its own -- it stages its (RT + 1) x 17 haloed texels
+// in an LDS region nobody else touches, so the steady state has NO workgroup barrier (LDS operations of one wave execute in order;
+// wave_sync() only keeps the compiler from reordering them) and the waves of a SIMD drift apart and fill each other's gaps.  A
+// stage reads its RT + 1 row fragments to registers first (tap pair 1 of output row r uses the fragment pair 0 of row r + 1 uses:
+// 15 reads instead of 24), which frees the region: the next slab is split and written between the MFMAs of the issuing wave,
+// where bf16 MFMAs co-execute with VALU work (r05), with one buffer.  Price: (RT + 1) / RT times the texel loads and splits.
+// A workgroup's run of items is cut at group changes (the only barriers: before and after the weights are replaced); inside a
+// segment wave v takes items v, v + 8, ...  Per output element: slabs in order, tap pairs in order, ORDER9 -- conv_tile3_kernel's bits.
+template <int RT, int NPROD>
+__global__ __launch_bounds__(512, 2) void conv_tile3w_kernel(Tile3P p, int ngroups, int tiles_y) {
+  constexpr int TNT = 2, CT = 2, NWV = 8;
+  constexpr int ROWS = RT + 1, UNITS = ROWS * 17 * 2, NB = (UNITS + 63) / 64;
+  constexpr int PLW = (ROWS * 17 + 15) / 16 * 16;                       // slots per (term, half) plane
+  constexpr int A_SLOTS = 2 * TNT * 3 * 64;
+  const int a_group = p.ncc * A_SLOTS;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kk = lane >> 4, j = lane & 15;
+  u32x4* const B = tile3r_lds + a_group + wave * (6 * PLW);
+  const long in_frame = (long)p.h * p.w;
+  const int tiles = p.frames * tiles_y * p.tiles_x;
+  const long items = (long)tiles * ngroups;
+  const int rank = xcd_tile3(blockIdx.x, gridDim.x);
+  const int it0 = (int)(rank * items / gridDim.x), it1 = (int)((rank + 1) * items / gridDim.x);
+
+  int b_lds[NB], b_hf[NB], b_tx[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int u = lane + 64 * i;
+    b_hf[i] = (u >> 3) & 1;
+    b_tx[i] = (u >> 4) * 8 + (u & 7);
+    b_st[i] = b_tx[i] < ROWS * 17;
+    b_lds[i] = b_hf[i] * PLW + b_tx[i];
+  }
+  int nf = 0, nty0 = 0, ntx0 = 0;
+  auto geom = [&](int t) {
+    ntx0 = (t % p.tiles_x) * TW; t /= p.tiles_x;
+    nty0 = (t % tiles_y) * RT;
+    nf = t / tiles_y;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int gy = nty0 + b_tx[i] / 17, gx = ntx0 + b_tx[i] % 17;
+      b_ok[i] = b_st[i] && gy < p.h && gx < p.w;
+      b_tex[i] = (long)gy * p.w + gx;
+    }
+  };
+  f32x4 rb[NB][2];
+  auto load_b = [&](int cc, int frame) {
+    const float* sp = p.src + (long)(nf * p.kobs + frame) * in_frame * p.ld + cc * 16;
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      rb[n][0] = b_ok[n] ? v0 : z;
+      rb[n][1] = b_ok[n] ? v1 : z;
+    }
+  };
+  auto store_b = [&]() {
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      if (!b_st[n]) continue;
+      unsigned hi[4], mid[4], lo[4];
+      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
+      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
+      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
+      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
+      u32x4* bb = B + b_lds[n];
+      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
+      bb[2 * PLW] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
+      bb[4 * PLW] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
+    }
+  };
+  auto wave_sync = [&]() {                                              // LDS written by one lane, read by another of the SAME wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+
+  int seg = it0;
+  while (seg < it1) {                                                   // one segment per output-channel group of the run
+    const int g = seg / tiles;
+    const int seg_end = min(it1, (g + 1) * tiles);
+    {
+      const u32x4* ap = reinterpret_cast<const u32x4*>(p.packed) + (long)g * a_group;
+      for (int i = tid; i < a_group; i += 64 * NWV) tile3r_lds[i] = ap[i];
+    }
+    __syncthreads();
+    int it = seg + wave;
+    if (it < seg_end) {
+      f32x4 acc[RT][CT], mean[RT][CT];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[rt][ct] = mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      geom(it - g * tiles);
+      load_b(0, 0);
+      store_b();
+      wave_sync();
+      for (; it < seg_end; it += NWV) {
+        const int f = nf, ty0 = nty0, tx0 = ntx0;
+        const bool last_item = it + NWV >= seg_end;
+        for (int i = 0; i < p.kobs; ++i) {
+          for (int s = 0; s < p.ncc; ++s) {
+            int ns = s + 1, ni = i;
+            if (ns == p.ncc) { ns = 0; ++ni; }
+            const bool item_end = ni == p.kobs;
+            if (item_end) {
+              ni = 0;
+              if (!last_item) geom(it + NWV - g * tiles);
+            }
+            load_b(ns, ni);
+            bf16x8 bt[3][ROWS];
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r)
+#pragma unroll
+              for (int t = 0; t < 3; ++t)
+                bt[t][r] = __builtin_bit_cast(bf16x8, B[t * 2 * PLW + (kk & 1) * PLW + r * 17 + j + (kk >> 1)]);
+            wave_sync();
+            const u32x4* A = tile3r_lds + s * A_SLOTS;
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl) {
+              bf16x8 at[3][CT];
+#pragma unroll
+              for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                for (int t = 0; t < 3; ++t) at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * TNT + ct) * 3 + t) * 64 + lane]);
+              constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
+#pragma unroll
+              for (int pi = 9 - NPROD; pi < 9; ++pi)
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+                  for (int ct = 0; ct < CT; ++ct)
+                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][rt + pl], acc[rt][ct], 0, 0, 0);
+            }
+            if (!(item_end && last_item)) store_b();
+            wave_sync();
+            if (s == p.ncc - 1) {
+#pragma unroll
+              for (int ct = 0; ct < CT; ++ct) {
+                const int oc = (g * TNT + ct) * 16 + 4 * kk;
+                const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + oc);
+#pragma unroll
+                for (int rt = 0; rt < RT; ++rt) {
+                  const int gy = ty0 + rt, gx = tx0 + j;
+                  f32x4 v = acc[rt][ct] + bv;
+                  if (p.act) {
+#pragma unroll
+                    for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
+                  }
+                  acc[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                  mean[rt][ct] += v;
+                  if (gy < p.oh && gx < p.ow) {
+                    const long ot = ((long)(f * p.kobs + i) * p.oh + gy) * p.ow + gx;
+                    if (p.out) *reinterpret_cast<f32x4*>(p.out + ot * p.ldo + oc) = v;
+                    if (p.mean_out && i == p.kobs - 1) {
+                      const long mt = ((long)f * p.oh + gy) * p.ow + gx;
+                      *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[rt][ct] * (1.f / (float)p.kobs);
+                    }
+                  }
+                  if (i == p.kobs - 1) mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+    seg = seg_end;
+    if (seg < it1) __syncthreads();                                     // every wave is done with this group's weights
+  }
+}
+
+// LDS = the group's weights + 8 single-buffered wave regions of 6 planes; refused where that exceeds the CU's 160 KB
+template <int RT>
+int launch3w(const Tile3P& p, int nprod, int max_wg, hipStream_t s) {
+  constexpr int PLW = ((RT + 1) * 17 + 15) / 16 * 16;
+  const size_t lds = (size_t)p.cin * 2 * 384 + 8 * 6 * PLW * sizeof(u32x4);
+  if (lds > TILE3R_LDS_CU) return NLT_ERR_UNSUPPORTED;
+  const int cus = tile3r_cus();
+  if (cus <= 0) return NLT_ERR_LAUNCH;
+  const int tiles_y = (p.oh + RT - 1) / RT;
+  const long items = (long)p.frames * tiles_y * p.tiles_x * (p.cout / 32);
+  long nwg = cus;
+  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
+  if (nwg > items) nwg = items;
+  auto* k = nprod == 9 ? conv_tile3w_kernel<RT, 9> : conv_tile3w_kernel<RT, 6>;
+  static size_t done[2][8] = {};
+  if (tile3r_allow_lds(reinterpret_cast<const void*>(k), lds, done[nprod == 9]) != NLT_OK) return NLT_ERR_LAUNCH;
+  hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), lds, s, p, p.cout / 32, tiles_y);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+// resident form (other than wave-private): LDS = the group's weights + the double-buffered texel stage; two 4-wave workgroups per CU where two fit the
+// CU's 160 KB, else one 8-wave workgroup (never fewer than 8 waves per CU); what does not fit at all is refused
 template <int MODE, int TNT, int KO>
-int launch3k(const Tile3P& p, int nprod, hipStream_t s) {
+int launch3r(const Tile3P& p, int nprod, int max_wg, hipStream_t s) {
+  if (nprod != 6 && nprod != 9) return NLT_ERR_UNSUPPORTED;
+  if (MODE == NLT_CONV_K2S1 && TNT == 2) {                              // wave-private staging: 4-row tiles, 2-row where 4 do not fit
+    int st = launch3w<4>(p, nprod, max_wg, s);
+    if (st == NLT_ERR_UNSUPPORTED) st = launch3w<2>(p, nprod, max_wg, s);
+    if (st != NLT_ERR_UNSUPPORTED) return st;
+  }
+  const size_t lds = (size_t)p.cin * TNT * 384 + 2 * T3<MODE>::B_SLOTS * sizeof(u32x4);
+  if (lds > TILE3R_LDS_CU) return NLT_ERR_UNSUPPORTED;
+  const bool wide = 2 * lds > TILE3R_LDS_CU;
+  const int cus = tile3r_cus();
+  if (cus <= 0) return NLT_ERR_LAUNCH;
+  const long items = (long)p.frames * p.tiles_y * p.tiles_x * (p.cout / (16 * TNT));
+  long nwg = (long)cus * (wide ? 1 : 2);
+  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
+  if (nwg > items) nwg = items;
+  if (items >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  if (wide) return nprod == 9 ? launch3r_k<MODE, TNT, 9, KO, 8>(p, lds, (int)nwg, s) : launch3r_k<MODE, TNT, 6, KO, 8>(p, lds, (int)nwg, s);
+  return nprod == 9 ? launch3r_k<MODE, TNT, 9, KO, 4>(p, lds, (int)nwg, s) : launch3r_k<MODE, TNT, 6, KO, 4>(p, lds, (int)nwg, s);
+}
+
+// resident_wg < 0: the streaming kernel; >= 0: the resident form with at most that many workgroups (0 = sized from the device)
+template <int MODE, int TNT, int KO>
+int launch3k(const Tile3P& p, int nprod, hipStream_t s, int resident_wg) {
+  if (resident_wg >= 0) return launch3r<MODE, TNT, KO>(p, nprod, resident_wg, s);
   const long tiles = (long)p.frames * p.tiles_y * p.tiles_x;
   const dim3 grid((unsigned)tiles, (unsigned)(p.cout / (16 * TNT)));
   if (nprod == 9) hipLaunchKernelGGL((conv_tile3_kernel<MODE, TNT, 9, KO>), grid, dim3(256), 0, s, p);
@@ -313,15 +780,16 @@ int launch3k(const Tile3P& p, int nprod, hipStream_t s) {
 // NLT_TILE3_KO: observation frames per pass over the weights (0 = the largest that fits the registers: 4 at 32 channels per
 // workgroup, 2 at 64; 1 = the r03 order) -- A/B switch
 template <int MODE, int TNT>
-int launch3(const Tile3P& p, int nprod, hipStream_t s) {
+int launch3(const Tile3P& p, int nprod, hipStream_t s, int resident_wg) {
   static const int want = [] { const char* e = getenv("NLT_TILE3_KO"); return e ? atoi(e) : 0; }();
   // (stride-1 conv at 64 channels per workgroup: two sets of 4 x 2 accumulators beside the three-term fragments of 4 rows spill)
-  const int cap = want > 0 ? want : (TNT == 2 ? 4 : (MODE == NLT_CONV_K2S1 ? 1 : 2));
+  // (the resident form has no weight stage to share: at 64 channels a second accumulator set only spills there)
+  const int cap = want > 0 ? want : (TNT == 2 ? 4 : (MODE == NLT_CONV_K2S1 || resident_wg >= 0 ? 1 : 2));
   if (nprod >= 6) {
-    if (TNT == 2 && cap >= 4 && p.kobs % 4 == 0) return launch3k<MODE, TNT, (TNT == 2 ? 4 : 1)>(p, nprod, s);
-    if (cap >= 2 && p.kobs % 2 == 0) return launch3k<MODE, TNT, 2>(p, nprod, s);
+    if (TNT == 2 && cap >= 4 && p.kobs % 4 == 0) return launch3k<MODE, TNT, (TNT == 2 ? 4 : 1)>(p, nprod, s, resident_wg);
+    if (cap >= 2 && p.kobs % 2 == 0) return launch3k<MODE, TNT, 2>(p, nprod, s, resident_wg);
   }
-  return launch3k<MODE, TNT, 1>(p, nprod, s);
+  return launch3k<MODE, TNT, 1>(p, nprod, s, resident_wg);
 }
 
 }  // namespace
@@ -343,9 +811,9 @@ extern "C" int nlt_pack_conv_tile3_weights(int mode, const float* w_keras, int c
   return NLT_OK;
 }
 
-extern "C" int nlt_conv_tile3_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
-                                      const unsigned short* packed, const float* bias, int cout, int tn,
-                                      float* out, int ldo, float* mean_out, int ldm, int act, float alpha, void* stream) {
+static int tile3_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                         const unsigned short* packed, const float* bias, int cout, int tn,
+                         float* out, int ldo, float* mean_out, int ldm, int act, float alpha, int resident_wg, void* stream) {
   if (!src || !packed || !bias || (!out && !mean_out) || (nprod != 1 && nprod != 3 && nprod != 6 && nprod != 9)) return NLT_ERR_BAD_ARG;
   if (frames <= 0 || kobs <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return NLT_ERR_BAD_ARG;
   if (nlt_conv_tile3_packed_elems(mode, cin, cout, tn) <= 0) return NLT_ERR_UNSUPPORTED;
@@ -361,6 +829,23 @@ extern "C" int nlt_conv_tile3_forward(int mode, int nprod, const float* src, int
   p.cout = cout; p.ldo = ldo; p.ldm = ldm; p.ncc = cin / 16; p.act = act; p.alpha = alpha;
   p.tiles_y = (p.oh + TH - 1) / TH; p.tiles_x = (p.ow + TW - 1) / TW;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (mode == NLT_CONV_K2S1) return tn == 64 ? launch3<NLT_CONV_K2S1, 4>(p, nprod, s) : launch3<NLT_CONV_K2S1, 2>(p, nprod, s);
-  return tn == 64 ? launch3<NLT_CONV_K2S2, 4>(p, nprod, s) : launch3<NLT_CONV_K2S2, 2>(p, nprod, s);
+  if (mode == NLT_CONV_K2S1)
+    return tn == 64 ? launch3<NLT_CONV_K2S1, 4>(p, nprod, s, resident_wg) : launch3<NLT_CONV_K2S1, 2>(p, nprod, s, resident_wg);
+  return tn == 64 ? launch3<NLT_CONV_K2S2, 4>(p, nprod, s, resident_wg) : launch3<NLT_CONV_K2S2, 2>(p, nprod, s, resident_wg);
+}
+
+extern "C" int nlt_conv_tile3_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                                      const unsigned short* packed, const float* bias, int cout, int tn,
+                                      float* out, int ldo, float* mean_out, int ldm, int act, float alpha, void* stream) {
+  return tile3_forward(mode, nprod, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm, act, alpha,
+                       -1, stream);
+}
+
+extern "C" int nlt_conv_tile3r_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                                       const unsigned short* packed, const float* bias, int cout, int tn,
+                                       float* out, int ldo, float* mean_out, int ldm, int act, float alpha, int max_workgroups,
+                                       void* stream) {
+  if (max_workgroups < 0) return NLT_ERR_BAD_ARG;
+  return tile3_forward(mode, nprod, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm, act, alpha,
+                       max_workgroups, stream);
 }

@@ -116,7 +116,7 @@ class RenderPlan(OverrideMixin):
         self._ran_direct = set()
         self._trial_lds = 0             # autotune: try the LDS-tiled kernel with this many output channels per workgroup
         self._ran_lds = set()
-        self.lds_hints = {}             # label -> tn (32 / 64) [+256: observations unfolded]: launches that go to csrc/conv_tile.hip
+        self.lds_hints = {}             # label -> tn (32 / 64) [+256: observations unfolded, +512: conv_tile3's resident form]: launches that go to csrc/conv_tile.hip
         # Winograd F(2x2, 2x2) kernel for the stride-1 k2 convs (csrc/conv_wino.hip: 9/16 of the matrix-pipe work); 0 = never
         self.use_wino = os.environ.get('NLT_WINO', '1') != '0'
         self._trial_wino = 0            # autotune: try it with this many output channels per workgroup
@@ -309,16 +309,20 @@ class RenderPlan(OverrideMixin):
                 and self._wino(*conv, obs_weights)):
             return
         hint = self._trial_lds or (0 if (self._trial_wino or self._trial_c32) else self.lds_hints.get(label, 0))
-        tn, unfold = hint & 255, bool(hint >> 8)       # +256: observations as separate frames, mean in its own launch
+        tn, unfold = hint & 255, bool((hint >> 8) & 1)  # +256: observations as separate frames, mean in its own launch
+        resident = bool(hint & 512)                     # +512: csrc/conv_tile3.hip's resident form (split weights stay in LDS)
         ok = (tn and obs_weights is None and algo == C.ALGO_AUTO and layer.mode in (C.CONV_K2S2, C.CONV_K2S1)
               and layer.cin == cin and cin % 16 == 0 and layer.n_ch_out % tn == 0)
+        if ok and resident and (self.precision not in ('f32x3', 'f32x3_9') or C.conv_tile3r_plan(layer.mode, cin, tn) is None):
+            ok = self._trial_lds == 0                   # the resident form refuses this launch: a trial leaves it to the others,
+            resident = False                            # a plan takes the streaming kernel
         if ok and unfold and kobs == 1:
             ok = self._trial_lds == 0                   # nothing to unfold here: leave this launch to the other trials
             unfold = False
         if ok and self.precision in ('f32x3', 'f32x3_9'):
             # fp32 operands as three bf16 terms on the bf16 matrix cores (csrc/conv_tile3.hip): 6 or all 9 term products
-            self._enc_launch(C.conv_tile3_forward, layer.packed_tile3(tn), (tn,), self._ran_lds, unfold, *conv,
-                             nprod=9 if self.precision == 'f32x3_9' else 6)
+            self._enc_launch(C.conv_tile3r_forward if resident else C.conv_tile3_forward, layer.packed_tile3(tn), (tn,),
+                             self._ran_lds, unfold, *conv, nprod=9 if self.precision == 'f32x3_9' else 6)
         elif ok:
             self._enc_launch(C.conv_tile_forward, layer.packed_tile(tn), (tn,), self._ran_lds, unfold, *conv)
         else:
@@ -349,6 +353,8 @@ class RenderPlan(OverrideMixin):
             trials.append(('direct', 0))    # only the 4/8-channel full-resolution layers ever preferred it
         if not backward:
             trials += [('lds', 32), ('lds', 64), ('lds', 256 + 32), ('lds', 256 + 64)]
+            if self.precision in ('f32x3', 'f32x3_9'):
+                trials += [('lds', 512 + 32), ('lds', 512 + 64)]    # the three-term split with its weights resident in LDS
         elif self.tile_dgrad:
             trials += [('lds', 32), ('lds', 64)]                  # backward-data launches on the LDS-tiled kernel
         if self.use_c32 and not backward:
