@@ -43,7 +43,7 @@ typedef enum {
   NLT_CONV_K3S1 = 5,   /* Conv2D k3 s1: out (h,w), zero pad 1 / 1; W keras (3,3,Cin,Cout)                     */
   NLT_CONV_K3S2 = 6,   /* Conv2D k3 s2: out (h/2,w/2), h,w even, zero pad 0 / 1; W keras (3,3,Cin,Cout)       */
   NLT_DECONV_K3S1 = 7, /* Conv2DTranspose k3 s1: out (h,w): the full transposed conv less its outer ring      */
-  NLT_DECONV_K3S2 = 8  /* Conv2DTranspose k3 s2: out (2h,2w): the first 2h x 2w of the full transposed conv   */
+  NLT_DECONV_K3S2 = 8  /* Conv2DTranspose k3 s2: out (2h,2w), any h,w: the first 2h x 2w of the full transposed conv */
 } nlt_conv_mode;
 
 typedef enum {
@@ -955,8 +955,10 @@ int nlt_chmix_bf16_forward(const unsigned short* x, long texels, int cin, const 
  *   NLT_CONV_K3S2    y[i,j,o] = b[o] + sum_{a,b,c} x[2i+a, 2j+b, c]   W[a,b,c,o]
  *   NLT_DECONV_K3S1  y[i,j,o] = b[o] + sum_{a,b,c} x[i+1-a, j+1-b, c] W[a,b,o,c]
  *   NLT_DECONV_K3S2  y[m,n,o] = b[o] + sum over the taps with (m-a), (n-b) even of x[(m-a)/2, (n-b)/2, c] W[a,b,o,c]
- * (h, w, cin) are the layer's INPUT dims in all four entry points; a stride-2 mode on an odd h or w is NLT_ERR_UNSUPPORTED
- * (TF would pad; the network's resolutions are multiples of 2^levels).  act != 0 applies LeakyReLU(alpha).
+ * (h, w, cin) are the layer's INPUT dims in all four entry points.  NLT_CONV_K3S2 on an odd h or w is NLT_ERR_UNSUPPORTED
+ * (TF would pad; the network's resolutions are multiples of 2^levels).  The transposed modes take any h, w >= 1: a stride-2
+ * transposed conv of h x w is 2h x 2w whatever h and w are, and backward-data of NLT_DECONV_K3S2 is NLT_CONV_K3S2 on that
+ * 2h x 2w map, so always on an even size.  act != 0 applies LeakyReLU(alpha).
  * algo: NLT_ALGO_MFMA (cin % 4 == 0, cout % 4 == 0, 16-byte aligned x and w_keras: input tile + halo and the live taps'
  * weights staged in LDS, v_mfma_f32_16x16x4_f32), NLT_ALGO_DIRECT (any channel count), NLT_ALGO_AUTO (MFMA when it can).
  * No packed weights: the kernels read the Keras array.

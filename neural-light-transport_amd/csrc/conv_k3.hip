@@ -340,7 +340,6 @@ extern "C" int nlt_conv_k3_forward(int mode, int algo, const float* x, int n, in
   K3P p;
   const int st = k3_fill(p, mode, n, h, w, cin, cout);
   if (st != NLT_OK) return st;
-  if (mode == NLT_DECONV_K3S2 && ((h | w) & 1)) return NLT_ERR_UNSUPPORTED;
   p.x = x; p.wgt = w_keras; p.bias = bias; p.y = y; p.act = act; p.alpha = alpha;
   return k3_forward(p, algo, static_cast<hipStream_t>(stream));
 }
@@ -351,7 +350,6 @@ extern "C" int nlt_conv_k3_backward_data(int mode, int algo, const float* dpre, 
   K3P fwd;
   int st = k3_fill(fwd, mode, n, h, w, cin, cout);                // the layer itself: validates (h, w) and gives dpre's dims
   if (st != NLT_OK) return st;
-  if (mode == NLT_DECONV_K3S2 && ((h | w) & 1)) return NLT_ERR_UNSUPPORTED;
   const int adj = mode == NLT_CONV_K3S1 ? NLT_DECONV_K3S1 : mode == NLT_CONV_K3S2 ? NLT_DECONV_K3S2
                 : mode == NLT_DECONV_K3S1 ? NLT_CONV_K3S1 : NLT_CONV_K3S2;
   K3P p;
@@ -365,7 +363,6 @@ extern "C" int nlt_conv_k3_backward_data(int mode, int algo, const float* dpre, 
 extern "C" long nlt_conv_k3_wgrad_workspace_floats(int mode, int n, int h, int w, int cin, int cout) {
   K3P p;
   if (k3_fill(p, mode, n, h, w, cin, cout) != NLT_OK) return -1;
-  if (mode == NLT_DECONV_K3S2 && ((h | w) & 1)) return -1;
   const K3Slices q = k3_slices(p);
   return (long)q.slices * (9l * cin * cout + cout);
 }
@@ -377,7 +374,6 @@ extern "C" int nlt_conv_k3_backward_weights(int mode, const float* x, int n, int
   K3P p;
   const int st = k3_fill(p, mode, n, h, w, cin, cout);
   if (st != NLT_OK) return st;
-  if (mode == NLT_DECONV_K3S2 && ((h | w) & 1)) return NLT_ERR_UNSUPPORTED;
   const K3Slices q = k3_slices(p);
   const long per = 9l * cin * cout;
   if (workspace_floats < (long)q.slices * (per + cout)) return NLT_ERR_BAD_ARG;

@@ -88,11 +88,12 @@ def _set_alpha(om, pm, alpha):
 
 
 def _oracle_grads(loss, uv, cam, n, dtype, batch, nn, alpha=None, masks=None, depth=256, seed=41, uvh=None, uvw=None, imh=None,
-                  imw=None):
+                  imw=None, **model_kw):
     """(loss, every kernel / bias gradient) of one train step of a fresh OracleModel(depth, seed) in `dtype`; masks: the
     activation branches to take (OracleModel.act_masks, e.g. `hip_activation_masks`).  uv / cam: the square shorthand for
-    uvh x uvw / imh x imw."""
-    om = O.OracleModel(depth=depth, uvh=uvh or uv, uvw=uvw or uv, imh=imh or cam, imw=imw or cam, loss=loss, seed=seed, dtype=dtype)
+    uvh x uvw / imh x imw; model_kw: further OracleModel keywords (kernel = 3, pool, ...)."""
+    om = O.OracleModel(depth=depth, uvh=uvh or uv, uvw=uvw or uv, imh=imh or cam, imw=imw or cam, loss=loss, seed=seed, dtype=dtype,
+                       **model_kw)
     if alpha is not None:
         om.alpha = alpha
     om.act_masks = masks

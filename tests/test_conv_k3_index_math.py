@@ -215,10 +215,10 @@ def emulate_wgrad(mode, x, g, cout, dw0):
     return dw.reshape(dw0.shape)
 
 
-def _case(mode, h, w, cin, cout, seed):
+def _case(mode, h, w, cin, cout, seed, n=1):
     rng = np.random.default_rng(seed)
     tr = mode in (DECONV_S1, DECONV_S2)
-    x = rng.standard_normal((1, h, w, cin)).astype(np.float32)
+    x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
     wk = rng.standard_normal((3, 3, cout, cin) if tr else (3, 3, cin, cout)).astype(np.float32)
     b = rng.standard_normal(cout).astype(np.float32)
     stride = 2 if mode in (CONV_S2, DECONV_S2) else 1
@@ -229,7 +229,14 @@ def _case(mode, h, w, cin, cout, seed):
 SHAPES = [(6, 10), (5, 7), (2, 2), (34, 18)]
 CHANNELS = [(4, 4), (16, 32), (80, 8), (128, 16)]
 CASES = [(m, h, w, ci, co) for m in (CONV_S1, CONV_S2, DECONV_S1, DECONV_S2) for (h, w) in SHAPES for (ci, co) in CHANNELS
-         if not (m in (CONV_S2, DECONV_S2) and (h, w) == (5, 7))]
+         if not (m == CONV_S2 and (h, w) == (5, 7))]                 # (only the stride-2 CONV needs an even input)
+# Shapes the device suite (tests/test_gpu_conv_k3.py) holds to float64: NB = 2 with 24 of 32 outputs live and a ragged third K
+# slice, NB = 4 with a fully masked fourth block, a second ragged blockIdx.y; grids one texel wide or high; the stride-2
+# transposed conv on odd inputs.  (h, w) is the GRID the case is about: CONV_S2 runs it on the 2h x 2w input.
+WIDE = [(9, 17, 40, 24), (9, 17, 32, 48), (9, 17, 20, 72)]
+THIN = [(1, 1, 8, 16), (1, 9, 20, 8), (9, 1, 8, 24), (2, 1, 16, 16)]
+CASES += [(m, (2 * h if m == CONV_S2 else h), (2 * w if m == CONV_S2 else w), ci, co)
+          for m in (CONV_S1, CONV_S2, DECONV_S1, DECONV_S2) for (h, w, ci, co) in WIDE + THIN]
 
 
 @pytest.mark.parametrize('mode,h,w,cin,cout', CASES)
@@ -247,18 +254,38 @@ def test_forward_kernel_wide_output_tile_and_channel_tail():
         assert np.abs(emulate_forward(mode, x, wk, b, 72) - ref).max() <= 2e-5 * np.abs(ref).max()
 
 
-@pytest.mark.parametrize('mode', [CONV_S1, CONV_S2, DECONV_S1, DECONV_S2])
-@pytest.mark.parametrize('h,w,cin,cout', [(6, 10, 5, 3), (2, 2, 16, 32), (6, 10, 20, 72), (18, 10, 4, 4)])
-def test_weight_gradient_index_math(mode, h, w, cin, cout):
+@pytest.mark.parametrize('mode', [CONV_S1, DECONV_S2])
+def test_forward_kernel_frame_and_class_decode_with_three_frames(mode):
+    """blockIdx.x -> (frame, parity class, tile) with more frames than classes and an odd tile count (5 x 9: 1 x 2 tiles)."""
+    x, wk, b, stride, tr, ref = _case(mode, 5, 9, 8, 16, mode, n=3)
+    assert np.abs(emulate_forward(mode, x, wk, b, 16) - ref).max() <= 2e-5 * np.abs(ref).max()
+
+
+def _wgrad_case(mode, h, w, cin, cout, n):
     import torch
     rng = np.random.default_rng(mode + h)
     tr, stride = mode in (DECONV_S1, DECONV_S2), 2 if mode in (CONV_S2, DECONV_S2) else 1
-    x = rng.standard_normal((2, h, w, cin)).astype(np.float32)
+    x = rng.standard_normal((n, h, w, cin)).astype(np.float32)
     oh, ow = (h * stride, w * stride) if tr else (h // stride, w // stride)
-    g = rng.standard_normal((2, oh, ow, cout)).astype(np.float32)
+    g = rng.standard_normal((n, oh, ow, cout)).astype(np.float32)
     dw0 = rng.standard_normal((3, 3, cout, cin) if tr else (3, 3, cin, cout)).astype(np.float32)
     got = emulate_wgrad(mode, x, g, cout, dw0)
     wz = torch.zeros(dw0.shape, dtype=torch.float64, requires_grad=True)
     y = R.layer_f64(torch.from_numpy(x).double(), wz, None, stride, tr)
     (ref,) = torch.autograd.grad(y, wz, torch.from_numpy(g).double())
     assert np.abs(got - dw0 - ref.numpy()).max() <= 2e-5 * np.abs(ref.numpy()).max()
+
+
+@pytest.mark.parametrize('mode', [CONV_S1, CONV_S2, DECONV_S1, DECONV_S2])
+@pytest.mark.parametrize('h,w,cin,cout', [(6, 10, 5, 3), (2, 2, 16, 32), (6, 10, 20, 72), (18, 10, 4, 4)])
+def test_weight_gradient_index_math(mode, h, w, cin, cout):
+    _wgrad_case(mode, h, w, cin, cout, 2)
+
+
+@pytest.mark.parametrize('mode', [CONV_S1, CONV_S2, DECONV_S1, DECONV_S2])
+@pytest.mark.parametrize('h,w,cin,cout,n', [(9, 17, 40, 24, 3), (9, 17, 32, 48, 2), (9, 17, 20, 72, 2), (1, 1, 8, 16, 2),
+                                            (1, 9, 20, 8, 5), (9, 1, 8, 24, 2), (2, 1, 16, 16, 2), (5, 7, 4, 4, 2)])
+def test_weight_gradient_index_math_wide_thin_and_odd(mode, h, w, cin, cout, n):
+    """The shapes tests/test_gpu_conv_k3.py runs on the device.  (h, w) is the row grid: the stride-2 conv gets the 2h x 2w
+    input that has it.  n = 3 at 9 x 17: 459 rows, a last slice whose length is no multiple of 4."""
+    _wgrad_case(mode, *((2 * h, 2 * w) if mode == CONV_S2 else (h, w)), cin, cout, n)

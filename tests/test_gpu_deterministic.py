@@ -227,6 +227,7 @@ CASES = {
     'barron_cam_ne_im': dict(loss='barron', uvh=128, uvw=64, imh=64, imw=32, cam=(36, 52), k=1),
     'depth1024_small_uv': dict(loss='l2', depth=1024, uvh=256, uvw=256, imh=64, imw=64, cam=(64, 64), k=1),
     'layer_by_layer_pool_upconv': dict(loss='l2', depth=32, uvh=128, uvw=64, imh=64, imw=32, cam=(48, 40), k=2, pool='avg'),
+    'layer_by_layer_kernel3': dict(loss='l2', depth=32, uvh=128, uvw=64, imh=64, imw=32, cam=(48, 40), k=2, kernel=3),
     'layer_by_layer_norm': dict(loss='barron', depth=32, uvh=64, uvw=128, imh=32, imw=64, cam=(32, 64), k=1, norm='layer'),
     'unfused_train_plan': dict(loss='l2', uvh=64, uvw=128, imh=32, imw=64, cam=(40, 56), k=2, fused=False),
 }
