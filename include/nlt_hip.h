@@ -15,6 +15,22 @@
  *     the default stream), re-entrant per stream, keeps no global state and never
  *     throws: it returns NLT_OK or a negative nlt_status;
  *   - sizes are ints; tensors hold < 2^31 elements.
+ *
+ * Memory contract
+ *   - an entry point reads and writes only the elements its arguments describe: n * h * w texels of `c` channels `ld` floats
+ *     apart (the ld - c floats between two channel slices belong to someone else and are neither read into a result nor
+ *     written), packed weights of exactly the queried length, `workspace_floats` floats of scratch.  Nothing before the first
+ *     or past the last such element is stored to, and nothing read from there may reach a result; read-only operands come
+ *     back bit for bit;
+ *   - the contents of scratch are undefined on entry (a kernel writes every slot before it reads it) and of no meaning on exit.
+ *     The one exception is split-K: the ticket counters at the head of its scratch (the first 16384 words) are zero on entry --
+ *     the caller zeroes them once, when it allocates -- and every launch leaves them zero; the partial tiles behind them are
+ *     plain scratch;
+ *   - a `*_workspace_floats` / `*_workspace_bytes` / `*_packed_*` query covers everything its kernel touches; where an entry
+ *     point takes the capacity, one float less is NLT_ERR_BAD_ARG and nothing is launched.
+ *   tests/test_gpu_guard_*.py hold every entry point of the render path and the train step to this, with 256 KiB guard bands
+ *   around each buffer, filled pad columns and scratch of exactly the queried size (tests/guard_util.py).  What that does not
+ *   see: a read outside a buffer whose value is discarded, and any access beyond the bands.
  */
 #ifndef NLT_HIP_H_
 #define NLT_HIP_H_

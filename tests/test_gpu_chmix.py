@@ -18,7 +18,8 @@ def ulp_bf16(ref):
 
 
 @pytest.mark.parametrize('cin,cout,shape,act', [(64, 64, (1, 33, 47), True), (32, 32, (2, 16, 16), True), (128, 128, (1, 8, 24), False),
-                                                 (64, 32, (1, 5, 3), True), (32, 128, (1, 1, 1), True), (64, 64, (2, 256, 256), True)])
+                                                 (64, 32, (1, 5, 3), True), (32, 128, (1, 1, 1), True), (64, 64, (2, 256, 256), True),
+                                                 (32, 32, (3, 17, 19), True)])
 def test_chmix_bf16_vs_oracle(cin, cout, shape, act):
     g = torch.Generator().manual_seed(cin + cout + shape[1])
     x = (torch.randn(shape + (cin,), generator=g) * 1.5).to(torch.bfloat16)

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
                                            (8, 16, 32, 2, 32, 48), (16, 32, 64, 1, 24, 40), (8, 16, 32, 1, 9, 17), (16, 32, 64, 2, 8, 16),
                                            (8, 16, 32, 1, 21, 13), (16, 32, 64, 1, 11, 7), (8, 16, 32, 1, 256, 256), (16, 32, 64, 2, 128, 128),
                                            (16, 32, 64, 1, 1, 1), (8, 16, 32, 1, 3, 35), (16, 32, 128, 1, 1, 1), (8, 16, 64, 1, 3, 35), (16, 32, 128, 2, 128, 128),
-                                           (8, 16, 64, 1, 21, 13), (16, 32, 128, 1, 11, 7)])
+                                           (8, 16, 64, 1, 21, 13), (16, 32, 128, 1, 11, 7), (8, 16, 64, 2, 3, 5), (16, 32, 128, 2, 3, 5)])
 def test_dec_block_matches_the_two_transposed_convs(c, cx, cs, n, h, w):
     rng = np.random.default_rng(c * 100 + h)
     x = torch.from_numpy(rng.standard_normal((n, h, w, cx), dtype=np.float32))

@@ -33,7 +33,7 @@ def _outs(n, k, h, w):
 
 
 @pytest.mark.parametrize('n,k,h,w', [(2, 1, 64, 96), (1, 2, 40, 72), (2, 4, 64, 64), (1, 3, 32, 32), (1, 4, 1024, 1024), (1, 4, 36, 100),
-                                     (1, 6, 64, 64), (3, 1, 8, 8), (1, 2, 4, 4)])
+                                     (1, 6, 64, 64), (3, 1, 8, 8), (1, 2, 4, 4), (1, 1, 8, 8), (2, 3, 24, 40)])
 def test_front4_float_matches_front2(n, k, h, w):
     """csrc/front4.hip (one wave per 4 x 16 strip, no workgroup barrier) against front_kernel<true>; k > 4 (which
     front_kernel<true> does not take) against the layer-by-layer plan instead."""
@@ -67,7 +67,8 @@ def test_front4_float_matches_front2(n, k, h, w):
         assert float((a - b).abs().max()) <= 2e-6 * float(a.abs().max())          # ... and no single texel is off by more than a few ulps
 
 
-@pytest.mark.parametrize('n,k,h,w', [(2, 1, 64, 96), (3, 4, 64, 64), (1, 2, 40, 72), (2, 4, 512, 512), (1, 7, 32, 64)])
+@pytest.mark.parametrize('n,k,h,w', [(2, 1, 64, 96), (3, 4, 64, 64), (1, 2, 40, 72), (2, 4, 512, 512), (1, 7, 32, 64),
+                                     (1, 1, 8, 8), (2, 3, 24, 40)])
 def test_front4_u8_store_matches_float_on_assembled_batch(n, k, h, w):
     """r05: the uint8 variant feeds stage 1 the byte values and carries 1 / 255 in its weights (fl(W / 255) . u instead of
     W . fl(u / 255)): <= 5e-7 rel-L2 from the float kernel on nlt_assemble_batch's output (measured 1-3e-7), no texel off by more
@@ -91,7 +92,8 @@ def test_front4_u8_store_matches_float_on_assembled_batch(n, k, h, w):
         assert float((a - c).abs().max()) <= 3e-6 * float(a.abs().max()), name
 
 
-@pytest.mark.parametrize('n,k,h,w', [(2, 1, 64, 96), (1, 2, 40, 72), (1, 4, 64, 64), (1, 1, 1024, 1024), (1, 3, 36, 100)])
+@pytest.mark.parametrize('n,k,h,w', [(2, 1, 64, 96), (1, 2, 40, 72), (1, 4, 64, 64), (1, 1, 1024, 1024), (1, 3, 36, 100),
+                                     (1, 1, 8, 8), (2, 3, 24, 40)])
 def test_front4_train_keeps_the_same_maps_as_the_first_generation_train_kernel(n, k, h, w):
     """nlt_front4_forward_train: fm1 / skip3 / qtmp2 / otmp2 bit-identical to nlt_front4_forward, and the three maps kept for
     the backward pass (obs1, qtmp1, otmp1) equal to what nlt_front_forward_train keeps up to the bias re-association (same

@@ -26,7 +26,8 @@ def _weights(om):
 
 
 @pytest.mark.parametrize('n,h,w,k,add_base', [(1, 64, 64, 2, True), (2, 40, 56, 3, False), (1, 16, 32, 1, True),
-                                              (1, 2, 2, 1, True), (2, 128, 256, 4, True), (1, 36, 44, 5, True)])
+                                              (1, 2, 2, 1, True), (2, 128, 256, 4, True), (1, 36, 44, 5, True),
+                                              (1, 8, 8, 1, True), (2, 24, 40, 3, False), (1, 6, 10, 1, True)])
 def test_front_and_back_kernels_vs_oracle_layers(n, h, w, k, add_base):
     om = O.OracleModel(depth=256, uvh=64, uvw=64, imh=32, imw=32, seed=n + h + k)
     rng = np.random.default_rng(h * 7 + w)

@@ -27,7 +27,8 @@ def _agg_from_oracle(om, batches):
     return [torch.cat([f[l] for f in feats], 0).mean(0, keepdim=True) for l in range(len(feats[0]))]
 
 
-@pytest.mark.parametrize('hw,n,add_base', [((64, 64), 2, True), ((72, 40), 1, True), ((128, 96), 3, False), ((36, 132), 2, True)])
+@pytest.mark.parametrize('hw,n,add_base', [((64, 64), 2, True), ((72, 40), 1, True), ((128, 96), 3, False), ((36, 132), 2, True),
+                                           ((8, 8), 1, True), ((24, 40), 2, True)])
 def test_front_ovr_kernel_against_the_layerwise_arithmetic(hw, n, add_base):
     """nlt_front_ovr_forward alone (incl. sizes whose strips cross the right / bottom border) against float64 torch."""
     h, w = hw
@@ -96,7 +97,7 @@ def test_conv_forward_map_equals_conv_plus_map(mode, c0, c1, cout, hw, frames):
         assert rel_l2(out.cpu(), want.cpu()) <= 1e-6, (ks, hint)
 
 
-@pytest.mark.parametrize('c,hw,n', [(8, (16, 32), 2), (8, (20, 24), 1), (16, (8, 16), 2), (16, (12, 40), 3)])
+@pytest.mark.parametrize('c,hw,n', [(8, (16, 32), 2), (8, (20, 24), 1), (16, (8, 16), 2), (16, (12, 40), 3), (8, (3, 5), 2), (16, (3, 5), 2)])
 def test_dec_block_forward_map_equals_the_interleaved_block(c, hw, n):
     """nlt_dec_block_forward_map([x | query half], map) == nlt_dec_block_forward([x | query | given]) when the map is what the given
     half contributes: conv over the given rows of the first kernel + its bias (both on the GPU; <= 2e-6: a re-association)."""
@@ -117,7 +118,7 @@ def test_dec_block_forward_map_equals_the_interleaved_block(c, hw, n):
     assert rel_l2(out.cpu(), ref.cpu()) <= 2e-6
 
 
-@pytest.mark.parametrize('hw,n', [((16, 32), 2), ((20, 24), 1), ((64, 48), 3)])
+@pytest.mark.parametrize('hw,n', [((16, 32), 2), ((20, 24), 1), ((64, 48), 3), ((3, 5), 1), ((12, 20), 2)])
 def test_back_forward_map_equals_the_interleaved_kernel(hw, n):
     h2, w2 = hw
     g = torch.Generator().manual_seed(h2 * 7 + w2)
@@ -227,7 +228,7 @@ def test_nlt_test_infer_end_to_end_with_lanes_and_new_feat_agg():
     assert rel_l2(out3[0]['pred'].cpu(), gen3[0]['pred'].cpu()) <= 1e-5
 
 
-@pytest.mark.parametrize('hw,n', [((64, 64), 3), ((72, 40), 2), ((36, 136), 2), ((256, 256), 2)])
+@pytest.mark.parametrize('hw,n', [((64, 64), 3), ((72, 40), 2), ((36, 136), 2), ((256, 256), 2), ((8, 8), 1), ((24, 40), 2)])
 def test_front_ovr_u8_reads_the_capture_store_like_the_float_kernel_reads_the_assembled_batch(hw, n):
     """nlt_front_ovr_forward_u8 (frame ids of the uint8 stores, 1 / 255 in registers) against nlt_front_ovr_forward on the float
     buffers `_load_data` would assemble (nlt/datasets/nlt.py:131-136): <= 1e-6 rel-L2 (fl(W / 255) . u vs W . fl(u / 255))."""

@@ -22,7 +22,7 @@ def _rand_weights(rng):
 ORDER = ('wq0', 'bq0', 'wo0', 'bo0', 'wqa', 'bqa', 'wqb', 'bqb', 'woa', 'boa', 'wob', 'bob', 'wh', 'bh')
 
 
-@pytest.mark.parametrize('n,h,w,k', [(1, 16, 16, 1), (2, 24, 40, 3), (1, 64, 128, 4), (1, 8, 8, 6)])
+@pytest.mark.parametrize('n,h,w,k', [(1, 16, 16, 1), (2, 24, 40, 3), (1, 64, 128, 4), (1, 8, 8, 6), (1, 8, 8, 1)])
 def test_front_forward_train_keeps_the_stride2_outputs(n, h, w, k):
     rng = np.random.default_rng(h + w + k)
     U = lambda *s: torch.from_numpy(rng.random(s, dtype=np.float32))
