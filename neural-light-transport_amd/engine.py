@@ -61,12 +61,34 @@ def _gemm(mode, n, h, w, cin, cout):
     return rows, ncols, 2 * rows * taps * cin * ncols
 
 
+# The kernel families a plan-time trial can give a launch label to: kind -> the dict attribute(s) of the plan its hint is stored
+# in (split-K's hint is the pair (wave tile, K slices)).  A new family is a row here and its launch branch.
+CHOICE_DICTS = {'tile': ('tile_hints',), 'direct': ('algo_hints',), 'lds': ('lds_hints',), 'splitk': ('tile_hints', 'splitk_hints'),
+                'wino': ('wino_hints',), 'c32': ('c32_hints',)}
+HINT_DICTS = tuple(dict.fromkeys(a for attrs in CHOICE_DICTS.values() for a in attrs))
+EXCLUSIVE = ('lds', 'wino', 'c32')      # one encoder launch goes to at most one of these: the first that won the label keeps it
+
+
+def hint_word(hint):
+    """(tn, unfold, resident) of an `lds_hints` / `wino_hints` value: the output channels per workgroup (32 / 64) in the low byte;
+    +256: the observations run as separate frames and their mean in a launch of its own; +512: csrc/conv_tile3.hip's resident
+    form, its split weights kept in LDS (lds only)."""
+    return hint & 255, bool(hint & 256), bool(hint & 512)
+
+
 class RenderPlan(OverrideMixin):
     def __init__(self, net_query, net_obs, use_obs=True):
         self.timer = None               # set to an OpTimer (or a set of labels via timer.only) to time launches
         self.q, self.o, self.use_obs = net_query, net_obs, use_obs
-        self.tile_hints = {}            # label -> 16*RT+CT wave tile ('*' = every launch)
-        self.algo_hints = {}            # label -> C.ALGO_DIRECT for the few tiny-channel layers where it wins
+        # the stored plan-time choices, label -> hint (CHOICE_DICTS says which kind lives where; `set_choice` writes, `_hint` reads):
+        self.tile_hints = {}            # 16*RT+CT wave tile of a register-tiled launch ('*' = every launch; 'bf.' + label: csrc/conv_bf16.hip's)
+        self.algo_hints = {}            # C.ALGO_DIRECT for the few tiny-channel layers where the direct kernel wins
+        self.lds_hints = {}             # a `hint_word`: the launch goes to csrc/conv_tile.hip (f32x3: conv_tile3.hip)
+        self.splitk_hints = {}          # K slices (split-K, csrc/conv_mfma.hip; < 0: its two-launch form) for launches with few GEMM rows
+        self.wino_hints = {}            # a `hint_word`: the launch goes to csrc/conv_wino.hip
+        self.c32_hints = {}             # 1 = observations folded (mean in registers), 2 = unfolded: csrc/conv_c32.hip
+        self._trial = None              # the running plan-time trial (kind, hint): hides the stored choices, every launch that can takes its hint
+        self._ran = set()               # (label, kind) of the launches a choice or the trial sent to that kind (`ran`); cleared per trial
         self.autotune = os.environ.get('NLT_AUTOTUNE', '1') != '0'
         self.fuse_ends = os.environ.get('NLT_FUSED', '1') != '0'   # inference: csrc/fused.hip for layers 0-1 and the last block + head
         self._front_blob = None
@@ -112,25 +134,11 @@ class RenderPlan(OverrideMixin):
         self.grad_mid_level = 0         # encoder level that closes range 1 (0: no such range); set by Model._flatten
         self.generation = 0             # bumped by every forward: the activations in the plan's buffers belong to that pass
         self.tape_replays = 0
-        self._trial_direct = False
-        self._ran_direct = set()
-        self._trial_lds = 0             # autotune: try the LDS-tiled kernel with this many output channels per workgroup
-        self._ran_lds = set()
-        self.lds_hints = {}             # label -> tn (32 / 64) [+256: observations unfolded, +512: conv_tile3's resident form]: launches that go to csrc/conv_tile.hip
         # Winograd F(2x2, 2x2) kernel for the stride-1 k2 convs (csrc/conv_wino.hip: 9/16 of the matrix-pipe work); 0 = never
         self.use_wino = os.environ.get('NLT_WINO', '1') != '0'
-        self._trial_wino = 0            # autotune: try it with this many output channels per workgroup
-        self._ran_wino = set()
-        self.wino_hints = {}            # label -> tn (32 / 64) [+256: observations unfolded]: launches that go to csrc/conv_wino.hip
         # narrow stride-1 convs (cin 16 | 32 -> 32) with LDS-resident weights, a frame per stage (csrc/conv_c32.hip)
         self.use_c32 = os.environ.get('NLT_C32', '1') != '0'
-        self._trial_c32 = 0             # autotune: 1 = observations folded (mean in registers), 2 = unfolded
-        self._ran_c32 = set()
-        self.c32_hints = {}             # label -> 1 | 2
         self.alias_obs = os.environ.get('NLT_ALIAS_OBS', '1') != '0'   # k = 1 inference: observation features live in fm[l]'s second half
-        self._trial_splitk = 0          # autotune: K slices to try on the small deep launches
-        self._ran_splitk = set()
-        self.splitk_hints = {}          # label -> K slices (split-K, csrc/conv_mfma.hip; < 0: its two-launch form) for launches with few GEMM rows
         is_c = net_query.is_contracting
         self.n_down = sum(is_c) - 1                      # contracting Sequential blocks
         self.n_up = len(is_c) - sum(is_c) - 1            # expanding Sequential blocks
@@ -191,18 +199,50 @@ class RenderPlan(OverrideMixin):
         else:
             fn(*args, **kw)
 
-    def _tile_splitk(self, label, rows, ncols, star, trial):
-        """Wave tile and split-K slices of a register-tiled launch: the plan's choice for the label, else what the running
-        plan-time trial asks of every launch (star: its tile_hints['*']; trial: its slices, where the waves are few)."""
-        tile_hint = self.tile_hints.get(label, self.tile_hints.get('*', 0) if star else 0)
+    # ------------------------------------------------------------------ plan-time choices
+    def _trying(self, kind):
+        return self._trial is not None and self._trial[0] == kind
+
+    def _hint(self, kind, label):
+        """The hint of this kind for this launch: the running trial's if it is of that kind, 0 while a trial of another kind
+        runs, else the stored choice.  (So a result that is not 0 is the trial's exactly when `_trial is not None`.)"""
+        if self._trial is not None:
+            return self._trial[1] if self._trial[0] == kind else 0
+        return getattr(self, CHOICE_DICTS[kind][0]).get(label, 0)
+
+    def ran(self, kind):
+        """The labels whose launches went to this kind since the last trial began (outside trials: ever)."""
+        return {label for label, k in self._ran if k == kind}
+
+    def set_choice(self, label, kind, hint):
+        """Stores a choice unless one stands in its way: the first winner keeps a label; lds / wino / c32 exclude each other."""
+        own = [getattr(self, a) for a in CHOICE_DICTS[kind]]
+        rivals = [getattr(self, CHOICE_DICTS[k][0]) for k in EXCLUSIVE] if kind in EXCLUSIVE else []
+        if any(label in d for d in own + rivals):
+            return
+        values = (C.ALGO_DIRECT,) if kind == 'direct' else hint if kind == 'splitk' else (hint,)
+        for d, v in zip(own, values):
+            d[label] = v
+
+    def clear_choices(self):
+        for a in HINT_DICTS:
+            setattr(self, a, {})
+
+    def _tile_splitk(self, label, rows, ncols, star, ok=True):
+        """Wave tile and split-K slices of a register-tiled launch: the plan's choice for the label (star: else its
+        tile_hints['*']), or what the running plan-time trial asks of every launch (its slices where ok and the waves are few)."""
+        kind, hint = self._trial or (None, 0)
+        if kind is None:
+            tile_hint, ks = self.tile_hints.get(label, self.tile_hints.get('*', 0) if star else 0), self.splitk_hints.get(label, 1)
+        else:
+            tile_hint, ks = (hint if kind == 'tile' else hint[0] if kind == 'splitk' else 0), 1
         if tile_hint and ((ncols + 15) // 16) % (tile_hint & 15):
             tile_hint = 0                # CT must divide the number of 16-column tiles
-        ks = self.splitk_hints.get(label, 1)
-        if trial:
+        if kind == 'splitk' and ok:
             rt, ct = (tile_hint >> 4, tile_hint & 15) if tile_hint else (1, 1)
             waves = -(-rows // (16 * rt)) * (-(-ncols // 16) // ct)
             npad = -(-ncols // 16) * 16
-            ks = self._trial_splitk if (waves < 4096 and rows * npad * abs(self._trial_splitk) <= (1 << 24)) else 1
+            ks = hint[1] if (waves < 4096 and rows * npad * abs(hint[1]) <= (1 << 24)) else 1
         return tile_hint, ks
 
     def _conv(self, label, layer, act, src0, c0, ld0, src1, c1, ld1, n, h, w, out, ldo, algo=C.ALGO_AUTO, bmap=None):
@@ -210,9 +250,9 @@ class RenderPlan(OverrideMixin):
         layer.build(c0 + c1, src0.device)
         assert layer.cin == c0 + c1, (layer.cin, c0, c1)
         small = (c0 + c1) * layer.n_ch_out <= 1024
-        if self.algo_hints.get(label) == C.ALGO_DIRECT or (self._trial_direct and small):
+        if self._hint('direct', label) == C.ALGO_DIRECT or (self._trying('direct') and small):
             algo = C.ALGO_DIRECT
-            self._ran_direct.add(label)
+            self._ran.add((label, 'direct'))
         ok = c0 % 4 == 0 and c1 % 4 == 0 and layer.n_ch_out % 4 == 0 and algo != C.ALGO_DIRECT
         oh, ow = layer.out_hw(h, w)
         # SURVEY 8d accounting: every input element read once, every output element written once
@@ -220,7 +260,7 @@ class RenderPlan(OverrideMixin):
         rows, ncols, flops = _gemm(layer.mode, n, h, w, c0 + c1, layer.n_ch_out)
         if c1 == 0 and ok and algo == C.ALGO_AUTO and self._wino(label, layer, act, src0, c0, ld0, n, 1, h, w, out, ldo):
             return
-        tile_hint, ks = self._tile_splitk(label, rows, ncols, True, self._trial_splitk and ok)
+        tile_hint, ks = self._tile_splitk(label, rows, ncols, True, ok)
         srcs = (src0, c0, ld0, src1, c1, ld1, n, h, w)
         dst = (layer.bias.detach(), layer.n_ch_out, out, ldo)
         kw = dict(_act_kw(act), flops=flops)
@@ -228,11 +268,11 @@ class RenderPlan(OverrideMixin):
             if not ok:
                 raise C.NLTError("a bias-map conv needs channel counts that are multiples of 4 (%s)" % label)
             if abs(ks) > 1:
-                self._ran_splitk.add(label)
+                self._ran.add((label, 'splitk'))
             self._launch(label, nbytes, C.conv_forward_map, layer.mode, ks or 1, *srcs, layer.packed(c0, c1), *dst, bmap,
                          tile_hint=tile_hint, w_keras=layer.kernel.detach(), **kw)
         elif abs(ks) > 1 and ok:
-            self._ran_splitk.add(label)
+            self._ran.add((label, 'splitk'))
             self._launch(label, nbytes, C.conv_forward_splitk, layer.mode, ks, *srcs, layer.packed(c0, c1), *dst,
                          tile_hint=tile_hint, **kw)
         else:
@@ -245,17 +285,17 @@ class RenderPlan(OverrideMixin):
         self._launch(label.replace('.s1', '.mean'), 4 * frames * hw * c * (kobs + 1), C.obs_mean_forward,
                      obs, obs_weights, frames, kobs, hw, c, mean_out, ldm)
 
-    def _enc_launch(self, fn, packed, extra, ran, unfold, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo,
+    def _enc_launch(self, fn, packed, extra, kind, unfold, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo,
                     mean_out, ldm, **kw):
         """The launch of `_conv_enc` on a kernel family that can fold the observation mean in (fn: its entry point, packed: its
-        fragments, extra: its own positional arguments, ran: its `_ran_*` set); unfold: observations as frames, the mean apart."""
+        fragments, extra: its own positional arguments, kind: its row of CHOICE_DICTS); unfold: observations as frames, the mean apart."""
         oh, ow = layer.out_hw(h, w)
         nf, c = frames * kobs, layer.n_ch_out
         fold_mean = mean_out is not None and not unfold
         nbytes = 4 * (nf * h * w * cin + nf * oh * ow * c)
         if fold_mean:
             nbytes += 4 * frames * oh * ow * c * (kobs + 1)       # what the separate mean launch would move
-        ran.add(label)
+        self._ran.add((label, kind))
         self._launch(label, nbytes, fn, layer.mode, src, ld, cin, nf if unfold else frames, 1 if unfold else kobs, h, w, packed,
                      layer.bias.detach(), c, *extra, out, ldo, mean_out if fold_mean else None, ldm, **_act_kw(act), **kw,
                      flops=2 * nf * oh * ow * 4 * cin * c)
@@ -264,19 +304,18 @@ class RenderPlan(OverrideMixin):
 
     def _wino(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, mean_out=None, ldm=0, obs_weights=None):
         """The launch on the Winograd kernel if the plan (or the running trial) gave it to it; False otherwise.
-        The observation mean stays in the kernel's registers; +256 runs the observations as frames and the mean in its own launch."""
-        hint = self._trial_wino or self.wino_hints.get(label, 0)
-        tn, unfold = hint & 255, bool(hint >> 8)
+        The observation mean stays in the kernel's registers unless the hint unfolds the observations (`hint_word`)."""
+        tn, unfold, _ = hint_word(self._hint('wino', label))
         if not (tn and self.use_wino and obs_weights is None and layer.mode in (C.CONV_K2S1, C.DECONV_K2S1) and layer.cin == cin
                 and cin % 8 == 0 and layer.n_ch_out % tn == 0 and ld % 4 == 0 and ldo % 4 == 0):
             return False
         if layer.mode == C.DECONV_K2S1 and (kobs > 1 or mean_out is not None):
             return False
         if kobs == 1 and mean_out is None:
-            if self._trial_wino >> 8:
-                return False                            # nothing to unfold here: leave this launch to the other trials
+            if unfold and self._trial is not None:
+                return False                            # nothing to unfold here: a trial leaves this launch to the other trials
             unfold = False
-        self._enc_launch(C.conv_wino_forward, layer.packed_wino(tn), (tn,), self._ran_wino, unfold, label, layer, act, src, cin, ld,
+        self._enc_launch(C.conv_wino_forward, layer.packed_wino(tn), (tn,), 'wino', unfold, label, layer, act, src, cin, ld,
                          frames, kobs, h, w, out, ldo, mean_out, ldm)
         return True
 
@@ -289,7 +328,7 @@ class RenderPlan(OverrideMixin):
         moved = n * h * w * (c0 * bpe(src0) + (c1 * bpe(src1) if c1 else 0)) + n * oh * ow * layer.n_ch_out * bpe(out)
         self._launch(label, 4 * (n * h * w * (c0 + c1) + n * oh * ow * layer.n_ch_out), C.conv_bf16_forward, layer.mode,
                      src0, c0, ld0, src1, c1, ld1, n, h, w, layer.packed_bf16(c0, c1), layer.bias.detach(), layer.n_ch_out, out, ldo,
-                     **_act_kw(act), tile_hint=self.tile_hints.get('bf.' + label, 0),
+                     **_act_kw(act), tile_hint=0 if self._trial is not None else self.tile_hints.get('bf.' + label, 0),
                      flops=_gemm(layer.mode, n, h, w, c0 + c1, layer.n_ch_out)[2], moved=moved)
 
     def _conv_enc(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, algo, mean_out=None, ldm=0,
@@ -300,31 +339,29 @@ class RenderPlan(OverrideMixin):
         direct kernels."""
         layer.build(cin, src.device)
         conv = (label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, mean_out, ldm)
-        chint = self._trial_c32 or self.c32_hints.get(label, 0)
+        trial = self._trial is not None                 # (a hint that is not 0 is then the trial's)
+        chint = self._hint('c32', label)
         if (chint and self.use_c32 and algo == C.ALGO_AUTO and obs_weights is None and layer.cin == cin and ld % 4 == 0 and ldo % 4 == 0
-                and C.conv_c32_supported(layer.mode, cin, layer.n_ch_out) and not (chint == 2 and kobs == 1 and self._trial_c32)):
-            self._enc_launch(C.conv_c32_forward, layer.packed_tile(32), (), self._ran_c32, chint == 2 and kobs > 1, *conv)
+                and C.conv_c32_supported(layer.mode, cin, layer.n_ch_out) and not (chint == 2 and kobs == 1 and trial)):
+            self._enc_launch(C.conv_c32_forward, layer.packed_tile(32), (), 'c32', chint == 2 and kobs > 1, *conv)
             return
-        if (algo == C.ALGO_AUTO and layer.mode == C.CONV_K2S1 and (self._trial_wino or label in self.wino_hints)
-                and self._wino(*conv, obs_weights)):
+        if (algo == C.ALGO_AUTO and layer.mode == C.CONV_K2S1 and self._hint('wino', label) and self._wino(*conv, obs_weights)):
             return
-        hint = self._trial_lds or (0 if (self._trial_wino or self._trial_c32) else self.lds_hints.get(label, 0))
-        tn, unfold = hint & 255, bool((hint >> 8) & 1)  # +256: observations as separate frames, mean in its own launch
-        resident = bool(hint & 512)                     # +512: csrc/conv_tile3.hip's resident form (split weights stay in LDS)
+        tn, unfold, resident = hint_word(self._hint('lds', label))
         ok = (tn and obs_weights is None and algo == C.ALGO_AUTO and layer.mode in (C.CONV_K2S2, C.CONV_K2S1)
               and layer.cin == cin and cin % 16 == 0 and layer.n_ch_out % tn == 0)
         if ok and resident and (self.precision not in ('f32x3', 'f32x3_9') or C.conv_tile3r_plan(layer.mode, cin, tn) is None):
-            ok = self._trial_lds == 0                   # the resident form refuses this launch: a trial leaves it to the others,
+            ok = not trial                              # the resident form refuses this launch: a trial leaves it to the others,
             resident = False                            # a plan takes the streaming kernel
         if ok and unfold and kobs == 1:
-            ok = self._trial_lds == 0                   # nothing to unfold here: leave this launch to the other trials
+            ok = not trial                              # nothing to unfold here: a trial leaves this launch to the other trials
             unfold = False
         if ok and self.precision in ('f32x3', 'f32x3_9'):
             # fp32 operands as three bf16 terms on the bf16 matrix cores (csrc/conv_tile3.hip): 6 or all 9 term products
             self._enc_launch(C.conv_tile3r_forward if resident else C.conv_tile3_forward, layer.packed_tile3(tn), (tn,),
-                             self._ran_lds, unfold, *conv, nprod=9 if self.precision == 'f32x3_9' else 6)
+                             'lds', unfold, *conv, nprod=9 if self.precision == 'f32x3_9' else 6)
         elif ok:
-            self._enc_launch(C.conv_tile_forward, layer.packed_tile(tn), (tn,), self._ran_lds, unfold, *conv)
+            self._enc_launch(C.conv_tile_forward, layer.packed_tile(tn), (tn,), 'lds', unfold, *conv)
         else:
             self._conv(label, layer, act, src, cin, ld, None, 0, 0, frames * kobs, h, w, out, ldo, algo)
             if mean_out is not None:
@@ -344,8 +381,9 @@ class RenderPlan(OverrideMixin):
         """Plan-creation-time choice of the MFMA wave tile (RT x CT) per launch: streaming layers
         want many small waves (memory-level parallelism), deep layers big register tiles (MFMA
         bound); a few 4/8-channel layers are faster on the direct kernel.  Times every candidate
-        with HIP events on this shape and keeps the fastest."""
-        saved = (self.timer, dict(self.tile_hints), dict(self.algo_hints))
+        with HIP events on this shape and keeps the fastest.  Each candidate is one `_trial`: it hides the stored choices
+        while it runs, so nothing is saved, blanked or restored around it."""
+        saved_timer = self.timer
         self._tuning = True                 # no launch tapes while trial plans run
         results = {}
         trials = [('tile', 16 * r + c) for r in (1, 2, 4) for c in (1, 2, 4)]
@@ -371,57 +409,31 @@ class RenderPlan(OverrideMixin):
             cand = ((4, 8, 16, 32, 64, 128) if forms != 'two' else ()) + ((-16, -32, -64, -128) if forms == 'both' else ()) + \
                    ((-4, -8, -16, -32, -64, -128) if forms == 'two' else ())
             trials += [('splitk', (16 * r + c, ks)) for (r, c) in ((1, 1), (1, 2), (2, 2), (1, 4)) for ks in cand]
-        saved_lds, saved_sk, saved_wino, saved_c32 = dict(self.lds_hints), dict(self.splitk_hints), dict(self.wino_hints), dict(self.c32_hints)
-        for kind, hint in trials:
-            self.tile_hints = {'*': hint} if kind == 'tile' else ({'*': hint[0]} if kind == 'splitk' else {})
-            self.algo_hints = {}
-            self.lds_hints, self.splitk_hints, self.wino_hints, self.c32_hints = {}, {}, {}, {}
-            self._trial_direct = kind == 'direct'
-            self._trial_lds = hint if kind == 'lds' else 0
-            self._trial_wino = hint if kind == 'wino' else 0
-            self._trial_c32 = hint if kind == 'c32' else 0
-            self._trial_splitk = hint[1] if kind == 'splitk' else 0
-            self._ran_direct, self._ran_lds, self._ran_splitk, self._ran_wino, self._ran_c32 = set(), set(), set(), set(), set()
-            self.timer = None
-            run()
-            self.timer = OpTimer()
-            run(); run()
-            rec = self.timer.collect()
-            for label, r in rec.items():
-                t = r[1] / r[0]
-                if label.endswith('.o.s1') and label.replace('.s1', '.mean') in rec:
-                    m = rec[label.replace('.s1', '.mean')]
-                    t += m[1] / m[0]        # the LDS kernel folds the mean in: compare like with like
-                if (kind == 'tile' or label in self._ran_direct or label in self._ran_lds or label in self._ran_splitk
-                        or label in self._ran_wino or label in self._ran_c32):
-                    results.setdefault(label, []).append((t, kind, hint))
-        self._trial_direct, self._trial_lds, self._trial_splitk, self._trial_wino, self._trial_c32 = False, 0, 0, 0, 0
-        self.timer, self.tile_hints, self.algo_hints = saved
-        self.lds_hints, self.splitk_hints, self.wino_hints, self.c32_hints = saved_lds, saved_sk, saved_wino, saved_c32
+        try:
+            for kind, hint in trials:
+                self._trial, self._ran = (kind, hint), set()
+                self.timer = None
+                run()
+                self.timer = OpTimer()
+                run(); run()
+                rec = self.timer.collect()
+                for label, r in rec.items():
+                    t = r[1] / r[0]
+                    if label.endswith('.o.s1') and label.replace('.s1', '.mean') in rec:
+                        m = rec[label.replace('.s1', '.mean')]
+                        t += m[1] / m[0]    # the LDS kernel folds the mean in: compare like with like
+                    if kind == 'tile' or (label, kind) in self._ran:
+                        results.setdefault(label, []).append((t, kind, hint))
+        finally:
+            self._trial, self.timer, self._tuning = None, saved_timer, False
         for label, res in results.items():
             if '.s1' not in label and '.s2' not in label and label != 'L0.q':
                 continue
-            t, kind, hint = min(res)
+            _, kind, hint = min(res)
             if backward and 'dgrad' not in label:
                 continue                                            # (a backward trial pass only chooses backward-data launches)
-            if kind == 'direct':
-                self.algo_hints.setdefault(label, C.ALGO_DIRECT)
-            elif kind == 'lds':
-                if label not in self.wino_hints and label not in self.c32_hints:
-                    self.lds_hints.setdefault(label, hint)
-            elif kind == 'wino':
-                if label not in self.lds_hints and label not in self.c32_hints:
-                    self.wino_hints.setdefault(label, hint)
-            elif kind == 'c32':
-                if label not in self.lds_hints and label not in self.wino_hints:
-                    self.c32_hints.setdefault(label, hint)
-            elif kind == 'splitk':
-                if label not in self.tile_hints and label not in self.splitk_hints:
-                    self.tile_hints[label], self.splitk_hints[label] = hint
-            else:
-                self.tile_hints.setdefault(label, hint)
+            self.set_choice(label, kind, hint)
         self.tuned = {**getattr(self, 'tuned', {}), **results}
-        self._tuning = False
         self._drop_tapes()
         reg = getattr(self.q.layers[0], '_registry', None)
         if reg is not None and self.prune_packs:
@@ -433,17 +445,13 @@ class RenderPlan(OverrideMixin):
 
     def export_tuning(self):
         """The plan-time choices (wave tiles, direct / LDS-tiled kernel, split-K slices per launch label) as one dict."""
-        return {'tile_hints': dict(self.tile_hints), 'algo_hints': dict(self.algo_hints), 'lds_hints': dict(self.lds_hints),
-                'splitk_hints': dict(self.splitk_hints), 'wino_hints': dict(self.wino_hints), 'c32_hints': dict(self.c32_hints)}
+        return {a: dict(getattr(self, a)) for a in HINT_DICTS}
 
     def import_tuning(self, d):
         """Takes another plan's (or an earlier run's) choices and skips the plan-time trials: two plans with the same
         choices issue the same kernels with the same summation orders."""
-        self.tile_hints.update(d['tile_hints']); self.algo_hints.update(d['algo_hints'])
-        self.lds_hints.update(d.get('lds_hints', {}))
-        self.splitk_hints.update(d.get('splitk_hints', {}))
-        self.wino_hints.update(d.get('wino_hints', {}))
-        self.c32_hints.update(d.get('c32_hints', {}))
+        for a in HINT_DICTS:
+            getattr(self, a).update(d.get(a, {}))       # (files from before a family existed lack its key)
         self.autotune = False
         self._drop_tapes()
 
@@ -721,7 +729,7 @@ class RenderPlan(OverrideMixin):
         # level 2): the per-observation level-1 maps never reach HBM and L2.{q,o}.s2 are not launched.
         v4 = self.front_v4 and 0.0 <= alpha <= 1.0 and (resident is not None or C.front4_supported(base, cvis, lvis, nn_rgb, nn_base))
         # (training: only the second-generation kernel has a form that also keeps the level-1 maps the backward reads)
-        front2 = (self.front_l2 and blob_l2 is not None and (k <= 4 or v4) and h % 4 == 0 and w % 4 == 0 and not self._trial_direct
+        front2 = (self.front_l2 and blob_l2 is not None and (k <= 4 or v4) and h % 4 == 0 and w % 4 == 0 and not self._trying('direct')
                   and (not train or (v4 and self.front4_train)))
         if resident is not None and not (front2 and v4 and w % 8 == 0):
             raise C.NLTError("store-resident inputs need the fused front kernel (front4, level-2 fold, w % 8 == 0)")
@@ -763,8 +771,7 @@ class RenderPlan(OverrideMixin):
         # never waits for the query path; the query convs of a level only need the previous level's observation mean.
         # With two HIP streams the small deep-level launches of one path fill the CUs the other leaves idle.
         concurrent = (self.two_streams and dev.type == 'cuda' and (self.timer is None or getattr(self.timer, 'only', None) is not None)
-                      and not self._trial_lds and not self._trial_splitk and not self._trial_direct and not self._trial_wino
-                      and not self._trial_c32)
+                      and (self._trial is None or self._trial[0] == 'tile'))
         if concurrent:
             if self._side is None:
                 self._side = (torch.cuda.Stream(device=dev), [C.new_event() for _ in range(D + 3)])
@@ -846,7 +853,7 @@ class RenderPlan(OverrideMixin):
                 x, cx = b['dec'][j], db.n_ch_out
                 continue
             if (self.fuse_dec and not train and nl in (8, 16) and db.n_ch_out == nl and cx % 4 == 0 and algo == C.ALGO_AUTO
-                    and dact_a is not None and dact_b is not None and dact_a.alpha == dact_b.alpha and not self._trial_direct):
+                    and dact_a is not None and dact_b is not None and dact_a.alpha == dact_b.alpha and not self._trying('direct')):
                 da.build(cx + cs, dev); db.build(nl, dev)
                 nbytes = 4 * n * hh * ww * ((cx + cs) + 4 * nl) + 4 * n * 4 * hh * ww * 2 * nl      # both convs
                 self._launch(lab, nbytes, C.dec_block_forward, x, cx, skip, cs, n, hh, ww, da.kernel.detach(), da.bias.detach(),
@@ -994,18 +1001,18 @@ class RenderPlan(OverrideMixin):
         nbytes = 4 * (n * oh * ow * layer.n_ch_out + out_px * (hi - lo))
         # wave tile / split-K of this launch: chosen by timing at plan time like the forward's (`_autotune` on the backward)
         rows, ncols, flops = _gemm(adj, n, oh, ow, layer.n_ch_out, hi - lo)
-        tile_hint, nks = self._tile_splitk(label, rows, ncols, self._tuning, self._trial_splitk)
+        tile_hint, nks = self._tile_splitk(label, rows, ncols, False)
         # LDS-tiled kernel (csrc/conv_tile.hip) for the launches the plan-time trials gave to it: the adjoint families it has
         # (CONV_K2S1 / CONV_K2S2 of the expanding blocks, the transposed k2s1 of the encoder's stride-1 convs), no split epilogue
-        wtn = (self._trial_wino or self.wino_hints.get(label, 0)) & 255
+        wtn = hint_word(self._hint('wino', label))[0]
         if (wtn and self.use_wino and split is None and adj in (C.CONV_K2S1, C.DECONV_K2S1) and layer.n_ch_out % 8 == 0
                 and (hi - lo) % wtn == 0 and ldp % 4 == 0 and ldo % 4 == 0 and layer.kernel.is_contiguous()):
-            self._ran_wino.add(label)
+            self._ran.add((label, 'wino'))
             self._launch(label, nbytes, C.conv_wino_backward_data, adj, dpre, layer.n_ch_out, ldp, n, oh, ow,
                          layer.packed_adjoint_wino(lo, hi, wtn), hi - lo, wtn, out, ldo, mask_src=mask_src, ldm=ldm,
                          mask_alpha=mask_alpha, accumulate=accumulate, flops=flops)
             return
-        tn = (self._trial_lds or (0 if self._trial_wino else self.lds_hints.get(label, 0))) & 255
+        tn = hint_word(self._hint('lds', label))[0]
         tile_ok = tn and ldp % 4 == 0 and ldo % 4 == 0 and layer.kernel.is_contiguous()
         if tile_ok and adj == C.DECONV_K2S2:                        # transposed k2s2: a GEMM with 4 (hi - lo) columns; takes the split
             tile_ok = layer.n_ch_out % 32 == 0 and (hi - lo) % 16 == 0 and (4 * (hi - lo)) % tn == 0
@@ -1013,13 +1020,13 @@ class RenderPlan(OverrideMixin):
             tile_ok = (split is None and adj in (C.CONV_K2S1, C.CONV_K2S2, C.DECONV_K2S1) and layer.n_ch_out % 16 == 0
                        and (hi - lo) % tn == 0)
         if tile_ok:
-            self._ran_lds.add(label)
+            self._ran.add((label, 'lds'))
             self._launch(label, nbytes, C.conv_tile_backward_data, adj, dpre, layer.n_ch_out, ldp, n, oh, ow,
                          layer.packed_adjoint_tile(lo, hi, tn), hi - lo, tn, out, ldo, mask_src=mask_src, ldm=ldm, mask_alpha=mask_alpha,
                          accumulate=accumulate, split=split, w_keras=ks, flops=flops)
             return
         if abs(nks) > 1:
-            self._ran_splitk.add(label)
+            self._ran.add((label, 'splitk'))
         self._launch(label, nbytes, C.conv_backward_data, adj, dpre, layer.n_ch_out, ldp, n, oh, ow, packed, zero_bias, hi - lo,
                      out, ldo, mask_src=mask_src, ldm=ldm, mask_alpha=mask_alpha, accumulate=accumulate, tile_hint=tile_hint,
                      ksplit=nks, split=split, w_keras=ks, flops=flops)

@@ -46,11 +46,9 @@ from .engine import RenderPlan
 _PLAN_SWITCHES = ('precision', 'fuse_ends', 'front_l2', 'fuse_dec', 'front_v4', 'two_streams', 'use_tape', 'use_wino', 'use_c32', 'fuse_override', 'alias_obs')
 
 
-def _copy_tuning(dst, src):
-    dst.tile_hints, dst.algo_hints = dict(src.tile_hints), dict(src.algo_hints)
-    dst.lds_hints, dst.splitk_hints = dict(src.lds_hints), dict(src.splitk_hints)
-    dst.wino_hints = dict(src.wino_hints)
-    dst.c32_hints = dict(src.c32_hints)
+def _copy_tuning(dst, choices):
+    for attr, d in choices.items():                 # (RenderPlan.export_tuning(): a copy of each of its hint dicts)
+        setattr(dst, attr, d)
     dst._drop_tapes()
 
 
@@ -125,7 +123,7 @@ class RenderPipeline:
         self._streams = [None] * lanes
         self._tuned_ref = [None] * lanes
         self._switches = [None] * lanes                     # the model plan's switches / hints each lane last copied
-        self._hints = [({}, {}, {}, {}, {}, {})] * lanes
+        self._hints = [None] * lanes                        # (export_tuning() of the model plan)
         self._recent = collections.deque()                  # tickets of the last `lanes` submissions
         self._graphs = bool(graphs)
         self._threads = bool(threads) and lanes > 1 and not self._graphs      # (stream capture wants the other host threads quiet)
@@ -150,15 +148,14 @@ class RenderPipeline:
             self._lanes[i] = lane
         lane.conv_algo, lane.skip_connect_base = m.conv_algo, m.skip_connect_base
         sw = tuple(getattr(m.plan, a) for a in _PLAN_SWITCHES)
-        hints = (m.plan.tile_hints, m.plan.algo_hints, m.plan.lds_hints, m.plan.splitk_hints, m.plan.wino_hints, m.plan.c32_hints)
-        if (new or self._tuned_ref[i] is not getattr(m.plan, 'tuned', None) or self._switches[i] != sw
-                or any(dict(a) != b for a, b in zip(hints, self._hints[i]))):
+        hints = m.plan.export_tuning()
+        if new or self._tuned_ref[i] is not getattr(m.plan, 'tuned', None) or self._switches[i] != sw or self._hints[i] != hints:
             for a in _PLAN_SWITCHES:                        # the model plan's switches and choices, programmatic ones included:
                 setattr(lane.plan, a, getattr(m.plan, a))   # a lane issues exactly the launches Model.call would
-            _copy_tuning(lane.plan, m.plan)                 # lane 0's plan-time trials decide for every lane
+            _copy_tuning(lane.plan, m.plan.export_tuning())   # lane 0's plan-time trials decide for every lane
             self._tuned_ref[i] = getattr(m.plan, 'tuned', None)
             self._switches[i] = sw
-            self._hints[i] = tuple(dict(a) for a in hints)
+            self._hints[i] = hints
         if self._graphs:
             lane.plan.two_streams = False                   # a linear chain: the cheap kind of graph to launch
         lane.plan.autotune = False

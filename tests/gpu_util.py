@@ -145,23 +145,11 @@ def _spy_backward(monkeypatch, plan):
 
 
 def _force(plan, kind, hint, labels):
-    """Exactly one plan-time candidate on `labels`, every other launch on its default, no trials: the way
-    `RenderPlan._autotune` turns a winner into hints."""
-    from nlt_amd import capi as C
-    plan.tile_hints, plan.lds_hints, plan.wino_hints, plan.c32_hints, plan.splitk_hints, plan.algo_hints = {}, {}, {}, {}, {}, {}
+    """Exactly one plan-time candidate on `labels`, every other launch on its default, no trials: stored the way
+    `RenderPlan._autotune` stores a winner."""
+    plan.clear_choices()
     for label in labels:
-        if kind == 'direct':
-            plan.algo_hints[label] = C.ALGO_DIRECT
-        elif kind == 'lds':
-            plan.lds_hints[label] = hint
-        elif kind == 'wino':
-            plan.wino_hints[label] = hint
-        elif kind == 'c32':
-            plan.c32_hints[label] = hint
-        elif kind == 'splitk':
-            plan.tile_hints[label], plan.splitk_hints[label] = hint
-        else:
-            plan.tile_hints[label] = hint
+        plan.set_choice(label, kind, hint)
     plan.autotune = plan.tune_backward = False
     plan._drop_tapes()
 

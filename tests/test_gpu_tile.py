@@ -152,7 +152,7 @@ def test_model_with_three_term_split_encoder_vs_oracle(precision, depth, uv, k, 
         m.plan.lds_hints = dict(hints)
         vis.append(m.call(to_device_batch(batch, nn), mode)[3])
     torch.cuda.synchronize()
-    assert 'L3.o.s1' in p3.plan._ran_lds and 'L%d.q.s2' % nlev in p3.plan._ran_lds
+    assert 'L3.o.s1' in p3.plan.ran('lds') and 'L%d.q.s2' % nlev in p3.plan.ran('lds')
     e_oracle, e_native = rel_l2(vis[1]['pred'].cpu(), o_vis['pred']), rel_l2(vis[1]['pred'].cpu(), vis[0]['pred'].cpu())
     print("%s depth %d: pred rel-L2 vs fp32 oracle %.2e, vs native fp32 plan %.2e (native vs oracle %.2e)"
           % (precision, depth, e_oracle, e_native, rel_l2(vis[0]['pred'].cpu(), o_vis['pred'])))
@@ -183,5 +183,5 @@ def test_model_with_lds_tiled_encoder_vs_oracle(depth, uv, k, tn, mode):
     pm.plan.lds_hints = {'L%d.%s.%s' % (l, p, s): tn for l in range(1, nlev + 1) for p in 'qo' for s in ('s1', 's2')}
     p_vis = pm.call(to_device_batch(batch, nn), mode)[3]
     torch.cuda.synchronize()
-    assert 'L3.o.s1' in pm.plan._ran_lds and 'L%d.q.s2' % nlev in pm.plan._ran_lds and ('L2.o.s1' in pm.plan._ran_lds) == (tn == 32)
+    assert 'L3.o.s1' in pm.plan.ran('lds') and 'L%d.q.s2' % nlev in pm.plan.ran('lds') and ('L2.o.s1' in pm.plan.ran('lds')) == (tn == 32)
     assert rel_l2(p_vis['pred'].cpu(), o_vis['pred']) <= 1e-4

@@ -140,7 +140,7 @@ def test_plan_with_the_resident_bit_renders_the_same_bits(monkeypatch):
         before = len(resident_calls)
         preds.append(pm.call(to_device_batch(batch, nn), 'test')[3]['pred'].clone())
         torch.cuda.synchronize()
-        ran.append((len(resident_calls) - before, set(pm.plan._ran_lds)))
+        ran.append((len(resident_calls) - before, pm.plan.ran('lds')))
     assert ran[0][0] == 0 and ran[1][0] >= 4, [r[0] for r in ran]
     assert ran[0][1] == ran[1][1] and len(ran[0][1]) >= 4             # the same launches on the LDS-tiled family both times
     assert torch.equal(preds[0], preds[1])

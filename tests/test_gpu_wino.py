@@ -105,7 +105,7 @@ def test_conv_wino_backward_data_with_mask_and_accumulate(transpose_fwd):
 def _force_wino(pm, tn=32):
     """Every eligible launch of the plan on the Winograd kernel (a trial-style blanket hint), nothing else tuned."""
     pm.plan.autotune = False
-    pm.plan._trial_wino = tn
+    pm.plan._trial = ('wino', tn)
 
 
 @pytest.mark.parametrize('tn,k,uv', [(32, 3, 128), (64, 3, 128), (256 + 32, 3, 128), (256 + 64, 3, 128), (32, 1, 64), (64, 1, 64)])
@@ -120,7 +120,7 @@ def test_model_call_with_every_stride1_conv_on_the_winograd_kernel(tn, k, uv):
     ran = set()
     for _ in range(3):
         p_c, _, _, p_vis = pm.call(db, 'test')
-        ran |= pm.plan._ran_wino
+        ran |= pm.plan.ran('wino')
     torch.cuda.synchronize()
     assert any('.o.s1' in l for l in ran), ran
     if tn < 256:                                            # (+256 = "observations unfolded": a trial of the observation launches only)
@@ -139,7 +139,9 @@ def test_plan_time_trials_may_choose_the_winograd_kernel_and_lanes_copy_the_choi
         p_c, _, _, p_vis = pm.call(db, 'test')
     assert rel_l2(p_vis['pred'].cpu(), o_vis['pred']) <= 2e-6
     tuned = pm.plan.export_tuning()
-    assert 'wino_hints' in tuned and not (set(tuned['wino_hints']) & set(tuned['lds_hints']))
+    assert 'wino_hints' in tuned
+    for a, b in (('wino_hints', 'lds_hints'), ('wino_hints', 'c32_hints'), ('lds_hints', 'c32_hints')):
+        assert not (set(tuned[a]) & set(tuned[b])), (a, b)                 # (one encoder launch, one of the three families)
     from nlt_amd.pipeline import RenderPipeline
     with RenderPipeline(pm, lanes=2) as pipe:
         outs = pipe.render([db, db, db], 'test')
@@ -163,7 +165,7 @@ def test_train_steps_with_the_winograd_kernel_in_forward_and_backward_data():
     for step in range(3):
         lo, _ = O.train_step(om, oopt, batch, global_bs=2, nn_list=nn)
         lp = float(trainvali.distributed_train_step(pm, db, opt, 2)[0])
-        ran |= pm.plan._ran_wino
+        ran |= pm.plan.ran('wino')
         assert abs(lp - float(lo)) <= 2e-5 * max(1.0, abs(float(lo))), (step, lp, float(lo))
     assert any('dgrad' in l for l in ran) and any(l.endswith('.o.s1') for l in ran), ran
     worst = max(float((po_.detach() - c.kernel.cpu()).abs().max()) for po_, c in zip(om.parameters()[::2], pm._conv_layers()))

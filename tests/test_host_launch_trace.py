@@ -133,16 +133,16 @@ def _cases():
                             ('wino320', {'wino_hints': 256 + 64}), ('c32_1', {'c32_hints': 1}), ('c32_2', {'c32_hints': 2})):
             attrs = {a: {lab: v for lab in LABELS} for a, v in hints.items()}
             c['hint.%s.k3.%s' % (name, f)] = _infer(256, 64, 64, 3, _set(fuse_ends=fused, **attrs), n=2)
-        for name, attrs in (('wino32', {'_trial_wino': 32}), ('wino288', {'_trial_wino': 256 + 32}), ('lds32', {'_trial_lds': 32}),
-                            ('lds320', {'_trial_lds': 256 + 64}), ('c32_1', {'_trial_c32': 1}), ('c32_2', {'_trial_c32': 2})):
+        for name, trial in (('wino32', ('wino', 32)), ('wino288', ('wino', 256 + 32)), ('lds32', ('lds', 32)),
+                            ('lds320', ('lds', 256 + 64)), ('c32_1', ('c32', 1)), ('c32_2', ('c32', 2))):
             for k in (1, 3):
-                c['trial.%s.k%d.%s' % (name, k, f)] = _infer(256, 64, 64, k, _set(fuse_ends=fused, autotune=False, **attrs), n=2)
+                c['trial.%s.k%d.%s' % (name, k, f)] = _infer(256, 64, 64, k, _set(fuse_ends=fused, autotune=False, _trial=trial), n=2)
         for prec in ('f32x3', 'f32x3_9'):
             c['%s.lds32.k3.%s' % (prec, f)] = _infer(256, 64, 64, 3, _set(fuse_ends=fused, precision=prec,
                                                                          lds_hints={lab: 32 for lab in LABELS}), n=2)
         for k in (1, 2):
             c['train.k%d.%s' % (k, f)] = _train(k, _set(fuse_ends=fused))
-        c['train.trial_wino32.k1.' + f] = _train(1, _set(fuse_ends=fused, autotune=False, _trial_wino=32))
+        c['train.trial_wino32.k1.' + f] = _train(1, _set(fuse_ends=fused, autotune=False, _trial=('wino', 32)))
     c['infer.d256.64x64.k5.front_v4_off'] = _infer(256, 64, 64, 5, _set(front_v4=False))
     c['infer.d256.64x64.k1.alias_obs_off'] = _infer(256, 64, 64, 1, _set(alias_obs=False))
     c['infer.d256.64x64.k3.fuse_dec_off'] = _infer(256, 64, 64, 3, _set(fuse_dec=False))

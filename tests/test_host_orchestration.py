@@ -198,9 +198,9 @@ def test_lds_tiled_encoder_launches_fold_the_observation_mean(monkeypatch, fused
     rec = pm.plan.timer.records
     means = sorted(l for l in rec if l.endswith('.o.mean'))
     assert means == ([] if fused else ['L1.o.mean'])            # level 1 has 16 output channels: not eligible
-    assert pm.plan._ran_lds >= {'L3.q.s2', 'L3.o.s2', 'L2.q.s1', 'L2.o.s1', 'L6.o.s1'}
-    assert ('L2.o.s2' in pm.plan._ran_lds) != fused             # fused: level 2's stride-2 convs ran inside the front kernel
-    assert 'L1.q.s2' not in pm.plan._ran_lds
+    assert pm.plan.ran('lds') >= {'L3.q.s2', 'L3.o.s2', 'L2.q.s1', 'L2.o.s1', 'L6.o.s1'}
+    assert ('L2.o.s2' in pm.plan.ran('lds')) != fused             # fused: level 2's stride-2 convs ran inside the front kernel
+    assert 'L1.q.s2' not in pm.plan.ran('lds')
 
 
 @pytest.mark.parametrize('fused', [False, True])
@@ -228,7 +228,7 @@ def test_winograd_launches_of_the_plan(monkeypatch, fused, hint):
     assert rel_l2(got, ref) < 1e-5
     rec = pm.plan.timer.records
     means = sorted(l for l in rec if l.endswith('.o.mean'))
-    ran = pm.plan._ran_wino
+    ran = pm.plan.ran('wino')
     assert not any(l.endswith('.s2') for l in ran)
     eligible = [l for l in range(2, 7) if hint & 255 == 32 or l >= 3]       # level 2 has 32 channels: not a multiple of 64
     assert ran >= {'L%d.o.s1' % l for l in eligible} | {'L%d.q.s1' % l for l in eligible}
@@ -262,7 +262,7 @@ def test_narrow_level_launches_of_the_plan(monkeypatch, hint):
     pm.plan.timer = Rec()
     got = pm.call(cpu_batch(batch, nn), 'test')[3]['pred']
     assert rel_l2(got, ref) < 1e-5
-    assert pm.plan._ran_c32 == {'L2.q.s1', 'L2.o.s1'}
+    assert pm.plan.ran('c32') == {'L2.q.s1', 'L2.o.s1'}
     assert ('L2.o.mean' in pm.plan.timer.records) == (hint == 2)
 
 

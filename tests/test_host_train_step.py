@@ -59,7 +59,7 @@ def test_train_step_with_the_winograd_launches_of_forward_and_backward_data(monk
     om, pm = make(256, 64, 32, loss='l2')
     pm.build('cpu'); pm.register_trainable()
     pm.plan.autotune = False
-    pm.plan._trial_wino = 32
+    pm.plan._trial = ('wino', 32)
     batch, nn = O.synth_batch(2, 64, 64, 32, 32, 32, 32, k=1, seed=12)
     opt_o = O.KerasAdamAMSGrad(om.parameters(), 1e-3)
     opt_p = nlt_amd.optim.AdamAMSGrad(pm, 1e-3)
@@ -68,7 +68,7 @@ def test_train_step_with_the_winograd_launches_of_forward_and_backward_data(monk
     assert abs(float(lp) - float(lo)) <= 1e-5 * max(1.0, abs(float(lo)))
     ref = flat_oracle_grads(om, pm, go)
     assert float((pm.flat_params.grad - ref).norm() / ref.norm()) < 2e-4
-    ran = pm.plan._ran_wino
+    ran = pm.plan.ran('wino')
     assert {'L3.q.s1', 'L3.o.s1', 'L7.q.s1', 'bwd.L3.q.s1.dgrad', 'bwd.L3.o.s1.dgrad', 'bwd.L7.q.s1.dgrad'} <= ran, sorted(ran)
     assert not any('.s2' in l for l in ran)
 
