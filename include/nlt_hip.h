@@ -383,6 +383,26 @@ int nlt_conv_bf16_forward(int mode, int tile_hint,
                           int cout, void* out, int ldo, int out_is_f32, int act, float alpha, void* stream);
 int nlt_obs_mean_bf16(const unsigned short* obs, int n, int k, long hw, int c, unsigned short* out, int ldo, void* stream);
 
+/*
+ * nlt_conv_bf16_forward_map = nlt_conv_bf16_forward with a per-output-texel fp32 map added in the epilogue: the per-frame
+ * half of a bf16-region conv over concat(query features, GIVEN observation map) of the reference's inference mode, the
+ * given half -- linear and frame-independent -- evaluated once per feat_agg on the same bf16 operands (an "override map",
+ * see nlt_conv_forward_map).  bias_map [map_frames, oh, ow, cout] dense fp32, 16-byte aligned, fewer than 2^31 elements;
+ * map_frames = 1 (shared by all n frames) or n.  For NLT_DECONV_K2S2 the map is indexed by the OUTPUT texel.
+ *   v = (acc + bias) + bias_map, in that order, then LeakyReLU, then the fp32 / bf16 store: with out_is_f32 the result is
+ *   bit-identical to nlt_conv_bf16_forward(act = 0, fp32 out) followed by "+ map" and LeakyReLU.
+ * Every other argument, and every check on it, is nlt_conv_bf16_forward's.
+ *   replaces: the tf.concat((query_y, obs_override[i])) + Conv2D / Conv2DTranspose + LeakyReLU of nlt/nlt_test.py:78-94 and
+ *             nlt/models/nlt.py:172-174 for the encoder levels >= 3 and the expanding blocks mirroring them when the
+ *             model's `precision` is bf16.
+ */
+int nlt_conv_bf16_forward_map(int mode, int tile_hint,
+                              const void* src0, int ld0, int c0, int src0_is_f32,
+                              const void* src1, int ld1, int c1, int src1_is_f32,
+                              int n, int h, int w, const unsigned short* w_packed, const float* bias,
+                              int cout, void* out, int ldo, int out_is_f32, int act, float alpha,
+                              const float* bias_map, int map_frames, void* stream);
+
 /* Layers of the config branches the released .ini files leave off (executed layer by layer, nlt_amd/generic.py):
  *   nlt_act_forward / _backward       kind 0: LeakyReLU(alpha) / ReLU (alpha = 0), kind 1: tf.keras.layers.ELU(alpha)
  *                                     (nlt/networks/elements.py:69-78); backward takes the layer's OUTPUT y

@@ -144,6 +144,9 @@ SIGNATURES = {
     'nlt_conv_bf16_pack': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_conv_bf16_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int,
                                        _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_float, _vp]),
+    'nlt_conv_bf16_forward_map': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int,
+                                           _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _c_float,
+                                           _vp, _c_int, _vp]),
     'nlt_obs_mean_bf16': (_c_int, [_vp, _c_int, _c_int, _c_long, _c_int, _vp, _c_int, _vp]),
     'nlt_chmix_bf16_packed_elems': (_c_long, [_c_int, _c_int]),
     'nlt_chmix_bf16_pack': (_c_int, [_vp, _c_int, _c_int, _vp, _vp]),
@@ -1185,6 +1188,18 @@ def conv_bf16_forward(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, w_packed, bia
     po, fo = _any_ptr(out, 'out')
     _call('nlt_conv_bf16_forward', mode, tile_hint, p0, ld0, c0, f0, p1, ld1, c1, f1, n, h, w,
           _tptr(w_packed, torch.bfloat16, 'w_packed'), _ptr(bias), cout, po, ldo, fo, 1 if act else 0, float(alpha))
+
+
+def conv_bf16_forward_map(mode, src0, c0, ld0, src1, c1, ld1, n, h, w, w_packed, bias, cout, out, ldo, bias_map,
+                          act=True, alpha=0.3, tile_hint=0):
+    """out = act((conv(src0 | src1) + bias) + bias_map) on the bf16 matrix cores: conv_bf16_forward with the per-output-texel
+    fp32 map [1 or n, oh, ow, cout] (dense) of the override plan (include/nlt_hip.h: nlt_conv_bf16_forward_map)."""
+    p0, f0 = _any_ptr(src0, 'src0')
+    p1, f1 = _any_ptr(src1, 'src1')
+    po, fo = _any_ptr(out, 'out')
+    _call('nlt_conv_bf16_forward_map', mode, tile_hint, p0, ld0, c0, f0, p1, ld1, c1, f1, n, h, w,
+          _tptr(w_packed, torch.bfloat16, 'w_packed'), _ptr(bias), cout, po, ldo, fo, 1 if act else 0, float(alpha),
+          _tptr(bias_map, torch.float32, 'bias_map'), bias_map.shape[0])
 
 
 def obs_mean_bf16(obs, n, k, hw, c, out, ldo):

@@ -11,6 +11,11 @@
 // group g owns channels 8g .. 8g+7 of the chunk, so both operands are one 16-byte load per lane (8 bf16).  A source may
 // also be fp32 (the region's inputs come from the fp32 level-2 kernels): two 16-byte loads, rounded to bf16 (nearest
 // even) in registers.  The output is bf16 (8-byte store per lane) or fp32 (the region's last layer).  No LDS, no barriers.
+//
+// nlt_conv_bf16_forward_map (template parameter MAP; the plain entry's instantiations keep their code) adds a per-output-texel
+// fp32 map in the epilogue, v = (acc + bias) + map, one 16-byte load per (rt, ct): the reference's inference mode under
+// precision = bf16 (nlt/nlt_test.py:78-94, nlt/models/nlt.py:172-174), where the GIVEN half of every concat is one map for all
+// frames and its share of the conv is evaluated once, on the same bf16 operands (engine_infer.py).
 #include "nlt_common.h"
 #include "pack_common.h"
 
@@ -34,6 +39,8 @@ struct BfP {
   const void* src0; const void* src1;       // NHWC, fp32 or bf16 (f0 / f1)
   const u16* wgt;                            // packed fragments
   const float* bias;
+  const float* map;                          // MAP kernels: per-output-texel fp32 addend [map_frames, oh, ow, cout], dense
+  long map_fstride;                          // oh * ow * cout (map per frame) or 0 (one map shared by all frames)
   void* out;                                 // fp32 or bf16 (fo)
   int f0, f1, fo;
   int n, h, w, c0, c1, ld0, ld1, cout, ldo;
@@ -71,7 +78,8 @@ __global__ void pack_bf16_kernel(const float* __restrict__ wk, int c0, int c1, i
   wp[idx] = f2bf(v);
 }
 
-template <int MODE, int RT, int CT>
+// MAP: v = (acc + bias) + map[output texel] before the activation (the override plan's frame-independent half of a concat conv)
+template <int MODE, int RT, int CT, bool MAP>
 __global__ __launch_bounds__(256) void conv_bf16_kernel(BfP p, int mtiles, int ngroups, int ntiles) {
   constexpr int TAPS = (MODE == NLT_CONV1X1 || MODE == NLT_DECONV_K2S2) ? 1 : 4;
   const int lane = threadIdx.x & 63;
@@ -175,6 +183,10 @@ __global__ __launch_bounds__(256) void conv_bf16_kernel(BfP p, int mtiles, int n
       int otex = rm[rt];
       if (MODE == NLT_DECONV_K2S2) otex = (rf[rt] * p.oh + 2 * ry[rt] + (ab >> 1)) * p.ow + 2 * rx[rt] + (ab & 1);
       f32x4 v = acc[rt][ct] + bv;
+      if (MAP) {                                                       // texel within its frame: frames share the map or own one
+        const size_t mtex = (size_t)otex - (size_t)rf[rt] * p.oh * p.ow;
+        v = v + *reinterpret_cast<const f32x4*>(p.map + (size_t)rf[rt] * p.map_fstride + mtex * p.cout + oc);
+      }
       if (p.act) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : p.alpha * v[j];
@@ -207,18 +219,18 @@ __global__ __launch_bounds__(256) void obs_mean_bf16_kernel(const u16* __restric
       make_uint4(pack2(s[0] * inv, s[1] * inv), pack2(s[2] * inv, s[3] * inv), pack2(s[4] * inv, s[5] * inv), pack2(s[6] * inv, s[7] * inv));
 }
 
-template <int MODE, int RT, int CT>
+template <int MODE, int RT, int CT, bool MAP>
 int launch_tile(const BfP& p, hipStream_t s) {
   const int ntiles = (p.N + 15) >> 4;
   const int ngroups = ntiles / CT;
   const int mtiles = (p.M + 16 * RT - 1) / (16 * RT);
   const long waves = (long)mtiles * ngroups;
-  hipLaunchKernelGGL((conv_bf16_kernel<MODE, RT, CT>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p, mtiles, ngroups, ntiles);
+  hipLaunchKernelGGL((conv_bf16_kernel<MODE, RT, CT, MAP>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, p, mtiles, ngroups, ntiles);
   NLT_CHECK_LAUNCH();
   return NLT_OK;
 }
 
-template <int MODE>
+template <int MODE, bool MAP>
 int launch_mode(const BfP& p, int tile_hint, hipStream_t s) {
   const int ntiles = (p.N + 15) >> 4;
   int RT = 0, CT = 0;
@@ -234,7 +246,7 @@ int launch_mode(const BfP& p, int tile_hint, hipStream_t s) {
     }
   }
   if (CT <= 0 || ntiles % CT) return NLT_ERR_UNSUPPORTED;
-#define NLT_TILE(R, C) if (RT == R && CT == C) return launch_tile<MODE, R, C>(p, s);
+#define NLT_TILE(R, C) if (RT == R && CT == C) return launch_tile<MODE, R, C, MAP>(p, s);
   NLT_TILE(4, 4) NLT_TILE(2, 4) NLT_TILE(4, 2) NLT_TILE(2, 2) NLT_TILE(1, 2) NLT_TILE(2, 1) NLT_TILE(1, 1)
 #undef NLT_TILE
   return NLT_ERR_UNSUPPORTED;
@@ -272,13 +284,16 @@ extern "C" int nlt_conv_bf16_pack(int mode, const float* w_keras, int c0, int c1
   return NLT_OK;
 }
 
-extern "C" int nlt_conv_bf16_forward(int mode, int tile_hint,
-                                     const void* src0, int ld0, int c0, int src0_is_f32,
-                                     const void* src1, int ld1, int c1, int src1_is_f32,
-                                     int n, int h, int w, const unsigned short* w_packed, const float* bias,
-                                     int cout, void* out, int ldo, int out_is_f32, int act, float alpha, void* stream) {
+namespace {
+
+// nlt_conv_bf16_forward and its bias-map form: one set of argument checks, the map a template parameter of the kernel
+template <bool MAP>
+int conv_bf16_run(int mode, int tile_hint, const void* src0, int ld0, int c0, int src0_is_f32, const void* src1, int ld1, int c1,
+                  int src1_is_f32, int n, int h, int w, const unsigned short* w_packed, const float* bias, int cout, void* out, int ldo,
+                  int out_is_f32, int act, float alpha, const float* bias_map, int map_frames, void* stream) {
   if (!src0 || !w_packed || !bias || !out) return NLT_ERR_BAD_ARG;
   if (n <= 0 || h <= 0 || w <= 0 || c0 <= 0 || c1 < 0 || cout <= 0 || (c1 > 0 && !src1)) return NLT_ERR_BAD_ARG;
+  if (MAP && (!bias_map || !nlt_aligned16(bias_map) || (map_frames != 1 && map_frames != n))) return NLT_ERR_BAD_ARG;
   if (nlt_conv_bf16_packed_elems(mode, c0, c1, cout) <= 0) return NLT_ERR_UNSUPPORTED;
   if (ld0 < c0 || (ld0 & 7) || (c1 > 0 && (ld1 < c1 || (ld1 & 7))) || ldo < cout || (ldo & 3)) return NLT_ERR_BAD_ARG;
   if (mode == NLT_CONV_K2S2 && ((h | w) & 1)) return NLT_ERR_UNSUPPORTED;
@@ -286,6 +301,7 @@ extern "C" int nlt_conv_bf16_forward(int mode, int tile_hint,
     return NLT_ERR_BAD_ARG;
   BfP p;
   p.src0 = src0; p.src1 = src1; p.wgt = w_packed; p.bias = bias; p.out = out;
+  p.map = nullptr; p.map_fstride = 0;
   p.f0 = src0_is_f32; p.f1 = src1_is_f32; p.fo = out_is_f32;
   p.n = n; p.h = h; p.w = w; p.c0 = c0; p.c1 = c1; p.ld0 = ld0; p.ld1 = ld1; p.cout = cout; p.ldo = ldo;
   p.act = act; p.alpha = alpha;
@@ -296,16 +312,44 @@ extern "C" int nlt_conv_bf16_forward(int mode, int tile_hint,
   const long long in_elems = (long long)n * h * w * (long long)(ld0 > ld1 ? ld0 : ld1);
   const long long out_elems = (long long)n * p.oh * p.ow * (long long)ldo;
   if (M >= (1ll << 31) || in_elems >= (1ll << 31) || out_elems >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+  if (MAP) {
+    const long long per_frame = (long long)p.oh * p.ow * cout;
+    if (per_frame * map_frames >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+    p.map = bias_map; p.map_fstride = map_frames == 1 ? 0 : (long)per_frame;
+  }
   p.M = (int)M;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (mode) {
-    case NLT_CONV1X1: return launch_mode<NLT_CONV1X1>(p, tile_hint, s);
-    case NLT_CONV_K2S2: return launch_mode<NLT_CONV_K2S2>(p, tile_hint, s);
-    case NLT_CONV_K2S1: return launch_mode<NLT_CONV_K2S1>(p, tile_hint, s);
-    case NLT_DECONV_K2S2: return launch_mode<NLT_DECONV_K2S2>(p, tile_hint, s);
-    case NLT_DECONV_K2S1: return launch_mode<NLT_DECONV_K2S1>(p, tile_hint, s);
+    case NLT_CONV1X1: return launch_mode<NLT_CONV1X1, MAP>(p, tile_hint, s);
+    case NLT_CONV_K2S2: return launch_mode<NLT_CONV_K2S2, MAP>(p, tile_hint, s);
+    case NLT_CONV_K2S1: return launch_mode<NLT_CONV_K2S1, MAP>(p, tile_hint, s);
+    case NLT_DECONV_K2S2: return launch_mode<NLT_DECONV_K2S2, MAP>(p, tile_hint, s);
+    case NLT_DECONV_K2S1: return launch_mode<NLT_DECONV_K2S1, MAP>(p, tile_hint, s);
   }
   return NLT_ERR_BAD_ARG;
+}
+
+}  // namespace
+
+extern "C" int nlt_conv_bf16_forward(int mode, int tile_hint,
+                                     const void* src0, int ld0, int c0, int src0_is_f32,
+                                     const void* src1, int ld1, int c1, int src1_is_f32,
+                                     int n, int h, int w, const unsigned short* w_packed, const float* bias,
+                                     int cout, void* out, int ldo, int out_is_f32, int act, float alpha, void* stream) {
+  return conv_bf16_run<false>(mode, tile_hint, src0, ld0, c0, src0_is_f32, src1, ld1, c1, src1_is_f32, n, h, w, w_packed, bias, cout,
+                              out, ldo, out_is_f32, act, alpha, nullptr, 0, stream);
+}
+
+// out = act((conv(src0 | src1) + bias) + bias_map[output texel]): the per-frame half of a bf16-region conv over
+// concat(query, given observation map) (engine_infer.py); bias_map fp32 [map_frames, oh, ow, cout], map_frames 1 or n
+extern "C" int nlt_conv_bf16_forward_map(int mode, int tile_hint,
+                                         const void* src0, int ld0, int c0, int src0_is_f32,
+                                         const void* src1, int ld1, int c1, int src1_is_f32,
+                                         int n, int h, int w, const unsigned short* w_packed, const float* bias,
+                                         int cout, void* out, int ldo, int out_is_f32, int act, float alpha,
+                                         const float* bias_map, int map_frames, void* stream) {
+  return conv_bf16_run<true>(mode, tile_hint, src0, ld0, c0, src0_is_f32, src1, ld1, c1, src1_is_f32, n, h, w, w_packed, bias, cout,
+                             out, ldo, out_is_f32, act, alpha, bias_map, map_frames, stream);
 }
 
 extern "C" int nlt_obs_mean_bf16(const unsigned short* obs, int n, int k, long hw, int c, unsigned short* out, int ldo, void* stream) {

@@ -123,7 +123,8 @@ class RenderPlan(OverrideMixin):
         self._tuning = False
         self.tune_backward = os.environ.get('NLT_TUNE_BWD', '1') != '0'   # plan-time trials for the backward-data launches too
         # 'bf16' (BASELINE config 5): encoder levels >= 3 and the expanding blocks mirroring them run on csrc/conv_bf16.hip with
-        # bf16-stored activations (inference, fused plan); everything at full / half / quarter resolution stays fp32.
+        # bf16-stored activations (inference: the fused plan and the fused obs_override plan of engine_infer.py); everything at
+        # full / half / quarter resolution stays fp32.
         # 'f32x3' / 'f32x3_9': fp32 storage everywhere; the LDS-tiled encoder convs multiply fp32 operands as three bf16 terms
         # on the bf16 matrix cores (6 / all 9 term products, csrc/conv_tile3.hip) -- forward launches of inference AND training
         self.precision = os.environ.get('NLT_PRECISION', 'fp32')
@@ -319,16 +320,21 @@ class RenderPlan(OverrideMixin):
                          frames, kobs, h, w, out, ldo, mean_out, ldm)
         return True
 
-    def _conv_bf(self, label, layer, act, src0, c0, ld0, src1, c1, ld1, n, h, w, out, ldo):
-        """One conv of the bf16 region (csrc/conv_bf16.hip); sources / output fp32 or bf16 as their tensors are."""
+    def _conv_bf(self, label, layer, act, src0, c0, ld0, src1, c1, ld1, n, h, w, out, ldo, bmap=None):
+        """One conv of the bf16 region (csrc/conv_bf16.hip); sources / output fp32 or bf16 as their tensors are.
+        bmap: fp32 per-output-texel map [1 | n, oh, ow, cout] added before the activation (engine_infer.py)."""
         layer.build(c0 + c1, src0.device)
         assert layer.cin == c0 + c1, (layer.cin, c0, c1)
         oh, ow = layer.out_hw(h, w)
         bpe = lambda t: 4 if t.dtype == torch.float32 else 2
         moved = n * h * w * (c0 * bpe(src0) + (c1 * bpe(src1) if c1 else 0)) + n * oh * ow * layer.n_ch_out * bpe(out)
-        self._launch(label, 4 * (n * h * w * (c0 + c1) + n * oh * ow * layer.n_ch_out), C.conv_bf16_forward, layer.mode,
+        fn, extra = C.conv_bf16_forward, ()
+        if bmap is not None:
+            fn, extra = C.conv_bf16_forward_map, (bmap,)
+            moved += 4 * bmap.numel()
+        self._launch(label, 4 * (n * h * w * (c0 + c1) + n * oh * ow * layer.n_ch_out), fn, layer.mode,
                      src0, c0, ld0, src1, c1, ld1, n, h, w, layer.packed_bf16(c0, c1), layer.bias.detach(), layer.n_ch_out, out, ldo,
-                     **_act_kw(act), tile_hint=0 if self._trial is not None else self.tile_hints.get('bf.' + label, 0),
+                     *extra, **_act_kw(act), tile_hint=0 if self._trial is not None else self.tile_hints.get('bf.' + label, 0),
                      flops=_gemm(layer.mode, n, h, w, c0 + c1, layer.n_ch_out)[2], moved=moved)
 
     def _conv_enc(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, algo, mean_out=None, ldm=0,
@@ -653,8 +659,11 @@ class RenderPlan(OverrideMixin):
         mult = 2 if self.use_obs else 1
         run_obs = self.use_obs and obs_override is None
         if self.precision == 'bf16' and not (fused and inference):
-            raise C.NLTError("precision = bf16 is an inference mode of the fused plan (training, obs_override / obs_weights and the "
-                             "layer-by-layer plan run fp32)")
+            what = ("training" if not inference else "obs_weights" if obs_weights is not None else
+                    "this obs_override (per-frame maps, or a network / plan / UV size the fused override plan does not take)"
+                    if obs_override is not None else "the layer-by-layer plan")
+            raise C.NLTError("precision = bf16 is an inference mode of the fused plans -- refused here: %s (training, obs_weights, "
+                             "per-frame obs_override maps and the layer-by-layer plan run fp32)" % what)
         if fused:
             return self._forward_fused(b, base, cvis, lvis, nn_rgb, nn_base, skip_connect_base, algo, train=not inference)
 

@@ -21,6 +21,14 @@ What qualifies (`can_fuse_override`): one [1,h,w,C] map per level, an expand()ed
 frames are copies of one map (the reference's tf.tile(x, (bs, 1, 1, 1)), nlt/nlt_test.py:83-86; checked on the device once per tensor
 set).  Store-resident batches (Dataset.load_batch(resident=True)) are read in place (`_forward_resident_ovr`, nlt_front_ovr_forward_u8).
 
+`precision = bf16`: the bf16 region of the ordinary fused forward (encoder levels >= 3, expanding blocks j <= D - 3, bf16-stored
+maps, block D - 3 handing fp32 on) runs here too -- its concat convs on nlt_conv_bf16_forward_map, the rest on
+nlt_conv_bf16_forward (csrc/conv_bf16.hip).  The maps of the region's consumers are evaluated on the region's OPERANDS (given map
+and weight slice rounded to bf16, fp32 accumulation, fp32 result), and the bottleneck's two weight slices stay two groups over the
+same tensor instead of being summed (round(W1 + W2) != round(W1) + round(W2)): against OracleModel.set_precision('bf16') with
+obs_override what is left is fp32 summation order -- level 3's output bit-equal in >= 98 % of its elements
+(tests/test_gpu_infer_bf16.py).  Levels <= 2 and blocks j > D - 3 are the fp32 plan unchanged.
+
 Same re-association as the folded front kernel (sum over [q | ovr] channels split into two sums): <= 1e-6 rel-L2 from the
 layer-by-layer plan, <= 1e-4 from the oracle (tests/test_gpu_infer.py).
 """
@@ -64,7 +72,9 @@ class OverrideMixin:
 
     def can_fuse_override(self, cl, obs_override, h, w, arrays=()):
         q, D, U = self.q, self.n_down, self.n_up
-        if not (self.fuse_ends and self.fuse_override and self.use_obs and D >= 2 and U >= 2 and self.precision != 'bf16'):
+        if not (self.fuse_ends and self.fuse_override and self.use_obs and D >= 2 and U >= 2):
+            return False
+        if self.precision == 'bf16' and not (D >= 3 and self._bf16_region_ok(cl)):
             return False
         if len(obs_override) != D + 1 or (h | w) & 3:
             return False
@@ -89,6 +99,14 @@ class OverrideMixin:
         # nlt/nlt_test.py:83-86 -- takes this plan when its frames are copies of one map (checked on the device once per tensor set)
         return not tiled or self._frames_identical(obs_override)
 
+    def _bf16_region_ok(self, cl):
+        """What csrc/conv_bf16.hip asks of the bf16 region (levels >= 3, expanding blocks j <= D - 3): input channel counts in
+        multiples of 8, output channel counts in multiples of 4."""
+        q, D = self.q, self.n_down
+        blocks = [tuple(c.n_ch_out for c, _ in q.layers[D + 1 + j].convs()) for j in range(D - 2)]
+        return all(c % 8 == 0 for c in cl[2:]) and all(a % 8 == 0 and b % 4 == 0 for a, b in blocks) \
+            and all(b % 8 == 0 for _, b in blocks[:-1])
+
     def _frames_identical(self, obs_override):
         key = tuple((t.data_ptr(), t._version, tuple(t.shape), t.stride(0)) for t in obs_override)
         with OverrideMixin._lock:
@@ -105,7 +123,7 @@ class OverrideMixin:
     def _ovr_stamp(self, obs_override):
         q = self.q
         convs = [q.layers[0], q.layers[-1]] + [c for l in q.layers[1:-1] for c, _ in l.convs()]
-        return (tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in obs_override),
+        return (self.precision, tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in obs_override),
                 tuple((c.kernel.data_ptr(), c.kernel._version, c.bias._version, c._epoch[0]) for c in convs))
 
     def _prepare_override(self, b, obs_override, dev):
@@ -127,6 +145,10 @@ class OverrideMixin:
         ovr = [t[0:1].contiguous() for t in obs_override]
         cl = [t.shape[3] for t in ovr]
         st = {'stamp': stamp, 'serial': OverrideMixin._serial[0], 'ovr': ovr, 'enc': {}, 'dec': {}}
+        # precision = bf16: the maps of the bf16 region's consumers (first conv of levels >= 3 and of blocks j <= D - 3) are
+        # evaluated on the region's OPERANDS -- given map and weight slice rounded to bf16, fp32 accumulation, fp32 result -- as
+        # the full-K conv over concat(query, given) would see them: what is left against it is fp32 summation order
+        bf = self.precision == 'bf16'
         OverrideMixin._serial[0] += 1
         paused = C.tape_pause()
         try:
@@ -138,6 +160,17 @@ class OverrideMixin:
                 out = torch.empty((1, oh, ow, c.n_ch_out), device=dev, dtype=torch.float32)
                 C.conv_forward(c.mode, x, cin, cin, None, 0, 0, 1, h, w, c.kernel, c.packed(cin, 0), c.bias, c.n_ch_out,
                                out, c.n_ch_out, act=False, alpha=0.0)
+                return out
+
+            def run_map_bf(d, x, twice=False):
+                """run_map on csrc/conv_bf16.hip (twice: x is both sources of a two-group conv); fp32 out, unrounded."""
+                c = d.conv
+                _, h, w, cin = x.shape
+                oh, ow = c.out_hw(h, w)
+                out = torch.empty((1, oh, ow, c.n_ch_out), device=dev, dtype=torch.float32)
+                c1 = cin if twice else 0
+                C.conv_bf16_forward(c.mode, x, cin, cin, x if twice else None, c1, c1, 1, h, w, c.packed_bf16(cin, c1), c.bias,
+                                    c.n_ch_out, out, c.n_ch_out, act=False, alpha=0.0)
                 return out
             q0, head = q.layers[0], q.layers[-1]
             (qa, _), (qb, _) = q.layers[1].convs()
@@ -155,20 +188,32 @@ class OverrideMixin:
                 c = cl[l - 1]
                 sa.build(2 * c, dev)
                 zero = torch.zeros_like(sa.bias)
-                st['enc'][l] = (_Derived(sa, [[(0, c)]], zero).conv, run_map(_Derived(sa, [[(c, 2 * c)]], sa.bias), ovr[l - 1]))
+                dq, dm = _Derived(sa, [[(0, c)]], zero).conv, _Derived(sa, [[(c, 2 * c)]], sa.bias)
+                if bf:
+                    dq.packed_bf16(c, 0)                    # (packed here: outside any launch tape)
+                st['enc'][l] = (dq, (run_map_bf if bf else run_map)(dm, ovr[l - 1]))
             cx = 2 * cl[D]
             for j in range(U):
                 (da, _), (db, _) = q.layers[D + 1 + j].convs()
                 c = cl[D - j]
                 da.build(cx + 2 * c, dev)
                 zero = torch.zeros_like(da.bias)
-                if j == 0:          # bottleneck self-concat (nlt.py:180-190): x = skip = fm[D] = [q | ovr | q | ovr]
+                region = bf and j <= D - 3
+                if j == 0 and region:
+                    # bf16: round(W1 + W2) != round(W1) + round(W2) -- the two slices stay two groups and the tensor enters twice
+                    dq = _Derived(da, [[(0, c)], [(2 * c, 3 * c)]], zero).conv
+                    dm = _Derived(da, [[(c, 2 * c)], [(3 * c, 4 * c)]], da.bias)
+                elif j == 0:        # bottleneck self-concat (nlt.py:180-190): x = skip = fm[D] = [q | ovr | q | ovr]
                     dq = _Derived(da, [[(0, c), (2 * c, 3 * c)]], zero).conv
                     dm = _Derived(da, [[(c, 2 * c), (3 * c, 4 * c)]], da.bias)
                 else:
                     dq = _Derived(da, [[(0, cx + c)]], zero).conv
                     dm = _Derived(da, [[(cx + c, cx + 2 * c)]], da.bias)
-                st['dec'][j] = (dq, run_map(dm, ovr[D - j]))
+                if region:
+                    dq.packed_bf16(c if j == 0 else cx, c)  # (packed here: outside any launch tape)
+                    st['dec'][j] = (dq, run_map_bf(dm, ovr[D - j], twice=j == 0))
+                else:
+                    st['dec'][j] = (dq, run_map(dm, ovr[D - j]))
                 cx = db.n_ch_out
         finally:
             C.tape_resume(paused)
@@ -228,21 +273,41 @@ class OverrideMixin:
             self._launch('F.front', nbytes, C.front_ovr_forward, base, cvis, lvis, n, h, w, blob, blob_l2, st['p1'], st['s0'], st['p2'],
                          skip_connect_base, alpha, b['fm'][1], 2 * cl[1], b['skip3'], b['qtmp'][2], flops=flops, moved=moved)
         hh, ww = h2, w2
+        # precision = bf16: the region of `_forward_fused` (levels >= 3, blocks j <= D - 3; bf16-stored maps as `_buffers` made them,
+        # block D - 3 hands fp32 on) on csrc/conv_bf16.hip, its concat convs with their override map in the epilogue
+        bf = self.precision == 'bf16'
         for l in range(2, D + 1):
             (qa, qact_a), (qb, qact_b) = q.layers[l].convs()
             c = cl[l]
             if l > 2:
                 dq, pmap = st['enc'][l]
-                self._conv('V%d.q.s2' % l, dq, qact_a, b['fm'][l - 1], cl[l - 1], 2 * cl[l - 1], None, 0, 0, n, hh, ww,
-                           b['qtmp'][l], c, algo, bmap=pmap)
+                if bf:                                              # (source: the query half of fm[l - 1]; fp32 at l = 3)
+                    self._conv_bf('V%d.q.s2' % l, dq, qact_a, b['fm'][l - 1], cl[l - 1], 2 * cl[l - 1], None, 0, 0, n, hh, ww,
+                                  b['qtmp'][l], c, bmap=pmap)
+                else:
+                    self._conv('V%d.q.s2' % l, dq, qact_a, b['fm'][l - 1], cl[l - 1], 2 * cl[l - 1], None, 0, 0, n, hh, ww,
+                               b['qtmp'][l], c, algo, bmap=pmap)
             hh, ww = hh // 2, ww // 2
-            self._conv_enc('L%d.q.s1' % l, qb, qact_b, b['qtmp'][l], c, c, n, 1, hh, ww, b['fm'][l], 2 * c, algo)
+            if bf and l > 2:
+                self._conv_bf('L%d.q.s1' % l, qb, qact_b, b['qtmp'][l], c, c, None, 0, 0, n, hh, ww, b['fm'][l], 2 * c)
+            else:
+                self._conv_enc('L%d.q.s1' % l, qb, qact_b, b['qtmp'][l], c, c, n, 1, hh, ww, b['fm'][l], 2 * c, algo)
         x, cx = b['fm'][D], 2 * cl[D]
         for j in range(U - 1):
             (da, dact_a), (db, dact_b) = q.layers[D + 1 + j].convs()
             skip, cs = b['fm'][D - j], 2 * cl[D - j]
             lab = 'L%d.q' % (D + 1 + j)
             nl = da.n_ch_out
+            if bf and j <= D - 3:
+                # [x | QUERY half of fm[D - j]] + the block's map; the bottleneck reads the query half of fm[D] as BOTH sources
+                dq, dmap = st['dec'][j]
+                c = cl[D - j]
+                srcs = (skip, c, 2 * c, skip, c, 2 * c) if j == 0 else (x, cx, cx, skip, c, 2 * c)
+                self._conv_bf('V' + lab[1:] + '.s2', dq, dact_a, *srcs, n, hh, ww, b['dtmp'][j], nl, bmap=dmap)
+                hh, ww = hh * 2, ww * 2
+                self._conv_bf(lab + '.s1', db, dact_b, b['dtmp'][j], nl, nl, None, 0, 0, n, hh, ww, b['dec'][j], db.n_ch_out)
+                x, cx = b['dec'][j], db.n_ch_out
+                continue
             if (self.fuse_dec and nl in (8, 16) and db.n_ch_out == nl and cx == 2 * nl and cs == 8 * nl and algo == C.ALGO_AUTO
                     and dact_a is not None and dact_b is not None and dact_a.alpha == dact_b.alpha and j > 0):
                 # csrc/dec_block.hip on [x | QUERY half of fm[D - j]] + the block's override map: the given half is never read

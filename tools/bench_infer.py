@@ -1,5 +1,6 @@
 """The reference's inference mode (nlt_test.extract_feat -> nlt_test.infer, Model.call(obs_override=feat_agg)) timed:
-   python tools/bench_infer.py depth uv frames cam [general] [lanes=N] [quiet]
+   python tools/bench_infer.py depth uv frames cam [general] [lanes=N] [quiet] [precision=NAME]
+   precision=bf16: the middle of the fused query-only plan on csrc/conv_bf16.hip (the config's `precision` key)
    config 3's UV size: 256 1024 4 512      config 2: 256 512 4 512"""
 import os
 import sys
@@ -18,8 +19,9 @@ depth, uv, n, cam = (int(x) for x in sys.argv[1:5])
 flags = sys.argv[5:]
 general, quiet = 'general' in flags, 'quiet' in flags
 lanes = max([int(f.split('=')[1]) for f in flags if f.startswith('lanes=')] + [1])
+precision = ([f.split('=')[1] for f in flags if f.startswith('precision=')] + ['fp32'])[-1]
 dev = torch.device('cuda')
-pm = get_model_class('nlt')(nlt_amd.make_config(depth=depth, uvh=uv, uvw=uv, imh=cam, imw=cam)).build(dev)
+pm = get_model_class('nlt')(nlt_amd.make_config(depth=depth, uvh=uv, uvw=uv, imh=cam, imw=cam, precision=precision)).build(dev)
 pm.register_trainable()
 pm.plan.fuse_override = not general
 train = [bench.synth_device_batch(n, uv, cam, 1, dev, seed=10 + i) for i in range(2)]       # feat_agg from 2 x n training frames
@@ -55,8 +57,8 @@ else:
         pm.call(batches[i % 3], 'test', obs_override=agg)
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
-print("infer depth %d uv %d frames %d (%s plan, %d lane%s): %.4f ms / step = %.1f Mtexels/s (tape replays %d)"
-      % (depth, uv, n, 'general' if general else 'fused', lanes, 's' * (lanes > 1), 1e3 * dt, n * uv * uv / dt / 1e6, pm.plan.tape_replays))
+print("infer depth %d uv %d frames %d (%s plan, %s, %d lane%s): %.4f ms / step = %.1f Mtexels/s (tape replays %d)"
+      % (depth, uv, n, 'general' if general else 'fused', precision, lanes, 's' * (lanes > 1), 1e3 * dt, n * uv * uv / dt / 1e6, pm.plan.tape_replays))
 if not quiet:
     t = OpTimer(); pm.plan.timer = t
     for i in range(3):
