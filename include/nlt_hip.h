@@ -672,9 +672,11 @@ int nlt_back_forward(const float* x, const float* fm1, const float* skip3, int n
  *   backward-data w.r.t. input channels [lo, hi) of a forward layer reads that layer's own array as the adjoint family.
  * kind NLT_REPACK_TILE: dst = what nlt_pack_conv_tile_weights(mode, src, cin = c0, cout, tn) writes.
  * kind NLT_REPACK_WINO: dst = what nlt_pack_conv_wino_weights[_adjoint](mode, src, cin = c0, cout, tn, full, lo) writes.
+ * kind NLT_REPACK_TILE3S2: dst = what nlt_pack_conv_tile3w_s2_weights(src, cin = c0, cout) writes (bf16 terms; `total` still
+ *   counts 4-byte words of dst: half its bf16 elements).
  * first_block: exclusive prefix sum of ceil(total / 256) over the table; total_blocks = its grand total.
  */
-typedef enum { NLT_REPACK_MFMA = 0, NLT_REPACK_TILE = 1, NLT_REPACK_WINO = 2 } nlt_repack_kind;
+typedef enum { NLT_REPACK_MFMA = 0, NLT_REPACK_TILE = 1, NLT_REPACK_WINO = 2, NLT_REPACK_TILE3S2 = 3 } nlt_repack_kind;
 typedef struct {
   const float* src;
   float* dst;
@@ -970,6 +972,33 @@ int nlt_conv_tile3_forward(int mode, int nprod, const float* src, int ld, int ci
 int nlt_conv_tile3r_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
                             const unsigned short* packed, const float* bias, int cout, int tn,
                             float* out, int ldo, float* mean_out, int ldm, int act, float alpha, int max_workgroups, void* stream);
+/*
+ * Two encoder convs of the observation path in ONE launch (nprod = 6 / 9): the wave-private stride-1 conv of
+ * nlt_conv_tile3r_forward at cin = cout = 32 (4 x 16 tiles), and the NEXT level's stride-2 conv (32 -> cout2 = 64) on the wave's
+ * own results.  The stride-1 stage keeps its four MFMA column tiles by tap class (ty, tx) of the stride-2 conv -- column (y', x')
+ * of tile (ty, tx) is texel (2y' + ty, 2x' + tx) of the 4 x 16 tile -- so after bias + LeakyReLU a lane's eight values are, split
+ * into three bf16 terms in registers, its B fragment of the stride-2 K block of that tap: no cross-lane move, no LDS hand-off,
+ * no barrier.  The per-observation stride-1 map [frames * kobs, h, w, 32] is never stored.
+ *   src [frames * kobs, h, w, ld >= 32]; packed / bias: the stride-1 conv's (nlt_pack_conv_tile3_weights, tn = 32);
+ *   mean_out (may be NULL) [frames, h, w, ldm]: the mean over the kobs observations, bit-identical to what
+ *     nlt_conv_tile3r_forward writes (per output element the same additions in the same order);
+ *   packed2 = nlt_pack_conv_tile3w_s2_weights (nlt_conv_tile3w_s2_packed_elems() bf16 elements), bias2 [cout2];
+ *   out2 [frames * kobs, h / 2, w / 2, ldo2 >= cout2] = act2(conv_k2s2(act(conv_k2s1(src)))): every term product exact, fp32
+ *     accumulation (taps in order, small terms first).
+ *   `out` must be NULL: a caller that wants the stride-1 map launches the two convs.  max_workgroups as nlt_conv_tile3r_forward.
+ * NLT_ERR_UNSUPPORTED, nothing launched: cin != 32, cout != 32, cout2 != 64, odd h or w, out != NULL, nprod not 6 / 9.  Both
+ * weight sets and both biases stay in LDS for the workgroup's lifetime (24 KB + 48 KB + 8 wave regions of 10.5 KB + 384 B = 160128 bytes of the CU's 163840).
+ *   replaces: the Conv2D + LeakyReLU (+ tf.reduce_mean) lines of nlt_conv_tile_forward for level l's stride-1 observation conv
+ *             AND level l + 1's stride-2 observation conv (nlt/models/nlt.py:166-174), inference only.
+ */
+long nlt_conv_tile3w_s2_packed_elems(int cin2, int cout2);
+int nlt_pack_conv_tile3w_s2_weights(const float* w_keras, int cin2, int cout2, unsigned short* packed, void* stream);
+long nlt_conv_tile3w_s2_lds_bytes(int cin, int cout, int cout2);
+int nlt_conv_tile3w_s2_forward(int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                               const unsigned short* packed, const float* bias, int cout, float* out, int ldo,
+                               float* mean_out, int ldm, int act, float alpha,
+                               const unsigned short* packed2, const float* bias2, int cout2, float* out2, int ldo2,
+                               int act2, float alpha2, int max_workgroups, void* stream);
 
 /* ======================= bf16 channel mix (csrc/chmix_bf16.hip) =======================
  * 1x1 conv with bf16 activations / weights and fp32 accumulation on v_mfma_f32_16x16x32_bf16: the literal dense GEMM

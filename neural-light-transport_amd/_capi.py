@@ -140,6 +140,11 @@ SIGNATURES = {
                                         _vp, _c_int, _vp, _c_int, _c_int, _c_float, _vp]),
     'nlt_conv_tile3r_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int,
                                          _vp, _c_int, _vp, _c_int, _c_int, _c_float, _c_int, _vp]),
+    'nlt_conv_tile3w_s2_packed_elems': (_c_long, [_c_int] * 2),
+    'nlt_pack_conv_tile3w_s2_weights': (_c_int, [_vp, _c_int, _c_int, _vp, _vp]),
+    'nlt_conv_tile3w_s2_lds_bytes': (_c_long, [_c_int] * 3),
+    'nlt_conv_tile3w_s2_forward': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _vp, _c_int,
+                                            _vp, _c_int, _c_int, _c_float, _vp, _vp, _c_int, _vp, _c_int, _c_int, _c_float, _c_int, _vp]),
     'nlt_conv_bf16_packed_elems': (_c_long, [_c_int] * 4),
     'nlt_conv_bf16_pack': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_conv_bf16_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int,
@@ -1036,7 +1041,7 @@ def conv_backward_data(adj_mode, dpre, cpre, ldp, n, h, w, w_packed, zero_bias, 
 
 
 # ---------------------------------------------------------------- one-launch refresh of all packed weights
-REPACK_MFMA, REPACK_TILE, REPACK_WINO = 0, 1, 2
+REPACK_MFMA, REPACK_TILE, REPACK_WINO, REPACK_TILE3S2 = 0, 1, 2, 3
 REPACK_FIELDS = [('src', 'u8'), ('dst', 'u8'), ('total', 'i8'), ('first_block', 'i8'), ('kind', 'i4'), ('mode', 'i4'),
                  ('c0', 'i4'), ('c1', 'i4'), ('cout', 'i4'), ('tn', 'i4'), ('lo', 'i4'), ('full', 'i4')]   # = nlt_repack_desc
 
@@ -1048,11 +1053,12 @@ def repack_table(entries, device):
     tab = np.zeros(len(entries), dtype=np.dtype(REPACK_FIELDS))
     blocks = 0
     for i, e in enumerate(entries):
-        if e['dst'].numel() % 4 or e['dst'].data_ptr() % 16:          # (the refresh launch stores quads)
+        nbytes = e['dst'].numel() * e['dst'].element_size()           # (bf16 term buffers count in 4-byte words like the rest)
+        if nbytes % 16 or e['dst'].data_ptr() % 16:                    # (the refresh launch stores quads)
             raise NLTError("repack_table: a packed buffer must be 16-byte aligned and a multiple of 4 floats long")
-        tab[i] = (e['src'].data_ptr(), e['dst'].data_ptr(), e['dst'].numel(), blocks, e['kind'], e['mode'], e['c0'], e['c1'],
+        tab[i] = (e['src'].data_ptr(), e['dst'].data_ptr(), nbytes // 4, blocks, e['kind'], e['mode'], e['c0'], e['c1'],
                   e['cout'], e['tn'], e['lo'], e['full'])
-        blocks += (e['dst'].numel() + 255) // 256
+        blocks += (nbytes // 4 + 255) // 256
     return torch.from_numpy(tab.view(np.uint8)).to(device), len(entries), blocks
 
 
@@ -1165,6 +1171,29 @@ def conv_tile3r_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, co
     """conv_tile3_forward by persistent workgroups with the group's split weights resident in LDS: the same bits."""
     _call('nlt_conv_tile3r_forward', mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
           _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), max_workgroups)
+
+
+def pack_conv_tile3w_s2_weights(w_keras, cin2, cout2):
+    """Three-term bf16 fragments of a stride-2 k2 kernel in the channel order the stride-1 stage of conv_tile3w_s2_forward hands
+    its results over in (csrc/pack_common.h: nlt_tile3s2_fragment)."""
+    return _pack('nlt_conv_tile3w_s2_packed_elems', (cin2, cout2),
+                 'nlt_pack_conv_tile3w_s2_weights', (_ptr(_dense(w_keras, 'w_keras')), cin2, cout2), torch.int16, w_keras.device)
+
+
+def conv_tile3w_s2_plan(cin, cout, cout2):
+    """LDS bytes of a workgroup of conv_tile3w_s2_forward (both weight sets + 8 wave regions), or None where it refuses."""
+    n = lib().nlt_conv_tile3w_s2_lds_bytes(cin, cout, cout2)          # (a query: no stream)
+    return n if n > 0 else None
+
+
+def conv_tile3w_s2_forward(src, ld, cin, frames, kobs, h, w, packed, bias, cout, mean_out, ldm, packed2, bias2, cout2, out2, ldo2,
+                           act=True, alpha=0.3, act2=True, alpha2=0.3, nprod=6, max_workgroups=0, out=None, ldo=0):
+    """The wave-private stride-1 conv (32 -> 32) and the next level's stride-2 conv (32 -> 64) per observation in one launch:
+    mean_out as conv_tile3r_forward's (the same bits), out2 [frames * kobs, h / 2, w / 2, ldo2]; the stride-1 map itself is not
+    stored (`out` must stay None: the entry point refuses it)."""
+    _call('nlt_conv_tile3w_s2_forward', nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout,
+          _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), packed2.data_ptr(), _ptr(bias2), cout2,
+          _ptr(out2), ldo2, 1 if act2 else 0, float(alpha2), max_workgroups)
 
 
 def conv_bf16_pack(mode, w_keras, c0, c1, cout):

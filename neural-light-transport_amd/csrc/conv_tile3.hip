@@ -792,6 +792,268 @@ int launch3(const Tile3P& p, int nprod, hipStream_t s, int resident_wg) {
   return launch3k<MODE, TNT, 1>(p, nprod, s, resident_wg);
 }
 
+// LEVEL HAND-OFF: conv_tile3w_kernel<4, NPROD> at cin = cout = 32, plus the next level's stride-2 conv (32 -> 64, one K block of
+// 32 per tap) per observation on the wave's own results, so the per-observation stride-1 map is never stored or read back.
+// The stride-1 stage keeps its four MFMA column tiles by TAP CLASS (ty, tx) of the stride-2 conv instead of by output row:
+// column j' = (y', x') = (j >> 3, j & 7) of tile (ty, tx) is texel (2y' + ty, 2x' + tx) of the wave's 4 x 16 tile, i.e. the
+// input that output texel j' of the wave's 2 x 8 stride-2 tile reads through tap (ty, tx).  The D layout gives lane (kk, j')
+// channels 4kk..4kk+3 of both 16-channel column tiles of that texel; the stride-2 weights are packed with exactly that channel
+// order inside a K octet (nlt_tile3s2_fragment), so after bias + LeakyReLU the lane's eight values, split in registers, ARE its B
+// fragment: no cross-lane move, no LDS hand-off region, no barrier.  Per output element of the stride-1 conv nothing changes
+// (slabs in order, tap pairs in order, ORDER9, bias, LeakyReLU, mean): only the order in which a wave visits its texels does.
+// The haloed 5 x 17 planes are stored by x parity, rows 20 slots apart (S2_PITCH): a B read takes columns 2x' + tx + b of rows
+// r and r + 2 -- 8 consecutive slots of one parity, twice, 40 = 8 (mod 16) slots apart: 16 different slots mod 16 for every
+// 16 lanes that share a b (and the plane stride is 0 mod 16, so the two channel halves of a lane group pair do not matter).
+constexpr int S2_PITCH = 20, S2_ODD = 9, S2_PLW = 112;                  // row pitch; first odd-x slot of a row; slots per plane (97 used)
+constexpr int S2_A1 = 2 * 2 * 2 * 3 * 64, S2_A2 = 4 * 4 * 3 * 64;      // 16-byte slots of the stride-1 / stride-2 weights
+constexpr size_t S2_LDS = (size_t)(S2_A1 + S2_A2 + 8 * 6 * S2_PLW) * sizeof(u32x4) + 96 * sizeof(float);   // + both biases
+
+struct Tile3S2P {
+  Tile3P a;
+  const u16* packed2; const float* bias2; float* out2;
+  int ldo2, act2; float alpha2;
+};
+
+template <int NPROD>
+__global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int tiles_y) {
+  const Tile3P& p = P.a;
+  constexpr int RT = 4, CT = 2, NWV = 8, NCL = 4, NC2 = 4;
+  constexpr int UNITS = 5 * 17 * 2, NB = (UNITS + 63) / 64;
+  constexpr int A_SLOTS = S2_A1 / 2;
+  constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kk = lane >> 4, j = lane & 15, yq = j >> 3, xq = j & 7;
+  const u32x4* const A2 = tile3r_lds + S2_A1;
+  u32x4* const B = tile3r_lds + S2_A1 + S2_A2 + wave * (6 * S2_PLW);
+  float* const biasl = reinterpret_cast<float*>(tile3r_lds + S2_A1 + S2_A2 + 8 * 6 * S2_PLW);    // [32 | 64]
+  const long in_frame = (long)p.h * p.w;
+  const int oh2 = p.h >> 1, ow2 = p.w >> 1;
+  const long items = (long)p.frames * tiles_y * p.tiles_x;
+  const int rank = xcd_tile3(blockIdx.x, gridDim.x);
+  const int it0 = (int)(rank * items / gridDim.x), it1 = (int)((rank + 1) * items / gridDim.x);
+
+  // B copy units in SLOT order: unit = (slot of the haloed tile, channel half); 8 consecutive lanes write 8 consecutive slots
+  int b_lds[NB], b_hf[NB], b_row[NB], b_x[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int u = lane + 64 * i;
+    const int t = (u >> 4) * 8 + (u & 7), q = t % 17;
+    b_hf[i] = (u >> 3) & 1;
+    b_row[i] = t / 17;
+    b_x[i] = q < S2_ODD ? 2 * q : 2 * (q - S2_ODD) + 1;
+    b_st[i] = t < 5 * 17;
+    b_lds[i] = b_hf[i] * S2_PLW + b_row[i] * S2_PITCH + q;
+  }
+  int nf = 0, nty0 = 0, ntx0 = 0;
+  auto geom = [&](int t) {
+    ntx0 = (t % p.tiles_x) * TW; t /= p.tiles_x;
+    nty0 = (t % tiles_y) * RT;
+    nf = t / tiles_y;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      const int gy = nty0 + b_row[i], gx = ntx0 + b_x[i];
+      b_ok[i] = b_st[i] && gy < p.h && gx < p.w;
+      b_tex[i] = (long)gy * p.w + gx;
+    }
+  };
+  f32x4 rb[NB][2];
+  auto load_b = [&](int cc, int frame) {
+    const float* sp = p.src + (long)(nf * p.kobs + frame) * in_frame * p.ld + cc * 16;
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
+      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      rb[n][0] = b_ok[n] ? v0 : z;
+      rb[n][1] = b_ok[n] ? v1 : z;
+    }
+  };
+  auto store_b = [&]() {
+#pragma unroll
+    for (int n = 0; n < NB; ++n) {
+      if (!b_st[n]) continue;
+      unsigned hi[4], mid[4], lo[4];
+      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
+      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
+      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
+      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
+      u32x4* bb = B + b_lds[n];
+      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
+      bb[2 * S2_PLW] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
+      bb[4 * S2_PLW] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
+    }
+  };
+  auto wave_sync = [&]() {                                              // LDS written by one lane, read by another of the SAME wave
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  };
+
+  {                                                                     // both weight sets, once per workgroup
+    const u32x4* a1 = reinterpret_cast<const u32x4*>(p.packed);
+    const u32x4* a2 = reinterpret_cast<const u32x4*>(P.packed2);
+    for (int i = tid; i < S2_A1; i += 64 * NWV) tile3r_lds[i] = a1[i];
+    for (int i = tid; i < S2_A2; i += 64 * NWV) tile3r_lds[S2_A1 + i] = a2[i];
+    // (the biases too: a global load in the epilogue would sit behind the next slab's loads in the in-order wait count)
+    if (tid < 32) biasl[tid] = p.bias[tid];
+    else if (tid < 96) biasl[tid] = P.bias2[tid - 32];
+  }
+  __syncthreads();
+  int it = it0 + wave;
+  if (it >= it1) return;
+  // fragment (row set rs = ty + pair, tx) of the stride-1 stage: rows rs + 2y', columns 2x' + tx + b, b = kk >> 1
+  const int bl0 = (kk & 1) * S2_PLW + 2 * yq * S2_PITCH + xq;
+  int offx[2];
+#pragma unroll
+  for (int tx = 0; tx < 2; ++tx) {
+    const int xx = tx + (kk >> 1);
+    offx[tx] = (xx & 1) * S2_ODD + (xx >> 1);
+  }
+  f32x4 acc[NCL][CT], mean[NCL][CT];
+#pragma unroll
+  for (int c = 0; c < NCL; ++c)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) acc[c][ct] = mean[c][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  geom(it);
+  load_b(0, 0);
+  store_b();
+  wave_sync();
+  for (; it < it1; it += NWV) {
+    const int f = nf, ty0 = nty0, tx0 = ntx0;
+    const bool last_item = it + NWV >= it1;
+    for (int i = 0; i < p.kobs; ++i) {
+      for (int s = 0; s < 2; ++s) {
+        int ns = s + 1, ni = i;
+        if (ns == 2) { ns = 0; ++ni; }
+        const bool item_end = ni == p.kobs;
+        if (item_end) {
+          ni = 0;
+          if (!last_item) geom(it + NWV);
+        }
+        load_b(ns, ni);                                                 // (in flight across the MFMAs and, after the last slab, the stride-2 stage)
+        bf16x8 bt[3][6];
+#pragma unroll
+        for (int rs = 0; rs < 3; ++rs)
+#pragma unroll
+          for (int tx = 0; tx < 2; ++tx)
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+              bt[t][rs * 2 + tx] = __builtin_bit_cast(bf16x8, B[t * 2 * S2_PLW + bl0 + rs * S2_PITCH + offx[tx]]);
+        wave_sync();
+        const u32x4* A = tile3r_lds + s * A_SLOTS;
+#pragma unroll
+        for (int pl = 0; pl < 2; ++pl) {
+          bf16x8 at[3][CT];
+#pragma unroll
+          for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int t = 0; t < 3; ++t) at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * 2 + ct) * 3 + t) * 64 + lane]);
+#pragma unroll
+          for (int pi = 9 - NPROD; pi < 9; ++pi)
+#pragma unroll
+            for (int c = 0; c < NCL; ++c)
+#pragma unroll
+              for (int ct = 0; ct < CT; ++ct)
+                acc[c][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][((c >> 1) + pl) * 2 + (c & 1)],
+                                                                     acc[c][ct], 0, 0, 0);
+        }
+        if (s == 1) {
+          u32x4 bs[3][NCL];                                             // the stride-2 conv's B fragments: tap class c, three terms
+#pragma unroll
+          for (int c = 0; c < NCL; ++c) {
+            const int gy = ty0 + 2 * yq + (c >> 1), gx = tx0 + 2 * xq + (c & 1);
+            f32x4 v2[CT];
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+              const int oc = ct * 16 + 4 * kk;
+              f32x4 v = acc[c][ct] + *reinterpret_cast<const f32x4*>(biasl + oc);
+              if (p.act) {
+#pragma unroll
+                for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
+              }
+              acc[c][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+              mean[c][ct] += v;
+              if (p.mean_out && i == p.kobs - 1 && gy < p.oh && gx < p.ow) {
+                const long mt = ((long)f * p.oh + gy) * p.ow + gx;
+                *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[c][ct] * (1.f / (float)p.kobs);
+              }
+              if (i == p.kobs - 1) mean[c][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+              v2[ct] = v;
+            }
+            unsigned hi[4], mid[4], lo[4];
+            split2(v2[0][0], v2[0][1], hi[0], mid[0], lo[0]);
+            split2(v2[0][2], v2[0][3], hi[1], mid[1], lo[1]);
+            split2(v2[1][0], v2[1][1], hi[2], mid[2], lo[2]);
+            split2(v2[1][2], v2[1][3], hi[3], mid[3], lo[3]);
+            bs[0][c] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
+            bs[1][c] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
+            bs[2][c] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
+          }
+          f32x4 acc2[NC2];
+#pragma unroll
+          for (int c2 = 0; c2 < NC2; ++c2) acc2[c2] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int c = 0; c < NCL; ++c) {                               // K block = tap (ty, tx) = c
+#pragma unroll
+            for (int ch = 0; ch < NC2; ch += 2) {                       // two column tiles at a time: 24 registers of A fragments
+              bf16x8 a2[3][2];
+#pragma unroll
+              for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+                for (int t = 0; t < 3; ++t) a2[t][c2] = __builtin_bit_cast(bf16x8, A2[((c * NC2 + ch + c2) * 3 + t) * 64 + lane]);
+#pragma unroll
+              for (int pi = 9 - NPROD; pi < 9; ++pi)
+#pragma unroll
+                for (int c2 = 0; c2 < 2; ++c2)
+                  acc2[ch + c2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[ORDER9[pi][0]][c2], __builtin_bit_cast(bf16x8, bs[ORDER9[pi][1]][c]),
+                                                                          acc2[ch + c2], 0, 0, 0);
+            }
+          }
+          const int oy = (ty0 >> 1) + yq, ox = (tx0 >> 1) + xq;
+          if (oy < oh2 && ox < ow2) {
+            const long ot = ((long)(f * p.kobs + i) * oh2 + oy) * ow2 + ox;
+#pragma unroll
+            for (int c2 = 0; c2 < NC2; ++c2) {
+              const int oc = c2 * 16 + 4 * kk;
+              f32x4 v = acc2[c2] + *reinterpret_cast<const f32x4*>(biasl + 32 + oc);
+              if (P.act2) {
+#pragma unroll
+                for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : P.alpha2 * v[c4];
+              }
+              *reinterpret_cast<f32x4*>(P.out2 + ot * P.ldo2 + oc) = v;
+            }
+          }
+        }
+        if (!(item_end && last_item)) store_b();
+        wave_sync();
+      }
+    }
+  }
+}
+
+int launch3w_s2(const Tile3S2P& P, int nprod, int max_wg, hipStream_t s) {
+  if (S2_LDS > TILE3R_LDS_CU) return NLT_ERR_UNSUPPORTED;
+  const int cus = tile3r_cus();
+  if (cus <= 0) return NLT_ERR_LAUNCH;
+  const int tiles_y = (P.a.oh + 3) / 4;
+  const long items = (long)P.a.frames * tiles_y * P.a.tiles_x;
+  if (items >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  long nwg = cus;
+  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
+  if (nwg > items) nwg = items;
+  auto* k = nprod == 9 ? conv_tile3w_s2_kernel<9> : conv_tile3w_s2_kernel<6>;
+  static size_t done[2][8] = {};
+  if (tile3r_allow_lds(reinterpret_cast<const void*>(k), S2_LDS, done[nprod == 9]) != NLT_OK) return NLT_ERR_LAUNCH;
+  hipLaunchKernelGGL(k, dim3((unsigned)nwg), dim3(512), S2_LDS, s, P, tiles_y);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+__global__ void pack_tile3s2_kernel(const float* __restrict__ wk, int cin, int cout, long total, u16* __restrict__ wp) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < total) wp[idx] = nlt_tile3s2_fragment(wk, idx, cin, cout);
+}
+
 }  // namespace
 
 extern "C" long nlt_conv_tile3_packed_elems(int mode, int cin, int cout, int tn) {
@@ -848,4 +1110,46 @@ extern "C" int nlt_conv_tile3r_forward(int mode, int nprod, const float* src, in
   if (max_workgroups < 0) return NLT_ERR_BAD_ARG;
   return tile3_forward(mode, nprod, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm, act, alpha,
                        max_workgroups, stream);
+}
+
+extern "C" long nlt_conv_tile3w_s2_packed_elems(int cin2, int cout2) {
+  return (cin2 == 32 && cout2 == 64) ? (long)12 * cin2 * cout2 : -1;   // 4 taps x 3 terms
+}
+
+extern "C" int nlt_pack_conv_tile3w_s2_weights(const float* w_keras, int cin2, int cout2, unsigned short* packed, void* stream) {
+  const long total = nlt_conv_tile3w_s2_packed_elems(cin2, cout2);
+  if (total <= 0) return NLT_ERR_UNSUPPORTED;
+  if (!w_keras || !packed || !nlt_aligned16(packed)) return NLT_ERR_BAD_ARG;
+  hipLaunchKernelGGL(pack_tile3s2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     w_keras, cin2, cout2, total, packed);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+// LDS bytes of a workgroup (both weight sets + 8 wave regions), or -1 where the kernel does not exist
+extern "C" long nlt_conv_tile3w_s2_lds_bytes(int cin, int cout, int cout2) {
+  return (cin == 32 && cout == 32 && cout2 == 64 && S2_LDS <= TILE3R_LDS_CU) ? (long)S2_LDS : -1;
+}
+
+extern "C" int nlt_conv_tile3w_s2_forward(int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                                          const unsigned short* packed, const float* bias, int cout, float* out, int ldo,
+                                          float* mean_out, int ldm, int act, float alpha,
+                                          const unsigned short* packed2, const float* bias2, int cout2, float* out2, int ldo2,
+                                          int act2, float alpha2, int max_workgroups, void* stream) {
+  if (!src || !packed || !bias || !packed2 || !bias2 || !out2 || max_workgroups < 0) return NLT_ERR_BAD_ARG;
+  if (frames <= 0 || kobs <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cout2 <= 0) return NLT_ERR_BAD_ARG;
+  if (nlt_conv_tile3w_s2_lds_bytes(cin, cout, cout2) <= 0 || (nprod != 6 && nprod != 9) || ((h | w) & 1) || out)
+    return NLT_ERR_UNSUPPORTED;
+  if (ld < cin || (ld & 3) || ldo2 < cout2 || (ldo2 & 3) || (mean_out && (ldm < cout || (ldm & 3)))) return NLT_ERR_BAD_ARG;
+  if (!nlt_aligned16(src) || !nlt_aligned16(packed) || !nlt_aligned16(bias) || !nlt_aligned16(packed2) || !nlt_aligned16(bias2) ||
+      !nlt_aligned16(out2) || (mean_out && !nlt_aligned16(mean_out))) return NLT_ERR_BAD_ARG;
+  if ((long long)frames * kobs * h * w * (long long)(ld > ldo2 ? ld : ldo2) >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+  Tile3S2P P;
+  Tile3P& p = P.a;
+  p.src = src; p.packed = packed; p.bias = bias; p.out = nullptr; p.mean_out = mean_out;
+  p.ld = ld; p.cin = cin; p.frames = frames; p.kobs = kobs; p.h = h; p.w = w;
+  p.oh = h; p.ow = w; p.cout = cout; p.ldo = ldo; p.ldm = ldm; p.ncc = cin / 16; p.act = act; p.alpha = alpha;
+  p.tiles_y = (h + TH - 1) / TH; p.tiles_x = (w + TW - 1) / TW;
+  P.packed2 = packed2; P.bias2 = bias2; P.out2 = out2; P.ldo2 = ldo2; P.act2 = act2; P.alpha2 = alpha2;
+  return launch3w_s2(P, nprod, max_workgroups, static_cast<hipStream_t>(stream));
 }

@@ -73,6 +73,41 @@ __device__ __forceinline__ float nlt_tile_fragment_d2(const float* __restrict__ 
   return wk[((long)ab * full + lo + o) * cin + c];
 }
 
+// bf16 bit patterns (round to nearest even) for the three-term split of an fp32 weight: w = hi + mid + lo exactly
+__host__ __device__ inline unsigned short nlt_bf16_rne_bits(float f) {
+  union { float f; unsigned u; } x; x.f = f;
+  x.u += 0x7fffu + ((x.u >> 16) & 1u);
+  return (unsigned short)(x.u >> 16);
+}
+__host__ __device__ inline float nlt_bf16_bits_float(unsigned short b) {
+  union { float f; unsigned u; } x; x.u = (unsigned)b << 16;
+  return x.f;
+}
+__host__ __device__ inline unsigned short nlt_bf16_term(float v, int term) {
+  const unsigned short hi = nlt_bf16_rne_bits(v);
+  const float r1 = v - nlt_bf16_bits_float(hi);
+  const unsigned short mid = nlt_bf16_rne_bits(r1);
+  const float r2 = r1 - nlt_bf16_bits_float(mid);
+  return term == 0 ? hi : (term == 1 ? mid : nlt_bf16_rne_bits(r2));
+}
+
+// Stride-2 conv fed from the registers of the stride-1 conv before it (conv_tile3.hip, conv_tile3w_s2_kernel):
+// [tap 4][ct = cout / 16][term 3][lane 64][e 8] bf16 of a Keras (2,2,cin = 32,cout) array.  A K block is one tap; lane group
+// kk = lane >> 4 holds the K octet the D fragments of the stride-1 stage hand it: channels 4kk..4kk+3 (e < 4, the column tile of
+// channels 0-15) and 16+4kk..16+4kk+3 (e >= 4, the column tile of channels 16-31).
+__host__ __device__ inline int nlt_tile3s2_channel(int kk, int e) { return (e < 4 ? 0 : 12) + 4 * kk + e; }
+__device__ __forceinline__ unsigned short nlt_tile3s2_fragment(const float* __restrict__ wk, long idx, int cin, int cout) {
+  const int e = idx & 7, lane = (idx >> 3) & 63;
+  long r = idx >> 9;
+  const int term = r % 3; r /= 3;
+  const int nct = cout >> 4;
+  const int ct = r % nct;
+  const int t = r / nct;
+  const int c = nlt_tile3s2_channel(lane >> 4, e);
+  const int o = ct * 16 + (lane & 15);
+  return nlt_bf16_term(wk[((long)t * cin + c) * cout + o], term);
+}
+
 // Winograd F(2x2, 2x2) kernel (conv_wino.hip): [g = N / TN][c8 = K / 8][position 9 = (xi, nu)][ct TNT][channel quad 2][column 16][e 4]
 // = U = G g G^T of the executed correlation's 2 x 2 taps g, G = [1 0; 1 1; 0 1]: position (xi, nu) sums the taps (a, b) with
 // a in {0} / {0, 1} / {1} for xi = 0 / 1 / 2 and b likewise for nu.  `transposed` (the Conv2DTranspose k2s1 family: a forward

@@ -31,7 +31,14 @@ __global__ __launch_bounds__(64) void repack_all_kernel(const nlt_repack_desc* _
   const long idx = ((long)blockIdx.x - e.first_block) * 256 + threadIdx.x * 4;
   if (idx >= e.total) return;                                          // (totals are multiples of 256)
   f32x4 v;
-  if (e.kind == NLT_REPACK_WINO) {
+  if (e.kind == NLT_REPACK_TILE3S2) {                                  // bf16 terms: a quad of floats = the 8 elements of one (lane, term) slot
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned a = nlt_tile3s2_fragment(e.src, 2 * (idx + j), e.c0, e.cout);
+      const unsigned b = nlt_tile3s2_fragment(e.src, 2 * (idx + j) + 1, e.c0, e.cout);
+      v[j] = __uint_as_float(a | (b << 16));
+    }
+  } else if (e.kind == NLT_REPACK_WINO) {
     const bool tr = e.mode == NLT_DECONV_K2S1;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = nlt_wino_fragment(e.src, idx + j, e.c0, e.cout, e.tn >> 4, e.full, e.lo, tr);

@@ -72,8 +72,14 @@ EXCLUSIVE = ('lds', 'wino', 'c32')      # one encoder launch goes to at most one
 def hint_word(hint):
     """(tn, unfold, resident) of an `lds_hints` / `wino_hints` value: the output channels per workgroup (32 / 64) in the low byte;
     +256: the observations run as separate frames and their mean in a launch of its own; +512: csrc/conv_tile3.hip's resident
-    form, its split weights kept in LDS (lds only)."""
+    form, its split weights kept in LDS (lds only); +1024 (`FOLD_S2`, with +512, inference plans only): the stride-1 observation
+    conv also runs the NEXT level's stride-2 observation conv on its own results (conv_tile3w_s2_kernel), which is then not
+    launched and whose input map is never stored."""
     return hint & 255, bool(hint & 256), bool(hint & 512)
+
+
+FOLD_S2 = 1024
+FOLD_HINT = FOLD_S2 + 512 + 32          # the one hint the level hand-off kernel runs under
 
 
 class RenderPlan(OverrideMixin):
@@ -139,6 +145,8 @@ class RenderPlan(OverrideMixin):
         self.use_wino = os.environ.get('NLT_WINO', '1') != '0'
         # narrow stride-1 convs (cin 16 | 32 -> 32) with LDS-resident weights, a frame per stage (csrc/conv_c32.hip)
         self.use_c32 = os.environ.get('NLT_C32', '1') != '0'
+        # f32x3 inference: level l's stride-1 observation conv + level l + 1's stride-2 one as ONE launch where the trials find it faster
+        self.fold_s2 = os.environ.get('NLT_FOLD_S2', '1') != '0'
         self.alias_obs = os.environ.get('NLT_ALIAS_OBS', '1') != '0'   # k = 1 inference: observation features live in fm[l]'s second half
         is_c = net_query.is_contracting
         self.n_down = sum(is_c) - 1                      # contracting Sequential blocks
@@ -337,8 +345,32 @@ class RenderPlan(OverrideMixin):
                      *extra, **_act_kw(act), tile_hint=0 if self._trial is not None else self.tile_hints.get('bf.' + label, 0),
                      flops=_gemm(layer.mode, n, h, w, c0 + c1, layer.n_ch_out)[2], moved=moved)
 
+    def _fold_ok(self, layer, cin, nxt):
+        """Does the level hand-off kernel exist for this stride-1 conv and the next level's stride-2 conv `nxt`?  (Plans on the
+        GPU only.)"""
+        return (self.fold_s2 and self.precision in ('f32x3', 'f32x3_9') and layer.kernel.is_cuda and layer.mode == C.CONV_K2S1
+                and nxt.mode == C.CONV_K2S2 and C.conv_tile3w_s2_plan(cin, layer.n_ch_out, nxt.n_ch_out) is not None)
+
+    def _conv_fold(self, label, layer, act, src, cin, ld, frames, kobs, h, w, mean_out, ldm, fold):
+        """`label`'s stride-1 observation conv and the next level's stride-2 one (fold = (label, layer, act, out, ldo) of that
+        launch) as one launch under `label`; the timer's figures are the sums of both launches', the bytes it must move are its
+        input, the mean and the stride-2 output -- the per-observation stride-1 map does not exist."""
+        label2, nxt, act2, out2, ldo2 = fold
+        nxt.build(layer.n_ch_out, src.device)
+        nf, c, c2 = frames * kobs, layer.n_ch_out, nxt.n_ch_out
+        nbytes = 4 * (nf * h * w * cin + nf * h * w * c) + 4 * frames * h * w * c * (kobs + 1)       # as `_enc_launch` counts label
+        nbytes += 4 * (nf * h * w * c + nf * (h // 2) * (w // 2) * c2)                                # ... and label2
+        moved = 4 * (nf * h * w * cin + (frames * h * w * c if mean_out is not None else 0) + nf * (h // 2) * (w // 2) * c2)
+        self._ran.add((label, 'lds'))
+        self._launch(label, nbytes, C.conv_tile3w_s2_forward, src, ld, cin, frames, kobs, h, w, layer.packed_tile3(32),
+                     layer.bias.detach(), c, mean_out, ldm, nxt.packed_tile3s2(), nxt.bias.detach(), c2, out2, ldo2,
+                     act=act is not None, alpha=act.alpha if act is not None else 0.0,
+                     act2=act2 is not None, alpha2=act2.alpha if act2 is not None else 0.0,
+                     nprod=9 if self.precision == 'f32x3_9' else 6,
+                     flops=2 * nf * h * w * 4 * cin * c + 2 * nf * (h // 2) * (w // 2) * 4 * c * c2, moved=moved)
+
     def _conv_enc(self, label, layer, act, src, cin, ld, frames, kobs, h, w, out, ldo, algo, mean_out=None, ldm=0,
-                  obs_weights=None):
+                  obs_weights=None, fold=None):
         """One encoder conv (single source) over frames*kobs frames; with mean_out also the mean over the kobs
         observations (label + '.mean' when it needs its own launch).  Goes to the kernel family the plan (or the running
         trial) chose for this launch -- narrow-level, Winograd, LDS-tiled, in that order -- else to the register-tiled MFMA /
@@ -353,9 +385,19 @@ class RenderPlan(OverrideMixin):
             return
         if (algo == C.ALGO_AUTO and layer.mode == C.CONV_K2S1 and self._hint('wino', label) and self._wino(*conv, obs_weights)):
             return
-        tn, unfold, resident = hint_word(self._hint('lds', label))
+        hint = self._hint('lds', label)
+        tn, unfold, resident = hint_word(hint)
         ok = (tn and obs_weights is None and algo == C.ALGO_AUTO and layer.mode in (C.CONV_K2S2, C.CONV_K2S1)
               and layer.cin == cin and cin % 16 == 0 and layer.n_ch_out % tn == 0)
+        if hint & FOLD_S2:
+            # the level hand-off: only where the caller offers the next level's stride-2 conv (an inference plan that keeps no
+            # per-observation map of this level) and the kernel takes the pair; True tells the caller not to launch that conv
+            if ok and fold is not None and hint == FOLD_HINT and ((h | w) & 1) == 0 and self._fold_ok(layer, cin, fold[1]):
+                if mean_out is None and kobs == 1:
+                    mean_out, ldm = out, ldo                    # one observation per frame: its features ARE the mean
+                self._conv_fold(label, layer, act, src, cin, ld, frames, kobs, h, w, mean_out, ldm, fold)
+                return True
+            ok = ok and not trial                               # a trial leaves the launch to the others; a plan runs the two convs
         if ok and resident and (self.precision not in ('f32x3', 'f32x3_9') or C.conv_tile3r_plan(layer.mode, cin, tn) is None):
             ok = not trial                              # the resident form refuses this launch: a trial leaves it to the others,
             resident = False                            # a plan takes the streaming kernel
@@ -399,6 +441,8 @@ class RenderPlan(OverrideMixin):
             trials += [('lds', 32), ('lds', 64), ('lds', 256 + 32), ('lds', 256 + 64)]
             if self.precision in ('f32x3', 'f32x3_9'):
                 trials += [('lds', 512 + 32), ('lds', 512 + 64)]    # the three-term split with its weights resident in LDS
+                if self.fold_s2 and self._fold_trial():
+                    trials.append(('lds', FOLD_HINT))               # ... and the next level's stride-2 conv on the same launch
         elif self.tile_dgrad:
             trials += [('lds', 32), ('lds', 64)]                  # backward-data launches on the LDS-tiled kernel
         if self.use_c32 and not backward:
@@ -432,10 +476,20 @@ class RenderPlan(OverrideMixin):
                         results.setdefault(label, []).append((t, kind, hint))
         finally:
             self._trial, self.timer, self._tuning = None, saved_timer, False
+        # The level hand-off replaces TWO launches: it is held against the sum of the best of each, and where it wins it takes
+        # the stride-1 label first (`set_choice`: the first winner keeps a label).  The stride-2 label keeps its own choice for
+        # the plans that still launch it (training, obs_override, layer by layer).
+        for label, res in results.items():
+            t_fold = [t for t, kind, hint in res if kind == 'lds' and hint == FOLD_HINT]
+            label2 = self._fold_partner(label)
+            if t_fold and not backward and label2 in results:
+                rest = [r for r in res if not (r[1] == 'lds' and r[2] == FOLD_HINT)]
+                if rest and min(t_fold) < min(rest)[0] + min(results[label2])[0]:
+                    self.set_choice(label, 'lds', FOLD_HINT)
         for label, res in results.items():
             if '.s1' not in label and '.s2' not in label and label != 'L0.q':
                 continue
-            _, kind, hint = min(res)
+            _, kind, hint = min(r for r in res if not (r[1] == 'lds' and r[2] == FOLD_HINT))
             if backward and 'dgrad' not in label:
                 continue                                            # (a backward trial pass only chooses backward-data launches)
             self.set_choice(label, kind, hint)
@@ -444,6 +498,19 @@ class RenderPlan(OverrideMixin):
         reg = getattr(self.q.layers[0], '_registry', None)
         if reg is not None and self.prune_packs:
             reg.begin_census()              # which of the candidates' fragment buffers does the chosen plan read?
+
+    def _fold_trial(self):
+        """Is the level hand-off kernel a candidate of this plan's trials at all?  (Its launches exist on the GPU only.)"""
+        k = getattr(self.q.layers[0], 'kernel', None)
+        return k is not None and k.is_cuda
+
+    @staticmethod
+    def _fold_partner(label):
+        """'L<l>.o.s1' -> 'L<l+1>.o.s2', the launch the level hand-off absorbs (None for any other label)."""
+        parts = label.split('.')
+        if len(parts) != 3 or parts[1:] != ['o', 's1'] or not parts[0][1:].isdigit():
+            return None
+        return 'L%d.o.s2' % (int(parts[0][1:]) + 1)
 
     def _drop_tapes(self):
         for b in self._bufs.values():
@@ -794,11 +861,18 @@ class RenderPlan(OverrideMixin):
         hh, ww = h // 2, w // 2
         bf = self.precision == 'bf16' and not train
         alias_obs = k == 1 and not train and not bf and self.alias_obs
+        folded = [False]                                            # did the previous level's stride-1 launch run this level's o.s2?
         for l in range(2, D + 1):
             (qa, qact_a), (qb, qact_b) = q.layers[l].convs()
             (oa, oact_a), (ob, oact_b) = o.layers[l].convs()
             cin = 2 * cl[l - 1]
             s2_done = front2 and l == 2                             # the front kernel already wrote qtmp[2] / otmp[2]
+            o_s2_done = s2_done or folded[0]                        # ... or level l - 1's stride-1 launch wrote otmp[l]
+            # inference: this level's stride-1 observation launch may take level l + 1's stride-2 one along (FOLD_S2)
+            fold = None
+            if not train and not bf and l < D:
+                na, nact = o.layers[l + 1].convs()[0]
+                fold = ('L%d.o.s2' % (l + 1), na, nact, b['otmp'][l + 1], cl[l + 1])
             c = cl[l]
             h2_, w2_ = hh // 2, ww // 2
 
@@ -814,18 +888,19 @@ class RenderPlan(OverrideMixin):
                     # ONE observation per frame, inference: the level's observation features ARE its "mean" -- the stride-1 conv
                     # writes them straight into the second half of the interleaved map and the next level reads them there
                     # (no obs[l] buffer traffic, no mean launch: one launch per level off the chain of the released shapes)
-                    if not s2_done:
+                    if not o_s2_done:
                         if l > 2:
                             self._conv_enc('L%d.o.s2' % l, oa, oact_a, b['fm'][l - 1].view(-1)[cl[l - 1]:], cl[l - 1], 2 * cl[l - 1],
                                            n, 1, hh, ww, b['otmp'][l], c, algo)
                         else:
                             self._conv_enc('L%d.o.s2' % l, oa, oact_a, b['obs'][1], cl[1], cl[1], n, 1, hh, ww, b['otmp'][l], c, algo)
-                    self._conv_enc('L%d.o.s1' % l, ob, oact_b, b['otmp'][l], c, c, n, 1, h2_, w2_, b['fm'][l].view(-1)[c:], 2 * c, algo)
+                    folded[0] = bool(self._conv_enc('L%d.o.s1' % l, ob, oact_b, b['otmp'][l], c, c, n, 1, h2_, w2_,
+                                                    b['fm'][l].view(-1)[c:], 2 * c, algo, fold=fold))
                     return
-                if not s2_done:
+                if not o_s2_done:
                     self._conv_enc('L%d.o.s2' % l, oa, oact_a, b['obs'][l - 1], cl[l - 1], cl[l - 1], n, k, hh, ww, b['otmp'][l], c, algo)
-                self._conv_enc('L%d.o.s1' % l, ob, oact_b, b['otmp'][l], c, c, n, k, h2_, w2_, b['obs'][l], c, algo,
-                               mean_out=b['fm'][l].view(-1)[c:], ldm=2 * c)
+                folded[0] = bool(self._conv_enc('L%d.o.s1' % l, ob, oact_b, b['otmp'][l], c, c, n, k, h2_, w2_, b['obs'][l], c, algo,
+                                                mean_out=b['fm'][l].view(-1)[c:], ldm=2 * c, fold=fold))
 
             def query_path():
                 if bf and l >= 3:

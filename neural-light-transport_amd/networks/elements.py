@@ -186,6 +186,14 @@ class Conv2D(Layer):
             ent = cache[tn] = (ver, C.pack_conv_tile3_weights(self.mode, self.kernel.detach(), self.cin, self.n_ch_out, tn))
         return ent[1]
 
+    def packed_tile3s2(self):
+        """Three-term bf16 fragments of a stride-2 k2 kernel (32 -> 64) in the channel order csrc/conv_tile3.hip's level hand-off
+        kernel receives the previous level's stride-1 results in.  A derived buffer like the rest: part of the one-launch
+        PackRegistry refresh, inactive under the census while no plan asks for it."""
+        return self._cached_pack(('tile3s2',), lambda: C.pack_conv_tile3w_s2_weights(self.kernel.detach(), self.cin, self.n_ch_out),
+                                 dict(kind=C.REPACK_TILE3S2, mode=self.mode, c0=self.cin, c1=0, cout=self.n_ch_out, tn=0, lo=0,
+                                      full=self.n_ch_out))
+
     ADJOINT = {C.CONV_K2S2: C.DECONV_K2S2, C.CONV_K2S1: C.DECONV_K2S1,
                C.DECONV_K2S2: C.CONV_K2S2, C.DECONV_K2S1: C.CONV_K2S1,
                C.CONV_K3S2: C.DECONV_K3S2, C.CONV_K3S1: C.DECONV_K3S1,
