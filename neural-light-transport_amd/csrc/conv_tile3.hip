@@ -17,6 +17,17 @@
 //     2-4 taps x TN output channels), into three planes [term][channel half][texel slot][8 bf16]; plane strides are multiples
 //     of 16 slots, so the 16 lanes a ds_read_b128 services together (4 + 4 + 8 lanes of two lane groups) hit 16 different slots;
 //   * the weights are split at pack time (nlt_pack_conv_tile3_weights): [g][cc][tap pair][ct][term][lane][8 bf16].
+//
+// Layout of this file: the STAGE PIECES, each defined once -- gather_unit (two 16-byte loads of a copy unit), split8 /
+// split_store_unit (the three terms, and their LDS stores), read_a (A fragments), ORDER9 + term_products (the MFMAs of a K block),
+// bias_act + epilogue (bias, LeakyReLU, out, observation mean), unit_slot / unit_source / stage_products (the shared 8 x 16 stage),
+// wave_sync -- and FOUR SCHEDULES around them, which differ only in who stages what, when, and between which barriers:
+//   conv_tile3_kernel      streaming: a tile per workgroup, weights and texels through the double-buffered stage;
+//   conv_tile3r_kernel     resident, shared stage: persistent workgroups, a group's weights stay in LDS;
+//   conv_tile3w_kernel     resident, wave-private: every wave stages its own RT x 16 tile, no workgroup barrier;
+//   conv_tile3w_s2_kernel  level hand-off: the wave-private schedule by tap class + the next level's stride-2 conv in registers.
+// Per output element all four issue the same floating-point operations in the same order because they call the same pieces:
+// slabs in order, tap pairs in order, ORDER9, bias, LeakyReLU, mean (tests/test_gpu_tile3_bits.py holds them to recorded bits).
 #include "nlt_common.h"
 #include "pack_common.h"
 
@@ -65,6 +76,86 @@ __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned&
   lo = cvt_pk_bf16(sa, sb);
 }
 
+// eight floats (a lane's two f32x4) -> the 16 bytes of each term: a B fragment of the bf16 MFMA, or one slot of each term plane
+__device__ __forceinline__ void split8(const f32x4& v0, const f32x4& v1, u32x4& hi, u32x4& mid, u32x4& lo) {
+  unsigned h[4], m[4], l[4];
+  split2(v0[0], v0[1], h[0], m[0], l[0]);
+  split2(v0[2], v0[3], h[1], m[1], l[1]);
+  split2(v1[0], v1[1], h[2], m[2], l[2]);
+  split2(v1[2], v1[3], h[3], m[3], l[3]);
+  hi = (u32x4){h[0], h[1], h[2], h[3]};
+  mid = (u32x4){m[0], m[1], m[2], m[3]};
+  lo = (u32x4){l[0], l[1], l[2], l[3]};
+}
+
+// ---- the pieces every schedule below is made of: each is defined once, so "the forms give the same bits" is structural ----
+
+// B copy unit u = (texel tx of the staged tile, channel half hf): 8 consecutive lanes take 8 consecutive texels of one half
+// (conflict-free 16-byte LDS stores; the two halves of a texel are its 64 contiguous bytes in global memory)
+__device__ __forceinline__ int unit_half(int u) { return (u >> 3) & 1; }
+__device__ __forceinline__ int unit_texel(int u) { return (u >> 4) * 8 + (u & 7); }
+
+// gather of a copy unit: channels [8 hf, 8 hf + 8) of texel `tex` of the slab at `sp`; zeros where the texel is outside the map
+__device__ __forceinline__ void gather_unit(const float* sp, int ld, bool ok, long tex, int hf, f32x4& v0, f32x4& v1) {
+  const float* q8 = sp + (ok ? tex : 0) * ld + 8 * hf;
+  const f32x4 g0 = *reinterpret_cast<const f32x4*>(q8), g1 = *reinterpret_cast<const f32x4*>(q8 + 4);
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  v0 = ok ? g0 : z;
+  v1 = ok ? g1 : z;
+}
+
+// split of a copy unit and its three 16-byte LDS stores: slot `bb` of the hi plane pair, mid and lo one plane PAIR (2 x bpl) on
+__device__ __forceinline__ void split_store_unit(u32x4* bb, int bpl, const f32x4& v0, const f32x4& v1) {
+  u32x4 hi, mid, lo;
+  split8(v0, v1, hi, mid, lo);
+  bb[0] = hi;
+  bb[2 * bpl] = mid;
+  bb[4 * bpl] = lo;
+}
+
+// LDS written by one lane, read by another of the SAME wave (the wave-private stages: LDS operations of one wave execute in
+// order; this only keeps the compiler from reordering them)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A fragments (three terms) of CT consecutive column tiles from tile `tile0` of a [tile][term][lane] block of packed weights
+template <int CT>
+__device__ __forceinline__ void read_a(const u32x4* A, int tile0, int lane, bf16x8 (&at)[3][CT]) {
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+    for (int t = 0; t < 3; ++t) at[t][ct] = __builtin_bit_cast(bf16x8, A[((tile0 + ct) * 3 + t) * 64 + lane]);
+}
+
+// (weight term, texel term), smallest products first
+constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
+
+// the last NPROD term products of one K block into NR x CT accumulators: product outermost, then row (or tap class), then column
+// tile, so consecutive MFMAs go to different accumulators.  bfrag(texel term, row) = the row's B fragment, wherever the caller keeps it
+template <int NPROD, int NR, int CT, class BFrag>
+__device__ __forceinline__ void term_products(const bf16x8 (&at)[3][CT], BFrag bfrag, f32x4 (&acc)[NR][CT]) {
+#pragma unroll
+  for (int pi = 9 - NPROD; pi < 9; ++pi)
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+        acc[r][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bfrag(ORDER9[pi][1], r), acc[r][ct], 0, 0, 0);
+}
+
+// accumulator + bias, LeakyReLU
+__device__ __forceinline__ f32x4 bias_act(const f32x4& acc, const f32x4& bv, int act, float alpha) {
+  f32x4 v = acc + bv;
+  if (act) {
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : alpha * v[c4];
+  }
+  return v;
+}
+
 __host__ __device__ inline u16 bf16_rne_bits(float f) {
   union { float f; unsigned u; } x; x.f = f;
   x.u += 0x7fffu + ((x.u >> 16) & 1u);
@@ -99,6 +190,86 @@ __global__ void pack_tile3_kernel(const float* __restrict__ wk, int cin, int cou
   wp[idx] = term == 0 ? hi : (term == 1 ? mid : bf16_rne_bits(r2));
 }
 
+// one finished observation frame i of an NR x 16 texel tile: bias, LeakyReLU, `out`, the running observation mean and, with the
+// last observation, `mean_out`.  Lane (kk, j) holds channels oc0 + 16 ct + [0, 4) of texel (gy0 + r, gx).  The accumulators are
+// cleared for the next frame; NEXT_ITEM: the registers go on to another tile (persistent forms), which starts its own mean
+template <bool NEXT_ITEM, int NR, int CT>
+__device__ __forceinline__ void epilogue(const Tile3P& p, int f, int i, int oc0, int gy0, int gx, f32x4 (&acc)[NR][CT],
+                                         f32x4 (&mean)[NR][CT]) {
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) {
+    const int oc = oc0 + 16 * ct;
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + oc);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+      const int gy = gy0 + r;
+      const f32x4 v = bias_act(acc[r][ct], bv, p.act, p.alpha);
+      acc[r][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      mean[r][ct] += v;
+      if (gy < p.oh && gx < p.ow) {
+        const long ot = ((long)(f * p.kobs + i) * p.oh + gy) * p.ow + gx;
+        if (p.out) *reinterpret_cast<f32x4*>(p.out + ot * p.ldo + oc) = v;
+        if (p.mean_out && i == p.kobs - 1) {
+          const long mt = ((long)f * p.oh + gy) * p.ow + gx;
+          *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[r][ct] * (1.f / (float)p.kobs);
+        }
+      }
+      if (NEXT_ITEM && i == p.kobs - 1) mean[r][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  }
+}
+
+// The SHARED STAGE of a 8 x 16 output tile (conv_tile3_kernel, conv_tile3r_kernel): term planes [term][half][slot] of BPL slots.
+// Copy unit u -> its channel half, its slot in the hi plane pair (+ term * 2 * BPL) and whether the unit exists at all ...
+template <int MODE>
+__device__ __forceinline__ void unit_slot(int u, int& hf, int& slot, bool& st) {
+  const int tx = unit_texel(u);
+  hf = unit_half(u);
+  if (MODE == NLT_CONV_K2S1) {                                          // haloed 9 x 17 tile, row-major
+    st = tx < 153;
+    slot = hf * PL + tx;
+  } else {                                                              // one tap row: 8 x 32 input texels, by x parity
+    const int y = tx >> 5, xx = tx & 31;
+    st = tx < 256;
+    slot = hf * QS2 + (xx & 1) * ODD2 + y * 16 + (xx >> 1);
+  }
+}
+// ... and, per tile (origin ty0, tx0 in output texels), texel tx of the staged tile in the input map and whether it lies inside.
+// (k2s1: any haloed tile of 17 columns, so the wave-private RT x 16 tiles use it too)
+template <int MODE>
+__device__ __forceinline__ void unit_source(const Tile3P& p, int tx, bool st, int ty0, int tx0, bool& ok, long& tex) {
+  if (MODE == NLT_CONV_K2S1) {
+    const int gy = ty0 + tx / 17, gx = tx0 + tx % 17;
+    ok = st && gy < p.h && gx < p.w;
+    tex = (long)gy * p.w + gx;
+  } else {
+    const int y = tx >> 5, xx = tx & 31;
+    const int gy = 2 * (ty0 + y), gx = 2 * tx0 + xx;
+    ok = st && (ty0 + y) < p.oh && gx < p.w;
+    tex = (long)gy * p.w + gx;
+  }
+}
+// one slab's products of wave (wm, wn): per tap pair, the B fragments of its RT rows, the A fragments of its CT column tiles
+template <int MODE, int TNT, int NPROD, int RT, int CT>
+__device__ __forceinline__ void stage_products(const u32x4* A, const u32x4* B, int lane, int wm, int wn, f32x4 (&acc)[RT][CT]) {
+  constexpr int BPL = MODE == NLT_CONV_K2S1 ? PL : QS2;
+  const int kk = lane >> 4, j = lane & 15;
+#pragma unroll
+  for (int pl = 0; pl < T3<MODE>::PAIRS; ++pl) {
+    bf16x8 bt[3][RT], at[3][CT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int y = wm * RT + rt;
+      const int slot = MODE == NLT_CONV_K2S1 ? (kk & 1) * PL + (y + pl) * 17 + j + (kk >> 1)
+                                             : (kk & 1) * QS2 + (kk >> 1) * ODD2 + y * 16 + j;
+#pragma unroll
+      for (int t = 0; t < 3; ++t) bt[t][rt] = __builtin_bit_cast(bf16x8, B[t * 2 * BPL + slot]);
+    }
+    read_a(A, pl * TNT + wn * CT, lane, at);
+    term_products<NPROD>(at, [&](int t, int rt) { return bt[t][rt]; }, acc);
+  }
+}
+
 // KO = observation frames of a tile that share ONE pass over the layer's weights (r04).  The weights are the larger half of what a
 // stage moves (k2s1 at 64 channels: 24.6 KB of term fragments against 9.8 KB of texels; every workgroup of the chip streams them
 // from L2), and the counter passes of r04 show the operand path, not the matrix pipe, bounding these launches.  With KO > 1 the
@@ -127,29 +298,11 @@ __global__ __launch_bounds__(256, 2) void conv_tile3_kernel(Tile3P p) {
   const int total = spf * p.kobs;                                      // micro-stages
   const long in_frame = (long)p.h * p.w;
 
-  // B copy units: unit = (texel, channel half): 8 consecutive lanes take 8 consecutive texels of one half (conflict-free
-  // 16-byte LDS stores; the two halves of a texel are its 64 contiguous bytes in global memory)
-  int b_lds[NB], b_hf[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
+  int b_lds[NB], b_hf[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];    // B copy units
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
-    const int u = tid + 256 * i;
-    const int hf = (u >> 3) & 1, tx = (u >> 4) * 8 + (u & 7);
-    b_hf[i] = hf;
-    if (MODE == NLT_CONV_K2S1) {
-      const int hy = tx / 17, hx = tx % 17;
-      const int gy = ty0 + hy, gx = tx0 + hx;
-      b_st[i] = tx < 153;
-      b_ok[i] = b_st[i] && gy < p.h && gx < p.w;
-      b_tex[i] = (long)gy * p.w + gx;
-      b_lds[i] = hf * PL + tx;                                        // + term * 2 * PL
-    } else {
-      const int y = tx >> 5, xx = tx & 31;
-      const int gy = 2 * (ty0 + y), gx = 2 * tx0 + xx;
-      b_st[i] = tx < 256;
-      b_ok[i] = b_st[i] && (ty0 + y) < p.oh && gx < p.w;
-      b_tex[i] = (long)gy * p.w + gx;
-      b_lds[i] = hf * QS2 + (xx & 1) * ODD2 + y * 16 + (xx >> 1);     // + term * 2 * QS2
-    }
+    unit_slot<MODE>(tid + 256 * i, b_hf[i], b_lds[i], b_st[i]);
+    unit_source<MODE>(p, unit_texel(tid + 256 * i), b_st[i], ty0, tx0, b_ok[i], b_tex[i]);
   }
   constexpr int BPL = MODE == NLT_CONV_K2S1 ? PL : QS2;
 
@@ -168,13 +321,7 @@ __global__ __launch_bounds__(256, 2) void conv_tile3_kernel(Tile3P p) {
     const int a = MODE == NLT_CONV_K2S1 ? 0 : (s & 1);
     const float* sp = p.src + ((long)(f * p.kobs + frame) * in_frame + (long)a * p.w) * p.ld + cc * 16;
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      rb[n][0] = b_ok[n] ? v0 : z;
-      rb[n][1] = b_ok[n] ? v1 : z;
-    }
+    for (int n = 0; n < NB; ++n) gather_unit(sp, p.ld, b_ok[n], b_tex[n], b_hf[n], rb[n][0], rb[n][1]);
   };
   auto store_a = [&](int buf) {
     u32x4* base = lds + buf * A_SLOTS;
@@ -185,18 +332,8 @@ __global__ __launch_bounds__(256, 2) void conv_tile3_kernel(Tile3P p) {
   auto store_b = [&](int buf) {
     u32x4* base = lds + 2 * A_SLOTS + buf * TT::B_SLOTS;
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      if (!b_st[n]) continue;
-      unsigned hi[4], mid[4], lo[4];
-      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
-      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
-      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
-      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
-      u32x4* bb = base + b_lds[n];
-      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
-      bb[2 * BPL] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
-      bb[4 * BPL] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
-    }
+    for (int n = 0; n < NB; ++n)
+      if (b_st[n]) split_store_unit(base + b_lds[n], BPL, rb[n][0], rb[n][1]);
   };
 
   f32x4 acc[KO][RT][CT], mean[RT][CT];
@@ -229,63 +366,11 @@ __global__ __launch_bounds__(256, 2) void conv_tile3_kernel(Tile3P p) {
           if (new_slab) load_a(ns);
           load_b(ns, ngi * KO + (new_slab ? 0 : io + 1));
         }
-        const u32x4* A = lds + sa * A_SLOTS;
-        const u32x4* B = lds + 2 * A_SLOTS + (q & 1) * TT::B_SLOTS;
-#pragma unroll
-        for (int pl = 0; pl < TT::PAIRS; ++pl) {
-          bf16x8 bt[3][RT], at[3][CT];
-#pragma unroll
-          for (int rt = 0; rt < RT; ++rt) {
-            const int y = wm * RT + rt;
-            const int slot = MODE == NLT_CONV_K2S1 ? (kk & 1) * PL + (y + pl) * 17 + j + (kk >> 1)
-                                                   : (kk & 1) * QS2 + (kk >> 1) * ODD2 + y * 16 + j;
-#pragma unroll
-            for (int t = 0; t < 3; ++t) bt[t][rt] = __builtin_bit_cast(bf16x8, B[t * 2 * BPL + slot]);
-          }
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-              at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * TNT + wn * CT + ct) * 3 + t) * 64 + lane]);
-          // (weight term, texel term), smallest products first; consecutive MFMAs go to different accumulators
-          constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
-#pragma unroll
-          for (int pi = 9 - NPROD; pi < 9; ++pi)
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-              for (int ct = 0; ct < CT; ++ct)
-                acc[io][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][rt], acc[io][rt][ct], 0, 0, 0);
-        }
+        stage_products<MODE, TNT, NPROD>(lds + sa * A_SLOTS, lds + 2 * A_SLOTS + (q & 1) * TT::B_SLOTS, lane, wm, wn, acc[io]);
         if (s == spf - 1 && io == KO - 1) {                             // the group's KO observation frames are complete
 #pragma unroll
-          for (int e = 0; e < KO; ++e) {
-            const int i = gi * KO + e;
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) {
-              const int oc = (g * TNT + wn * CT + ct) * 16 + 4 * kk;
-              const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + oc);
-#pragma unroll
-              for (int rt = 0; rt < RT; ++rt) {
-                const int gy = ty0 + wm * RT + rt, gx = tx0 + j;
-                f32x4 v = acc[e][rt][ct] + bv;
-                if (p.act) {
-#pragma unroll
-                  for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
-                }
-                acc[e][rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                mean[rt][ct] += v;
-                if (gy < p.oh && gx < p.ow) {
-                  const long ot = ((long)(f * p.kobs + i) * p.oh + gy) * p.ow + gx;
-                  if (p.out) *reinterpret_cast<f32x4*>(p.out + ot * p.ldo + oc) = v;
-                  if (p.mean_out && i == p.kobs - 1) {
-                    const long mt = ((long)f * p.oh + gy) * p.ow + gx;
-                    *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[rt][ct] * (1.f / (float)p.kobs);
-                  }
-                }
-              }
-            }
-          }
+          for (int e = 0; e < KO; ++e)
+            epilogue<false>(p, f, gi * KO + e, (g * TNT + wn * CT) * 16 + 4 * kk, ty0 + wm * RT, tx0 + j, acc[e], mean);
         }
         if (more) {
           if (new_slab) store_a(sa ^ 1);
@@ -335,19 +420,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_tile3r_kernel(Tile3P p, int 
 
   int b_lds[NB], b_hf[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
 #pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int u = tid + NT * i;
-    const int hf = (u >> 3) & 1, tx = (u >> 4) * 8 + (u & 7);
-    b_hf[i] = hf;
-    if (MODE == NLT_CONV_K2S1) {
-      b_st[i] = tx < 153;
-      b_lds[i] = hf * PL + tx;
-    } else {
-      const int y = tx >> 5, xx = tx & 31;
-      b_st[i] = tx < 256;
-      b_lds[i] = hf * QS2 + (xx & 1) * ODD2 + y * 16 + (xx >> 1);
-    }
-  }
+  for (int i = 0; i < NB; ++i) unit_slot<MODE>(tid + NT * i, b_hf[i], b_lds[i], b_st[i]);
   int ng = 0, nf = 0, nty0 = 0, ntx0 = 0;                               // the item whose slabs are being LOADED
   auto geom = [&](int item) {
     ng = item / tiles;
@@ -356,20 +429,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_tile3r_kernel(Tile3P p, int 
     nty0 = (t % p.tiles_y) * TH;
     nf = t / p.tiles_y;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int u = tid + NT * i;
-      const int tx = (u >> 4) * 8 + (u & 7);
-      if (MODE == NLT_CONV_K2S1) {
-        const int gy = nty0 + tx / 17, gx = ntx0 + tx % 17;
-        b_ok[i] = b_st[i] && gy < p.h && gx < p.w;
-        b_tex[i] = (long)gy * p.w + gx;
-      } else {
-        const int y = tx >> 5, xx = tx & 31;
-        const int gy = 2 * (nty0 + y), gx = 2 * ntx0 + xx;
-        b_ok[i] = b_st[i] && (nty0 + y) < p.oh && gx < p.w;
-        b_tex[i] = (long)gy * p.w + gx;
-      }
-    }
+    for (int i = 0; i < NB; ++i) unit_source<MODE>(p, unit_texel(tid + NT * i), b_st[i], nty0, ntx0, b_ok[i], b_tex[i]);
   };
 
   f32x4 rb[NB][2];
@@ -378,29 +438,13 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_tile3r_kernel(Tile3P p, int 
     const int a = MODE == NLT_CONV_K2S1 ? 0 : (s & 1);
     const float* sp = p.src + ((long)(nf * p.kobs + frame) * in_frame + (long)a * p.w) * p.ld + cc * 16;
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      rb[n][0] = b_ok[n] ? v0 : z;
-      rb[n][1] = b_ok[n] ? v1 : z;
-    }
+    for (int n = 0; n < NB; ++n) gather_unit(sp, p.ld, b_ok[n], b_tex[n], b_hf[n], rb[n][0], rb[n][1]);
   };
   auto store_b = [&](int buf) {
     u32x4* base = lds_b + buf * TT::B_SLOTS;
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      if (!b_st[n]) continue;
-      unsigned hi[4], mid[4], lo[4];
-      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
-      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
-      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
-      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
-      u32x4* bb = base + b_lds[n];
-      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
-      bb[2 * BPL] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
-      bb[4 * BPL] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
-    }
+    for (int n = 0; n < NB; ++n)
+      if (b_st[n]) split_store_unit(base + b_lds[n], BPL, rb[n][0], rb[n][1]);
   };
   auto copy_a = [&](int grp) {                                          // the group's whole block, as it lies in `packed`
     const u32x4* ap = reinterpret_cast<const u32x4*>(p.packed) + (long)grp * a_group;
@@ -440,63 +484,11 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv_tile3r_kernel(Tile3P p, int 
             if (!last_item) geom(it + 1);
           }
           load_b(ns, ngi * KO + (new_slab ? 0 : io + 1));
-          const u32x4* A = tile3r_lds + s * A_SLOTS;
-          const u32x4* B = lds_b + (q & 1) * TT::B_SLOTS;
-#pragma unroll
-          for (int pl = 0; pl < TT::PAIRS; ++pl) {
-            bf16x8 bt[3][RT], at[3][CT];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-              const int y = wm * RT + rt;
-              const int slot = MODE == NLT_CONV_K2S1 ? (kk & 1) * PL + (y + pl) * 17 + j + (kk >> 1)
-                                                     : (kk & 1) * QS2 + (kk >> 1) * ODD2 + y * 16 + j;
-#pragma unroll
-              for (int t = 0; t < 3; ++t) bt[t][rt] = __builtin_bit_cast(bf16x8, B[t * 2 * BPL + slot]);
-            }
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-              for (int t = 0; t < 3; ++t)
-                at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * TNT + wn * CT + ct) * 3 + t) * 64 + lane]);
-            constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
-#pragma unroll
-            for (int pi = 9 - NPROD; pi < 9; ++pi)
-#pragma unroll
-              for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-                  acc[io][rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][rt], acc[io][rt][ct], 0, 0, 0);
-          }
+          stage_products<MODE, TNT, NPROD>(tile3r_lds + s * A_SLOTS, lds_b + (q & 1) * TT::B_SLOTS, lane, wm, wn, acc[io]);
           if (s == spf - 1 && io == KO - 1) {                           // the group's KO observation frames are complete
 #pragma unroll
-            for (int e = 0; e < KO; ++e) {
-              const int i = gi * KO + e;
-#pragma unroll
-              for (int ct = 0; ct < CT; ++ct) {
-                const int oc = (g * TNT + wn * CT + ct) * 16 + 4 * kk;
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + oc);
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                  const int gy = ty0 + wm * RT + rt, gx = tx0 + j;
-                  f32x4 v = acc[e][rt][ct] + bv;
-                  if (p.act) {
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
-                  }
-                  acc[e][rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                  mean[rt][ct] += v;
-                  if (gy < p.oh && gx < p.ow) {
-                    const long ot = ((long)(f * p.kobs + i) * p.oh + gy) * p.ow + gx;
-                    if (p.out) *reinterpret_cast<f32x4*>(p.out + ot * p.ldo + oc) = v;
-                    if (p.mean_out && i == p.kobs - 1) {
-                      const long mt = ((long)f * p.oh + gy) * p.ow + gx;
-                      *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[rt][ct] * (1.f / (float)p.kobs);
-                    }
-                  }
-                  if (i == p.kobs - 1) mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};     // the next item starts its own mean
-                }
-              }
-            }
+            for (int e = 0; e < KO; ++e)
+              epilogue<true>(p, f, gi * KO + e, (g * TNT + wn * CT) * 16 + 4 * kk, ty0 + wm * RT, tx0 + j, acc[e], mean);
           }
           if (!(item_end && last_item)) store_b((q + 1) & 1);
           __syncthreads();
@@ -520,6 +512,14 @@ int tile3r_cus() {
     return v;
   }();
   return n;
+}
+
+// workgroups of a persistent launch: per_cu on every CU, at most max_wg (where > 0) and no more than there are items;
+// 0 where the device cannot be asked
+long tile3r_grid(int per_cu, int max_wg, long items) {
+  long nwg = (long)tile3r_cus() * per_cu;
+  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
+  return nwg > items ? items : nwg;
 }
 
 // dynamic LDS above 64 KB needs the kernel's limit raised: once per device and kernel (`done`: the instantiation's largest size so far)
@@ -571,9 +571,8 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_kernel(Tile3P p, int ngrou
   int b_lds[NB], b_hf[NB], b_tx[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
-    const int u = lane + 64 * i;
-    b_hf[i] = (u >> 3) & 1;
-    b_tx[i] = (u >> 4) * 8 + (u & 7);
+    b_hf[i] = unit_half(lane + 64 * i);
+    b_tx[i] = unit_texel(lane + 64 * i);
     b_st[i] = b_tx[i] < ROWS * 17;
     b_lds[i] = b_hf[i] * PLW + b_tx[i];
   }
@@ -583,43 +582,18 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_kernel(Tile3P p, int ngrou
     nty0 = (t % tiles_y) * RT;
     nf = t / tiles_y;
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const int gy = nty0 + b_tx[i] / 17, gx = ntx0 + b_tx[i] % 17;
-      b_ok[i] = b_st[i] && gy < p.h && gx < p.w;
-      b_tex[i] = (long)gy * p.w + gx;
-    }
+    for (int i = 0; i < NB; ++i) unit_source<NLT_CONV_K2S1>(p, b_tx[i], b_st[i], nty0, ntx0, b_ok[i], b_tex[i]);
   };
   f32x4 rb[NB][2];
   auto load_b = [&](int cc, int frame) {
     const float* sp = p.src + (long)(nf * p.kobs + frame) * in_frame * p.ld + cc * 16;
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      rb[n][0] = b_ok[n] ? v0 : z;
-      rb[n][1] = b_ok[n] ? v1 : z;
-    }
+    for (int n = 0; n < NB; ++n) gather_unit(sp, p.ld, b_ok[n], b_tex[n], b_hf[n], rb[n][0], rb[n][1]);
   };
   auto store_b = [&]() {
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      if (!b_st[n]) continue;
-      unsigned hi[4], mid[4], lo[4];
-      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
-      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
-      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
-      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
-      u32x4* bb = B + b_lds[n];
-      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
-      bb[2 * PLW] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
-      bb[4 * PLW] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
-    }
-  };
-  auto wave_sync = [&]() {                                              // LDS written by one lane, read by another of the SAME wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int n = 0; n < NB; ++n)
+      if (b_st[n]) split_store_unit(B + b_lds[n], PLW, rb[n][0], rb[n][1]);
   };
 
   int seg = it0;
@@ -666,48 +640,12 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_kernel(Tile3P p, int ngrou
 #pragma unroll
             for (int pl = 0; pl < 2; ++pl) {
               bf16x8 at[3][CT];
-#pragma unroll
-              for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int t = 0; t < 3; ++t) at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * TNT + ct) * 3 + t) * 64 + lane]);
-              constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
-#pragma unroll
-              for (int pi = 9 - NPROD; pi < 9; ++pi)
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                  for (int ct = 0; ct < CT; ++ct)
-                    acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][rt + pl], acc[rt][ct], 0, 0, 0);
+              read_a(A, pl * TNT, lane, at);
+              term_products<NPROD>(at, [&](int t, int rt) { return bt[t][rt + pl]; }, acc);
             }
             if (!(item_end && last_item)) store_b();
             wave_sync();
-            if (s == p.ncc - 1) {
-#pragma unroll
-              for (int ct = 0; ct < CT; ++ct) {
-                const int oc = (g * TNT + ct) * 16 + 4 * kk;
-                const f32x4 bv = *reinterpret_cast<const f32x4*>(p.bias + oc);
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                  const int gy = ty0 + rt, gx = tx0 + j;
-                  f32x4 v = acc[rt][ct] + bv;
-                  if (p.act) {
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
-                  }
-                  acc[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                  mean[rt][ct] += v;
-                  if (gy < p.oh && gx < p.ow) {
-                    const long ot = ((long)(f * p.kobs + i) * p.oh + gy) * p.ow + gx;
-                    if (p.out) *reinterpret_cast<f32x4*>(p.out + ot * p.ldo + oc) = v;
-                    if (p.mean_out && i == p.kobs - 1) {
-                      const long mt = ((long)f * p.oh + gy) * p.ow + gx;
-                      *reinterpret_cast<f32x4*>(p.mean_out + mt * p.ldm + oc) = mean[rt][ct] * (1.f / (float)p.kobs);
-                    }
-                  }
-                  if (i == p.kobs - 1) mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                }
-              }
-            }
+            if (s == p.ncc - 1) epilogue<true>(p, f, i, g * TNT * 16 + 4 * kk, ty0, tx0 + j, acc, mean);
           }
         }
       }
@@ -723,13 +661,9 @@ int launch3w(const Tile3P& p, int nprod, int max_wg, hipStream_t s) {
   constexpr int PLW = ((RT + 1) * 17 + 15) / 16 * 16;
   const size_t lds = (size_t)p.cin * 2 * 384 + 8 * 6 * PLW * sizeof(u32x4);
   if (lds > TILE3R_LDS_CU) return NLT_ERR_UNSUPPORTED;
-  const int cus = tile3r_cus();
-  if (cus <= 0) return NLT_ERR_LAUNCH;
   const int tiles_y = (p.oh + RT - 1) / RT;
-  const long items = (long)p.frames * tiles_y * p.tiles_x * (p.cout / 32);
-  long nwg = cus;
-  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
-  if (nwg > items) nwg = items;
+  const long nwg = tile3r_grid(1, max_wg, (long)p.frames * tiles_y * p.tiles_x * (p.cout / 32));
+  if (nwg <= 0) return NLT_ERR_LAUNCH;
   auto* k = nprod == 9 ? conv_tile3w_kernel<RT, 9> : conv_tile3w_kernel<RT, 6>;
   static size_t done[2][8] = {};
   if (tile3r_allow_lds(reinterpret_cast<const void*>(k), lds, done[nprod == 9]) != NLT_OK) return NLT_ERR_LAUNCH;
@@ -751,15 +685,12 @@ int launch3r(const Tile3P& p, int nprod, int max_wg, hipStream_t s) {
   const size_t lds = (size_t)p.cin * TNT * 384 + 2 * T3<MODE>::B_SLOTS * sizeof(u32x4);
   if (lds > TILE3R_LDS_CU) return NLT_ERR_UNSUPPORTED;
   const bool wide = 2 * lds > TILE3R_LDS_CU;
-  const int cus = tile3r_cus();
-  if (cus <= 0) return NLT_ERR_LAUNCH;
   const long items = (long)p.frames * p.tiles_y * p.tiles_x * (p.cout / (16 * TNT));
-  long nwg = (long)cus * (wide ? 1 : 2);
-  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
-  if (nwg > items) nwg = items;
+  const int nwg = (int)tile3r_grid(wide ? 1 : 2, max_wg, items);
+  if (nwg <= 0) return NLT_ERR_LAUNCH;
   if (items >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
-  if (wide) return nprod == 9 ? launch3r_k<MODE, TNT, 9, KO, 8>(p, lds, (int)nwg, s) : launch3r_k<MODE, TNT, 6, KO, 8>(p, lds, (int)nwg, s);
-  return nprod == 9 ? launch3r_k<MODE, TNT, 9, KO, 4>(p, lds, (int)nwg, s) : launch3r_k<MODE, TNT, 6, KO, 4>(p, lds, (int)nwg, s);
+  if (wide) return nprod == 9 ? launch3r_k<MODE, TNT, 9, KO, 8>(p, lds, nwg, s) : launch3r_k<MODE, TNT, 6, KO, 8>(p, lds, nwg, s);
+  return nprod == 9 ? launch3r_k<MODE, TNT, 9, KO, 4>(p, lds, nwg, s) : launch3r_k<MODE, TNT, 6, KO, 4>(p, lds, nwg, s);
 }
 
 // resident_wg < 0: the streaming kernel; >= 0: the resident form with at most that many workgroups (0 = sized from the device)
@@ -820,7 +751,6 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
   constexpr int RT = 4, CT = 2, NWV = 8, NCL = 4, NC2 = 4;
   constexpr int UNITS = 5 * 17 * 2, NB = (UNITS + 63) / 64;
   constexpr int A_SLOTS = S2_A1 / 2;
-  constexpr int ORDER9[9][2] = {{2, 2}, {2, 1}, {1, 2}, {2, 0}, {0, 2}, {1, 1}, {1, 0}, {0, 1}, {0, 0}};
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int kk = lane >> 4, j = lane & 15, yq = j >> 3, xq = j & 7;
   const u32x4* const A2 = tile3r_lds + S2_A1;
@@ -836,9 +766,8 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
   int b_lds[NB], b_hf[NB], b_row[NB], b_x[NB]; long b_tex[NB]; bool b_ok[NB], b_st[NB];
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
-    const int u = lane + 64 * i;
-    const int t = (u >> 4) * 8 + (u & 7), q = t % 17;
-    b_hf[i] = (u >> 3) & 1;
+    const int t = unit_texel(lane + 64 * i), q = t % 17;
+    b_hf[i] = unit_half(lane + 64 * i);
     b_row[i] = t / 17;
     b_x[i] = q < S2_ODD ? 2 * q : 2 * (q - S2_ODD) + 1;
     b_st[i] = t < 5 * 17;
@@ -860,33 +789,12 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
   auto load_b = [&](int cc, int frame) {
     const float* sp = p.src + (long)(nf * p.kobs + frame) * in_frame * p.ld + cc * 16;
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      const float* q8 = sp + (b_ok[n] ? b_tex[n] : 0) * p.ld + 8 * b_hf[n];
-      const f32x4 v0 = *reinterpret_cast<const f32x4*>(q8), v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
-      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-      rb[n][0] = b_ok[n] ? v0 : z;
-      rb[n][1] = b_ok[n] ? v1 : z;
-    }
+    for (int n = 0; n < NB; ++n) gather_unit(sp, p.ld, b_ok[n], b_tex[n], b_hf[n], rb[n][0], rb[n][1]);
   };
   auto store_b = [&]() {
 #pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      if (!b_st[n]) continue;
-      unsigned hi[4], mid[4], lo[4];
-      split2(rb[n][0][0], rb[n][0][1], hi[0], mid[0], lo[0]);
-      split2(rb[n][0][2], rb[n][0][3], hi[1], mid[1], lo[1]);
-      split2(rb[n][1][0], rb[n][1][1], hi[2], mid[2], lo[2]);
-      split2(rb[n][1][2], rb[n][1][3], hi[3], mid[3], lo[3]);
-      u32x4* bb = B + b_lds[n];
-      bb[0] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
-      bb[2 * S2_PLW] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
-      bb[4 * S2_PLW] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
-    }
-  };
-  auto wave_sync = [&]() {                                              // LDS written by one lane, read by another of the SAME wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int n = 0; n < NB; ++n)
+      if (b_st[n]) split_store_unit(B + b_lds[n], S2_PLW, rb[n][0], rb[n][1]);
   };
 
   {                                                                     // both weight sets, once per workgroup
@@ -944,20 +852,11 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
           bf16x8 at[3][CT];
-#pragma unroll
-          for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int t = 0; t < 3; ++t) at[t][ct] = __builtin_bit_cast(bf16x8, A[((pl * 2 + ct) * 3 + t) * 64 + lane]);
-#pragma unroll
-          for (int pi = 9 - NPROD; pi < 9; ++pi)
-#pragma unroll
-            for (int c = 0; c < NCL; ++c)
-#pragma unroll
-              for (int ct = 0; ct < CT; ++ct)
-                acc[c][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at[ORDER9[pi][0]][ct], bt[ORDER9[pi][1]][((c >> 1) + pl) * 2 + (c & 1)],
-                                                                     acc[c][ct], 0, 0, 0);
+          read_a(A, pl * 2, lane, at);
+          term_products<NPROD>(at, [&](int t, int c) { return bt[t][((c >> 1) + pl) * 2 + (c & 1)]; }, acc);
         }
         if (s == 1) {
+          // (its own epilogue: no `out`, tap classes instead of rows, biases from LDS -- and the values stay in registers)
           u32x4 bs[3][NCL];                                             // the stride-2 conv's B fragments: tap class c, three terms
 #pragma unroll
           for (int c = 0; c < NCL; ++c) {
@@ -966,11 +865,7 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
               const int oc = ct * 16 + 4 * kk;
-              f32x4 v = acc[c][ct] + *reinterpret_cast<const f32x4*>(biasl + oc);
-              if (p.act) {
-#pragma unroll
-                for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : p.alpha * v[c4];
-              }
+              const f32x4 v = bias_act(acc[c][ct], *reinterpret_cast<const f32x4*>(biasl + oc), p.act, p.alpha);
               acc[c][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
               mean[c][ct] += v;
               if (p.mean_out && i == p.kobs - 1 && gy < p.oh && gx < p.ow) {
@@ -980,33 +875,18 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
               if (i == p.kobs - 1) mean[c][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
               v2[ct] = v;
             }
-            unsigned hi[4], mid[4], lo[4];
-            split2(v2[0][0], v2[0][1], hi[0], mid[0], lo[0]);
-            split2(v2[0][2], v2[0][3], hi[1], mid[1], lo[1]);
-            split2(v2[1][0], v2[1][1], hi[2], mid[2], lo[2]);
-            split2(v2[1][2], v2[1][3], hi[3], mid[3], lo[3]);
-            bs[0][c] = (u32x4){hi[0], hi[1], hi[2], hi[3]};
-            bs[1][c] = (u32x4){mid[0], mid[1], mid[2], mid[3]};
-            bs[2][c] = (u32x4){lo[0], lo[1], lo[2], lo[3]};
+            split8(v2[0], v2[1], bs[0][c], bs[1][c], bs[2][c]);
           }
-          f32x4 acc2[NC2];
+          f32x4 acc2[NC2 / 2][1][2];                                    // [pair of column tiles]: one row of two tiles per K block
 #pragma unroll
-          for (int c2 = 0; c2 < NC2; ++c2) acc2[c2] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          for (int c2 = 0; c2 < NC2; ++c2) acc2[c2 >> 1][0][c2 & 1] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int c = 0; c < NCL; ++c) {                               // K block = tap (ty, tx) = c
 #pragma unroll
             for (int ch = 0; ch < NC2; ch += 2) {                       // two column tiles at a time: 24 registers of A fragments
               bf16x8 a2[3][2];
-#pragma unroll
-              for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-                for (int t = 0; t < 3; ++t) a2[t][c2] = __builtin_bit_cast(bf16x8, A2[((c * NC2 + ch + c2) * 3 + t) * 64 + lane]);
-#pragma unroll
-              for (int pi = 9 - NPROD; pi < 9; ++pi)
-#pragma unroll
-                for (int c2 = 0; c2 < 2; ++c2)
-                  acc2[ch + c2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2[ORDER9[pi][0]][c2], __builtin_bit_cast(bf16x8, bs[ORDER9[pi][1]][c]),
-                                                                          acc2[ch + c2], 0, 0, 0);
+              read_a(A2, c * NC2 + ch, lane, a2);
+              term_products<NPROD>(a2, [&](int t, int) { return __builtin_bit_cast(bf16x8, bs[t][c]); }, acc2[ch >> 1]);
             }
           }
           const int oy = (ty0 >> 1) + yq, ox = (tx0 >> 1) + xq;
@@ -1015,12 +895,8 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
 #pragma unroll
             for (int c2 = 0; c2 < NC2; ++c2) {
               const int oc = c2 * 16 + 4 * kk;
-              f32x4 v = acc2[c2] + *reinterpret_cast<const f32x4*>(biasl + 32 + oc);
-              if (P.act2) {
-#pragma unroll
-                for (int c4 = 0; c4 < 4; ++c4) v[c4] = v[c4] > 0.f ? v[c4] : P.alpha2 * v[c4];
-              }
-              *reinterpret_cast<f32x4*>(P.out2 + ot * P.ldo2 + oc) = v;
+              *reinterpret_cast<f32x4*>(P.out2 + ot * P.ldo2 + oc) =
+                  bias_act(acc2[c2 >> 1][0][c2 & 1], *reinterpret_cast<const f32x4*>(biasl + 32 + oc), P.act2, P.alpha2);
             }
           }
         }
@@ -1033,14 +909,11 @@ __global__ __launch_bounds__(512, 2) void conv_tile3w_s2_kernel(Tile3S2P P, int 
 
 int launch3w_s2(const Tile3S2P& P, int nprod, int max_wg, hipStream_t s) {
   if (S2_LDS > TILE3R_LDS_CU) return NLT_ERR_UNSUPPORTED;
-  const int cus = tile3r_cus();
-  if (cus <= 0) return NLT_ERR_LAUNCH;
   const int tiles_y = (P.a.oh + 3) / 4;
   const long items = (long)P.a.frames * tiles_y * P.a.tiles_x;
+  const long nwg = tile3r_grid(1, max_wg, items);
+  if (nwg <= 0) return NLT_ERR_LAUNCH;
   if (items >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
-  long nwg = cus;
-  if (max_wg > 0 && nwg > max_wg) nwg = max_wg;
-  if (nwg > items) nwg = items;
   auto* k = nprod == 9 ? conv_tile3w_s2_kernel<9> : conv_tile3w_s2_kernel<6>;
   static size_t done[2][8] = {};
   if (tile3r_allow_lds(reinterpret_cast<const void*>(k), S2_LDS, done[nprod == 9]) != NLT_OK) return NLT_ERR_LAUNCH;
@@ -1052,6 +925,28 @@ int launch3w_s2(const Tile3S2P& P, int nprod, int max_wg, hipStream_t s) {
 __global__ void pack_tile3s2_kernel(const float* __restrict__ wk, int cin, int cout, long total, u16* __restrict__ wp) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx < total) wp[idx] = nlt_tile3s2_fragment(wk, idx, cin, cout);
+}
+
+// What every forward entry point checks, in the order its statuses rank (bad argument, unsupported shape, bad layout, too large),
+// and the Tile3P of the conv.  The caller's own conditions come evaluated, one per rank: own_args, supported, own_layout;
+// ld_other = the row length of the per-observation map it writes, for the 32-bit index bound.
+int tile3_params(Tile3P& p, bool own_args, bool supported, bool own_layout, int ld_other, bool stride2,
+                 const float* src, int ld, int cin, int frames, int kobs, int h, int w, const u16* packed, const float* bias, int cout,
+                 float* out, int ldo, float* mean_out, int ldm, int act, float alpha) {
+  if (!own_args || !src || !packed || !bias) return NLT_ERR_BAD_ARG;
+  if (frames <= 0 || kobs <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return NLT_ERR_BAD_ARG;
+  if (!supported) return NLT_ERR_UNSUPPORTED;
+  if (!own_layout || ld < cin || (ld & 3) || (out && (ldo < cout || (ldo & 3))) || (mean_out && (ldm < cout || (ldm & 3))))
+    return NLT_ERR_BAD_ARG;
+  if (!nlt_aligned16(src) || !nlt_aligned16(packed) || !nlt_aligned16(bias) || (out && !nlt_aligned16(out)) ||
+      (mean_out && !nlt_aligned16(mean_out))) return NLT_ERR_BAD_ARG;
+  if ((long long)frames * kobs * h * w * (long long)(ld > ld_other ? ld : ld_other) >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+  p.src = src; p.packed = packed; p.bias = bias; p.out = out; p.mean_out = mean_out;
+  p.ld = ld; p.cin = cin; p.frames = frames; p.kobs = kobs; p.h = h; p.w = w;
+  p.oh = stride2 ? h / 2 : h; p.ow = stride2 ? w / 2 : w;
+  p.cout = cout; p.ldo = ldo; p.ldm = ldm; p.ncc = cin / 16; p.act = act; p.alpha = alpha;
+  p.tiles_y = (p.oh + TH - 1) / TH; p.tiles_x = (p.ow + TW - 1) / TW;
+  return NLT_OK;
 }
 
 }  // namespace
@@ -1076,20 +971,12 @@ extern "C" int nlt_pack_conv_tile3_weights(int mode, const float* w_keras, int c
 static int tile3_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
                          const unsigned short* packed, const float* bias, int cout, int tn,
                          float* out, int ldo, float* mean_out, int ldm, int act, float alpha, int resident_wg, void* stream) {
-  if (!src || !packed || !bias || (!out && !mean_out) || (nprod != 1 && nprod != 3 && nprod != 6 && nprod != 9)) return NLT_ERR_BAD_ARG;
-  if (frames <= 0 || kobs <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0) return NLT_ERR_BAD_ARG;
-  if (nlt_conv_tile3_packed_elems(mode, cin, cout, tn) <= 0) return NLT_ERR_UNSUPPORTED;
-  if (mode == NLT_CONV_K2S2 && ((h | w) & 1)) return NLT_ERR_UNSUPPORTED;
-  if (ld < cin || (ld & 3) || (out && (ldo < cout || (ldo & 3))) || (mean_out && (ldm < cout || (ldm & 3)))) return NLT_ERR_BAD_ARG;
-  if (!nlt_aligned16(src) || !nlt_aligned16(packed) || !nlt_aligned16(bias) || (out && !nlt_aligned16(out)) ||
-      (mean_out && !nlt_aligned16(mean_out))) return NLT_ERR_BAD_ARG;
-  if ((long long)frames * kobs * h * w * (long long)(ld > ldo ? ld : ldo) >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+  const bool own_args = (out || mean_out) && (nprod == 1 || nprod == 3 || nprod == 6 || nprod == 9);
+  const bool supported = nlt_conv_tile3_packed_elems(mode, cin, cout, tn) > 0 && !(mode == NLT_CONV_K2S2 && ((h | w) & 1));
   Tile3P p;
-  p.src = src; p.packed = packed; p.bias = bias; p.out = out; p.mean_out = mean_out;
-  p.ld = ld; p.cin = cin; p.frames = frames; p.kobs = kobs; p.h = h; p.w = w;
-  p.oh = mode == NLT_CONV_K2S2 ? h / 2 : h; p.ow = mode == NLT_CONV_K2S2 ? w / 2 : w;
-  p.cout = cout; p.ldo = ldo; p.ldm = ldm; p.ncc = cin / 16; p.act = act; p.alpha = alpha;
-  p.tiles_y = (p.oh + TH - 1) / TH; p.tiles_x = (p.ow + TW - 1) / TW;
+  const int st = tile3_params(p, own_args, supported, true, ldo, mode == NLT_CONV_K2S2, src, ld, cin, frames, kobs, h, w, packed, bias,
+                              cout, out, ldo, mean_out, ldm, act, alpha);
+  if (st != NLT_OK) return st;
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (mode == NLT_CONV_K2S1)
     return tn == 64 ? launch3<NLT_CONV_K2S1, 4>(p, nprod, s, resident_wg) : launch3<NLT_CONV_K2S1, 2>(p, nprod, s, resident_wg);
@@ -1136,20 +1023,14 @@ extern "C" int nlt_conv_tile3w_s2_forward(int nprod, const float* src, int ld, i
                                           float* mean_out, int ldm, int act, float alpha,
                                           const unsigned short* packed2, const float* bias2, int cout2, float* out2, int ldo2,
                                           int act2, float alpha2, int max_workgroups, void* stream) {
-  if (!src || !packed || !bias || !packed2 || !bias2 || !out2 || max_workgroups < 0) return NLT_ERR_BAD_ARG;
-  if (frames <= 0 || kobs <= 0 || h <= 0 || w <= 0 || cin <= 0 || cout <= 0 || cout2 <= 0) return NLT_ERR_BAD_ARG;
-  if (nlt_conv_tile3w_s2_lds_bytes(cin, cout, cout2) <= 0 || (nprod != 6 && nprod != 9) || ((h | w) & 1) || out)
-    return NLT_ERR_UNSUPPORTED;
-  if (ld < cin || (ld & 3) || ldo2 < cout2 || (ldo2 & 3) || (mean_out && (ldm < cout || (ldm & 3)))) return NLT_ERR_BAD_ARG;
-  if (!nlt_aligned16(src) || !nlt_aligned16(packed) || !nlt_aligned16(bias) || !nlt_aligned16(packed2) || !nlt_aligned16(bias2) ||
-      !nlt_aligned16(out2) || (mean_out && !nlt_aligned16(mean_out))) return NLT_ERR_BAD_ARG;
-  if ((long long)frames * kobs * h * w * (long long)(ld > ldo2 ? ld : ldo2) >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+  const bool own_args = packed2 && bias2 && out2 && max_workgroups >= 0 && cout2 > 0;
+  // (the stride-1 map is not stored: a caller that wants `out` is refused)
+  const bool supported = nlt_conv_tile3w_s2_lds_bytes(cin, cout, cout2) > 0 && (nprod == 6 || nprod == 9) && !((h | w) & 1) && !out;
+  const bool own_layout = ldo2 >= cout2 && !(ldo2 & 3) && nlt_aligned16(packed2) && nlt_aligned16(bias2) && nlt_aligned16(out2);
   Tile3S2P P;
-  Tile3P& p = P.a;
-  p.src = src; p.packed = packed; p.bias = bias; p.out = nullptr; p.mean_out = mean_out;
-  p.ld = ld; p.cin = cin; p.frames = frames; p.kobs = kobs; p.h = h; p.w = w;
-  p.oh = h; p.ow = w; p.cout = cout; p.ldo = ldo; p.ldm = ldm; p.ncc = cin / 16; p.act = act; p.alpha = alpha;
-  p.tiles_y = (h + TH - 1) / TH; p.tiles_x = (w + TW - 1) / TW;
+  const int st = tile3_params(P.a, own_args, supported, own_layout, ldo2, false, src, ld, cin, frames, kobs, h, w, packed, bias, cout,
+                              out, ldo, mean_out, ldm, act, alpha);
+  if (st != NLT_OK) return st;
   P.packed2 = packed2; P.bias2 = bias2; P.out2 = out2; P.ldo2 = ldo2; P.act2 = act2; P.alpha2 = alpha2;
   return launch3w_s2(P, nprod, max_workgroups, static_cast<hipStream_t>(stream));
 }
