@@ -13,7 +13,8 @@ template <int MODE>
 __device__ __forceinline__ long nlt_keras_widx(int t, int c, int ncol, int cin, int cout, int full, int lo) {
   if (MODE == NLT_CONV1X1 || MODE == NLT_CONV_K2S2 || MODE == NLT_CONV_K2S1) return ((long)t * cin + c) * full + lo + ncol;
   if (MODE == NLT_DECONV_K2S1) return ((long)t * full + lo + ncol) * cin + c;
-  const int ab = ncol / cout, o = ncol - ab * cout;                    // DECONV_K2S2: ncol = (a*2+b)*cout + o
+  if (full == cout) return ((long)lo + ncol) * cin + c;                // DECONV_K2S2: ncol = (a*2+b)*cout + o; unsliced: no division
+  const int ab = ncol / cout, o = ncol - ab * cout;
   return ((long)ab * full + lo + o) * cin + c;
 }
 

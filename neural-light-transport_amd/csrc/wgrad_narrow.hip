@@ -8,16 +8,10 @@
 // v_mfma_f32_16x16x4_f32.  Operands are 4-byte loads -- lane (i, kk) reads X[row kk][k = 16 mt + i] and
 // dP[row kk][n = 16 nt + i], 16 consecutive floats per row -- MT + NT loads feed MT * NT MFMAs, all of them useful.
 // Any channel count works (no quad alignment).  Row slices -> workspace -> fixed-order reduction, as in wgrad_tile.
-#include "nlt_common.h"
+#include "wgrad_common.h"
+#include <type_traits>
 
 namespace {
-
-template <int MODE>
-__device__ __forceinline__ long keras_widx_n(int t, int c, int ncol, int cin, int cout) {
-  if (MODE == NLT_CONV_K2S2 || MODE == NLT_CONV_K2S1) return ((long)t * cin + c) * cout + ncol;
-  if (MODE == NLT_DECONV_K2S1) return ((long)t * cout + ncol) * cin + c;
-  return (long)ncol * cin + c;   // DECONV_K2S2: ncol = (a*2+b)*cout + o
-}
 
 struct WN {
   ConvP c;
@@ -28,6 +22,11 @@ struct WN {
   int msplits, rows_per_split;
 };
 
+// One slice's workspace block: [K padded to MT * 16][NC] floats + NC column sums of dP.
+template <int MT, int NT>
+struct NarrowBlock { static constexpr int NC = NT * 16, KN = MT * 16 * NC, PER = KN + NC; };
+
+// Scalar-A form: any channel count and leading dimension; the rows re-derived per step (RowCursor).
 template <int MODE, int MT, int NT>
 __global__ __launch_bounds__(256) void wgrad_narrow_kernel(WN w) {
   extern __shared__ float xch[];                                       // one wave's block: [MT*16][NT*16] + [NT*16] column sums
@@ -37,165 +36,93 @@ __global__ __launch_bounds__(256) void wgrad_narrow_kernel(WN w) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = lane & 15, kk = lane >> 4;
   const int ms = blockIdx.x;
-  const int cin = p.c0 + p.c1;
 
-  // A role, per M tile: K index 16 mt + i = (tap, channel of the virtual concat)
-  const float* ap[MT]; int ald[MT], oy[MT], ox[MT], tdelta[MT]; bool aok[MT];
+  // A role per M tile: K index 16 mt + i, input texel of a row = (S * y + oy, S * x + ox); B role per N tile
+  ARole<1> ar[MT]; int oy[MT], ox[MT], tdelta[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
-    const int kidx = mt * 16 + i;
-    aok[mt] = kidx < w.K;
-    const int tap = aok[mt] ? kidx / cin : 0;
-    const int c = aok[mt] ? kidx - tap * cin : 0;
-    const bool from1 = c >= p.c0;
-    ap[mt] = from1 ? p.src1 + (c - p.c0) : p.src0 + c;
-    ald[mt] = from1 ? p.ld1 : p.ld0;
-    const int a = TAPS == 4 ? tap >> 1 : 0, b = TAPS == 4 ? tap & 1 : 0;
-    oy[mt] = MODE == NLT_DECONV_K2S1 ? -a : a;                         // input texel = (S * y + oy, S * x + ox)
+    ar[mt] = ARole<1>(mt * 16 + i, w.K, p);
+    const int a = TAPS == 4 ? ar[mt].ta() : 0, b = TAPS == 4 ? ar[mt].tb() : 0;
+    oy[mt] = MODE == NLT_DECONV_K2S1 ? -a : a;
     ox[mt] = MODE == NLT_DECONV_K2S1 ? -b : b;
     tdelta[mt] = oy[mt] * p.w + ox[mt];
   }
-  // B role, per N tile
-  int boff[NT], bdelta[NT]; bool bok[NT];
+  BRole<MODE> br[NT]; int bdelta[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    const int n = nt * 16 + i;
-    bok[nt] = n < w.N;
-    const int nn = bok[nt] ? n : 0;
-    if (MODE == NLT_DECONV_K2S2) {
-      const int ab = nn / p.cout;
-      boff[nt] = nn - ab * p.cout;
-      bdelta[nt] = (ab >> 1) * p.ow + (ab & 1);
-    } else {
-      boff[nt] = nn;
-      bdelta[nt] = 0;
-    }
+    br[nt] = BRole<MODE>(nt * 16 + i, w.N, p);
+    bdelta[nt] = (br[nt].ab >> 1) * p.ow + (br[nt].ab & 1);
   }
 
-  f32x4 acc[MT][NT];
+  f32x4 acc[MT * NT];
   float bsum[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     bsum[nt] = 0.f;
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int mt = 0; mt < MT; ++mt) acc[mt * NT + nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
 
-  const int m_begin = ms * w.rows_per_split;
-  int m_end = m_begin + w.rows_per_split;
-  if (m_end > p.M) m_end = p.M;
-  int m = m_begin + 4 * wv + kk;                                       // this lane's row of the NEXT step to be loaded
-  int rx, ry, rf;
-  {
-    const int mc = m < p.M ? m : p.M - 1;
-    rx = mc % p.gw; ry = (mc / p.gw) % p.gh; rf = mc / (p.gw * p.gh);
-  }
+  RowCursor c;
+  c.init(ms * w.rows_per_split, w.rows_per_split, wv, kk, p);
   auto issue = [&](float (&av)[MT], float (&bv)[NT]) {
-    const bool rv = m < m_end;
-    const int ys = S * ry, xs = S * rx;
-    const int rowtex = (rf * p.h + ys) * p.w + xs;
+    const bool rv = c.valid();
+    const int ys = S * c.ry, xs = S * c.rx;
+    const int rowtex = (c.rf * p.h + ys) * p.w + xs;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      const bool ok = rv && aok[mt] && (unsigned)(ys + oy[mt]) < (unsigned)p.h && (unsigned)(xs + ox[mt]) < (unsigned)p.w;
+      const bool ok = rv && ar[mt].ok && (unsigned)(ys + oy[mt]) < (unsigned)p.h && (unsigned)(xs + ox[mt]) < (unsigned)p.w;
       const int tex = ok ? rowtex + tdelta[mt] : 0;
-      const float v = ap[mt][(size_t)tex * ald[mt]];                   // unconditional, clamped address
+      const float v = ar[mt].src[(size_t)tex * ar[mt].ld];                // unconditional, clamped address
       av[mt] = ok ? v : 0.f;
     }
-    const int rowo = MODE == NLT_DECONV_K2S2 ? (rf * p.oh + 2 * ry) * p.ow + 2 * rx : m;
+    const int rowo = MODE == NLT_DECONV_K2S2 ? (c.rf * p.oh + 2 * c.ry) * p.ow + 2 * c.rx : c.m;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      const bool ok = rv && bok[nt];
+      const bool ok = rv && br[nt].ok;
       const int otex = ok ? rowo + bdelta[nt] : 0;
-      const float v = w.dp[(size_t)otex * w.ldp + boff[nt]];
+      const float v = w.dp[(size_t)otex * w.ldp + br[nt].off];
       bv[nt] = ok ? v : 0.f;
     }
-    m += 16; rx += 16;                                                 // the wave's next step is 16 rows further
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {                                      // gw >= 4 (checked by the host): at most 4 wraps, branch-free
-      const bool wx = rx >= p.gw;
-      rx -= wx ? p.gw : 0;
-      ry += wx ? 1 : 0;
-      const bool wy = ry >= p.gh;
-      ry = wy ? 0 : ry;
-      rf += wy ? 1 : 0;
-    }
+    c.advance16(p);
   };
   auto compute = [&](const float (&av)[MT], const float (&bv)[NT]) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       bsum[nt] += bv[nt];
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+      for (int mt = 0; mt < MT; ++mt) acc[mt * NT + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[nt], acc[mt * NT + nt], 0, 0, 0);
     }
   };
-  const int first = m_begin + 4 * wv;
-  const int nsteps = first < m_end ? (m_end - first + 15) / 16 : 0;
+  // (RowCursor::rotate3 written out: through the function, wgrad_narrow_kernel<NLT_DECONV_K2S2, 8, 1> loses a wave of occupancy)
   float a0[MT], b0[NT], a1[MT], b1[NT], a2[MT], b2[NT];
   issue(a0, b0);
   issue(a1, b1);
-  for (int s3 = 0; s3 < nsteps; s3 += 3) {                             // steps past nsteps carry zero operands
+  for (int s3 = 0; s3 < c.nsteps; s3 += 3) {                           // steps past nsteps carry zero operands
     issue(a2, b2); compute(a0, b0);
     issue(a0, b0); compute(a1, b1);
     issue(a1, b1); compute(a2, b2);
   }
 
-  // waves 1..3 hand their blocks to wave 0 one after the other (fixed order -> deterministic)
-  constexpr int NC = NT * 16, KN = MT * 16 * NC;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    bsum[nt] += __shfl_xor(bsum[nt], 16);
-    bsum[nt] += __shfl_xor(bsum[nt], 32);
-  }
-  for (int src = 1; src < 4; ++src) {
-    if (wv == src) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) xch[(mt * 16 + 4 * kk + r) * NC + nt * 16 + i] = acc[mt][nt][r];
-      if (kk == 0)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) xch[KN + nt * 16 + i] = bsum[nt];
-    }
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[mt][nt][r] += xch[(mt * 16 + 4 * kk + r) * NC + nt * 16 + i];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) bsum[nt] += xch[KN + nt * 16 + i];
-    }
-    __syncthreads();
-  }
+  // waves 1..3 hand their blocks to wave 0 one after the other; accumulator (mt, nt), D row 4 kk + r: K index 16 mt + 4 kk + r
+  using Blk = NarrowBlock<MT, NT>;
+  ColumnSums<NT> cols{bsum, Blk::KN + i, kk == 0};
+  cols.across_row_groups();
+  auto slot = [i, kk](int j, int r) { return (16 * (j / NT) + 4 * kk + r) * Blk::NC + (j % NT) * 16 + i; };
+  wave_order_sum(xch, wv, acc, slot, cols);
   if (wv) return;
-  float* dst = w.ws + (size_t)ms * (KN + NC);
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dst[(mt * 16 + 4 * kk + r) * NC + nt * 16 + i] = acc[mt][nt][r];
-  if (kk == 0)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) dst[KN + nt * 16 + i] = bsum[nt];
+  float* dst = w.ws + (size_t)ms * Blk::PER;
+  store_block(dst, acc, slot);
+  cols.put(dst);
 }
 
-// Quad-A form (channel counts and leading dimensions multiples of 4, 16-byte aligned sources): ONE 16-byte load per lane
-// brings the four K values of a channel quad, so a 64-entry slice of K (= all four taps of a 16-channel layer) costs one
-// load + one address computation instead of four; tile e of the four MFMA row tiles it feeds holds K indices
-// 4 * quad + e, i.e. the same [K][N] workspace layout as the scalar form above.  B stays one 4-byte load per 16 columns.
-//
-// WALK (row grid a multiple of 4 texels wide -- every released shape): the rows are walked instead of re-derived.  A wave
-// takes a contiguous run of its slice, 4 rows per step; 4 | gw means the 4 rows of a step share one image row, so the
-// step's position (x0, y) lives in scalar registers, every lane keeps its operand POINTERS and advances them by
-// lane-constant increments (a second constant on steps that wrap to the next image row, where the stride-2 families
-// jump), padding validity is two compares against lane constants, loads are unconditional, and the loads run PF - 1
-// steps ahead.  The generic form's ~70 VALU instructions of index arithmetic per step (for 4 to 16 MFMAs) were this
-// kernel's time; past the end of a run dP is read from a zero page.
+// Quad-A form (channel counts and leading dimensions multiples of 4, 16-byte aligned sources): ONE 16-byte load per lane brings the
+// four K values of a channel quad, so a 64-entry slice of K (= all four taps of a 16-channel layer) costs one load + one address
+// computation instead of four; tile e of the four MFMA row tiles it feeds holds K indices 4 * quad + e, i.e. the same [K][N]
+// workspace layout as the scalar form above.  B stays one 4-byte load per 16 columns.
+// WALK (row grid a multiple of 4 texels wide -- every released shape): the rows are walked (RowWalk) instead of re-derived
+// (RowCursor), and the loads run PF - 1 steps ahead.  The re-deriving form's ~70 VALU instructions of index arithmetic per step
+// (for 4 to 16 MFMAs) were this kernel's time.
 template <int MQ, int NT> struct NarrowPF { static constexpr int value = MQ * NT >= 4 ? 6 : 8; };
 
 template <int MODE, int MQ, int NT, bool WALK>
@@ -203,96 +130,75 @@ __global__ __launch_bounds__(256) void wgrad_narrowq_kernel(WN w) {
   extern __shared__ float xch[];
   const ConvP& p = w.c;
   constexpr int TAPS = MODE == NLT_DECONV_K2S2 ? 1 : 4;
-  constexpr int S = MODE == NLT_CONV_K2S2 ? 2 : 1;
-  constexpr int MT = 4 * MQ;
+  constexpr int S = MODE == NLT_CONV_K2S2 ? 2 : 1;                     // input rows per GEMM-grid row
+  using Blk = NarrowBlock<4 * MQ, NT>;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int i = lane & 15, kk = lane >> 4;
   const int ms = blockIdx.x;
-  const int q0 = p.c0 >> 2, qpt = (p.c0 + p.c1) >> 2, nquads = w.K >> 2;
 
-  const float* ap[MQ]; int ald[MQ], oy[MQ], ox[MQ], tdelta[MQ]; bool aok[MQ];
+  // A role per M tile: input texel of a row = (S * y + oy, S * x + ox); B role per N tile
+  ARole<4> ar[MQ]; int oy[MQ], ox[MQ], tdelta[MQ];
 #pragma unroll
   for (int mq = 0; mq < MQ; ++mq) {
-    const int q = mq * 16 + i;
-    aok[mq] = q < nquads;
-    const int tap = aok[mq] ? q / qpt : 0;
-    const int cq = aok[mq] ? q - tap * qpt : 0;
-    const bool from1 = cq >= q0;
-    ap[mq] = from1 ? p.src1 + 4 * (cq - q0) : p.src0 + 4 * cq;
-    ald[mq] = from1 ? p.ld1 : p.ld0;
-    const int a = TAPS == 4 ? tap >> 1 : 0, b = TAPS == 4 ? tap & 1 : 0;
+    ar[mq] = ARole<4>(mq * 16 + i, w.K >> 2, p);
+    const int a = TAPS == 4 ? ar[mq].ta() : 0, b = TAPS == 4 ? ar[mq].tb() : 0;
     oy[mq] = MODE == NLT_DECONV_K2S1 ? -a : a;
     ox[mq] = MODE == NLT_DECONV_K2S1 ? -b : b;
     tdelta[mq] = oy[mq] * p.w + ox[mq];
   }
-  int boff[NT], bdelta[NT]; bool bok[NT];
+  BRole<MODE> br[NT]; int bdelta[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
-    const int n = nt * 16 + i;
-    bok[nt] = n < w.N;
-    const int nn = bok[nt] ? n : 0;
-    if (MODE == NLT_DECONV_K2S2) {
-      const int ab = nn / p.cout;
-      boff[nt] = nn - ab * p.cout;
-      bdelta[nt] = (ab >> 1) * p.ow + (ab & 1);
-    } else {
-      boff[nt] = nn;
-      bdelta[nt] = 0;
-    }
+    br[nt] = BRole<MODE>(nt * 16 + i, w.N, p);
+    bdelta[nt] = (br[nt].ab >> 1) * p.ow + (br[nt].ab & 1);
   }
 
-  f32x4 acc[MQ][4][NT];
+  f32x4 acc[MQ * 4 * NT];                                              // [mq][e][nt]
   float bsum[NT];
 #pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    bsum[nt] = 0.f;
+  for (int nt = 0; nt < NT; ++nt) bsum[nt] = 0.f;
 #pragma unroll
-    for (int mq = 0; mq < MQ; ++mq)
+  for (int j = 0; j < MQ * 4 * NT; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  auto compute = [&](const f32x4 (&av)[MQ], const float (&bv)[NT]) {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc[mq][e][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  }
+    for (int nt = 0; nt < NT; ++nt) {
+      bsum[nt] += bv[nt];
+#pragma unroll
+      for (int mq = 0; mq < MQ; ++mq)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          acc[(mq * 4 + e) * NT + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mq][e], bv[nt], acc[(mq * 4 + e) * NT + nt], 0, 0, 0);
+    }
+  };
 
   if constexpr (WALK) {
-    const int wvu = __builtin_amdgcn_readfirstlane(wv);
-    const int chunk = w.rows_per_split >> 2;                           // multiple of 4 * PF rows
-    const int m0 = __builtin_amdgcn_readfirstlane(ms * w.rows_per_split + wvu * chunk);
-    int m1 = m0 + chunk;
-    if (m1 > p.M) m1 = p.M;
-    const int nsteps = m1 > m0 ? (m1 - m0) >> 2 : 0;
-    int x0 = m0 % p.gw;                                                // wave-uniform position of the step's first row
-    const int R0 = m0 / p.gw;
-    int y = R0 % p.gh;
-    const float* pa[MQ]; int ainc[MQ], aincw[MQ], xlim[MQ], ylim[MQ], xlo[MQ], ylo[MQ];
+    using Walk = RowWalk<MODE>;
+    Walk k;
+    k.start(ms, __builtin_amdgcn_readfirstlane(wv), w.rows_per_split, p);   // (rows_per_split: a multiple of 16 * PF rows)
+    const float* pa[MQ]; int ainc[MQ], aincw[MQ]; typename Walk::TapBounds tb[MQ];
 #pragma unroll
     for (int mq = 0; mq < MQ; ++mq) {
       const int a = oy[mq] < 0 ? -oy[mq] : oy[mq], b = ox[mq] < 0 ? -ox[mq] : ox[mq];
-      long tex;
-      if (MODE == NLT_CONV_K2S2) tex = (long)(2 * R0 + a) * p.w + 2 * (x0 + kk) + b;
-      else tex = (long)m0 + kk + tdelta[mq];
-      pa[mq] = nsteps > 0 ? ap[mq] + tex * ald[mq] : ap[mq];           // an empty run (slice past M) must not form an address past the buffer
-      ainc[mq] = (MODE == NLT_CONV_K2S2 ? 8 : 4) * ald[mq];
-      aincw[mq] = MODE == NLT_CONV_K2S2 ? (8 + p.w) * ald[mq] : ainc[mq];
-      xlim[mq] = p.gw - kk - b; ylim[mq] = p.gh - a;                   // k2s1: valid iff x0 < xlim && y < ylim
-      xlo[mq] = b - kk; ylo[mq] = a;                                   // transposed k2s1: valid iff x0 >= xlo && y >= ylo
+      // an empty run (slice past M) must not form an address past the buffer
+      pa[mq] = k.nsteps > 0 ? ar[mq].src + k.a_start_texel(a, b, kk, p) * ar[mq].ld : ar[mq].src;
+      ainc[mq] = Walk::a_inc(ar[mq].ld);
+      aincw[mq] = Walk::a_inc_wrap(ar[mq].ld, p);
+      tb[mq] = Walk::tap_bounds(a, b, kk, p);
     }
     const float* pb[NT]; int binc[NT], bincw[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      long otex;
-      if (MODE == NLT_DECONV_K2S2) otex = (long)(2 * R0) * p.ow + 2 * (x0 + kk) + bdelta[nt];
-      else otex = (long)m0 + kk;
-      pb[nt] = nsteps > 0 ? w.dp + otex * w.ldp + boff[nt] : w.zeros;
-      binc[nt] = (MODE == NLT_DECONV_K2S2 ? 8 : 4) * w.ldp;
-      bincw[nt] = MODE == NLT_DECONV_K2S2 ? (8 + p.ow) * w.ldp : binc[nt];
+      pb[nt] = k.nsteps > 0 ? w.dp + k.b_start_texel(br[nt].ab, kk, p) * w.ldp + br[nt].off : w.zeros;
+      binc[nt] = Walk::b_inc(w.ldp);
+      bincw[nt] = Walk::b_inc_wrap(w.ldp, p);
     }
     const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    int issued = 0;
     auto issue = [&](f32x4 (&av)[MQ], float (&bv)[NT]) {
 #pragma unroll
       for (int mq = 0; mq < MQ; ++mq) {
-        if (MODE == NLT_CONV_K2S1 || MODE == NLT_DECONV_K2S1) {
-          const bool ok = MODE == NLT_CONV_K2S1 ? (x0 < xlim[mq] && y < ylim[mq]) : (x0 >= xlo[mq] && y >= ylo[mq]);
-          const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? pa[mq] : ap[mq]);   // a padded tap must not be dereferenced
+        if (Walk::PADS) {
+          const bool ok = MODE == NLT_CONV_K2S1 ? (k.x0 < tb[mq].xlim && k.y < tb[mq].ylim) : (k.x0 >= tb[mq].xlo && k.y >= tb[mq].ylo);
+          const f32x4 v = *reinterpret_cast<const f32x4*>(ok ? pa[mq] : ar[mq].src);   // a padded tap must not be dereferenced
           av[mq] = ok ? v : zero4;
         } else {
           av[mq] = *reinterpret_cast<const f32x4*>(pa[mq]);
@@ -300,10 +206,7 @@ __global__ __launch_bounds__(256) void wgrad_narrowq_kernel(WN w) {
       }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) bv[nt] = *pb[nt];
-      ++issued;
-      const bool adv = issued < nsteps;                                // everything below is wave-uniform
-      const int xn = x0 + 4;
-      const bool wrap = xn >= p.gw;
+      const bool adv = k.advances(), wrap = k.wraps(p);
 #pragma unroll
       for (int mq = 0; mq < MQ; ++mq) {
         const float* nx = pa[mq] + (wrap ? aincw[mq] : ainc[mq]);
@@ -314,148 +217,48 @@ __global__ __launch_bounds__(256) void wgrad_narrowq_kernel(WN w) {
         const float* nx = pb[nt] + (wrap ? bincw[nt] : binc[nt]);
         pb[nt] = adv ? nx : w.zeros;
       }
-      const int yn = y + 1 >= p.gh ? 0 : y + 1;
-      y = (adv && wrap) ? yn : y;
-      x0 = adv ? (wrap ? 0 : xn) : x0;
+      k.move_on(adv, wrap, p);
     };
-    auto compute = [&](const f32x4 (&av)[MQ], const float (&bv)[NT]) {
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        bsum[nt] += bv[nt];
-#pragma unroll
-        for (int mq = 0; mq < MQ; ++mq)
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            acc[mq][e][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mq][e], bv[nt], acc[mq][e][nt], 0, 0, 0);
-      }
-    };
-    constexpr int PF = NarrowPF<MQ, NT>::value;
-    f32x4 av[PF][MQ];
-    float bv[PF][NT];
-#pragma unroll
-    for (int j = 0; j < PF - 1; ++j) issue(av[j], bv[j]);
-    for (int s0 = 0; s0 < nsteps; s0 += PF) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        issue(av[(j + PF - 1) % PF], bv[(j + PF - 1) % PF]);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(av[j], bv[j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
+    k.template pipeline<NarrowPF<MQ, NT>::value, f32x4[MQ], float[NT]>(issue, compute);
   } else {
-    const int m_begin = ms * w.rows_per_split;
-    int m_end = m_begin + w.rows_per_split;
-    if (m_end > p.M) m_end = p.M;
-    int m = m_begin + 4 * wv + kk;
-    int rx, ry, rf;
-    {
-      const int mc = m < p.M ? m : p.M - 1;
-      rx = mc % p.gw; ry = (mc / p.gw) % p.gh; rf = mc / (p.gw * p.gh);
-    }
+    RowCursor c;
+    c.init(ms * w.rows_per_split, w.rows_per_split, wv, kk, p);
     auto issue = [&](f32x4 (&av)[MQ], float (&bv)[NT]) {
-      const bool rv = m < m_end;
-      const int ys = S * ry, xs = S * rx;
-      const int rowtex = (rf * p.h + ys) * p.w + xs;
-  #pragma unroll
+      const bool rv = c.valid();
+      const int ys = S * c.ry, xs = S * c.rx;
+      const int rowtex = (c.rf * p.h + ys) * p.w + xs;
+#pragma unroll
       for (int mq = 0; mq < MQ; ++mq) {
-        const bool ok = rv && aok[mq] && (unsigned)(ys + oy[mq]) < (unsigned)p.h && (unsigned)(xs + ox[mq]) < (unsigned)p.w;
+        const bool ok = rv && ar[mq].ok && (unsigned)(ys + oy[mq]) < (unsigned)p.h && (unsigned)(xs + ox[mq]) < (unsigned)p.w;
         const int tex = ok ? rowtex + tdelta[mq] : 0;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(ap[mq] + (size_t)tex * ald[mq]);   // unconditional, clamped address
+        const f32x4 v = *reinterpret_cast<const f32x4*>(ar[mq].src + (size_t)tex * ar[mq].ld);   // unconditional, clamped address
         av[mq] = ok ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
       }
-      const int rowo = MODE == NLT_DECONV_K2S2 ? (rf * p.oh + 2 * ry) * p.ow + 2 * rx : m;
-  #pragma unroll
+      const int rowo = MODE == NLT_DECONV_K2S2 ? (c.rf * p.oh + 2 * c.ry) * p.ow + 2 * c.rx : c.m;
+#pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        const bool ok = rv && bok[nt];
+        const bool ok = rv && br[nt].ok;
         const int otex = ok ? rowo + bdelta[nt] : 0;
-        const float v = w.dp[(size_t)otex * w.ldp + boff[nt]];
+        const float v = w.dp[(size_t)otex * w.ldp + br[nt].off];
         bv[nt] = ok ? v : 0.f;
       }
-      m += 16; rx += 16;
-  #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const bool wx = rx >= p.gw;
-        rx -= wx ? p.gw : 0;
-        ry += wx ? 1 : 0;
-        const bool wy = ry >= p.gh;
-        ry = wy ? 0 : ry;
-        rf += wy ? 1 : 0;
-      }
+      c.advance16(p);
     };
-    auto compute = [&](const f32x4 (&av)[MQ], const float (&bv)[NT]) {
-  #pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        bsum[nt] += bv[nt];
-  #pragma unroll
-        for (int mq = 0; mq < MQ; ++mq)
-  #pragma unroll
-          for (int e = 0; e < 4; ++e)
-            acc[mq][e][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mq][e], bv[nt], acc[mq][e][nt], 0, 0, 0);
-      }
-    };
-    const int first = m_begin + 4 * wv;
-    const int nsteps = first < m_end ? (m_end - first + 15) / 16 : 0;
-    f32x4 a0[MQ], a1[MQ], a2[MQ];
-    float b0[NT], b1[NT], b2[NT];
-    issue(a0, b0);
-    issue(a1, b1);
-    for (int s3 = 0; s3 < nsteps; s3 += 3) {
-      issue(a2, b2); compute(a0, b0);
-      issue(a0, b0); compute(a1, b1);
-      issue(a1, b1); compute(a2, b2);
-    }
+    c.template rotate3<f32x4[MQ], float[NT]>(issue, compute);
   }
 
-  constexpr int NC = NT * 16, KN = MT * 16 * NC;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    bsum[nt] += __shfl_xor(bsum[nt], 16);
-    bsum[nt] += __shfl_xor(bsum[nt], 32);
-  }
-  // K index of accumulator (mq, e), D row 4 kk + r:  4 * (16 mq + 4 kk + r) + e
-  for (int src = 1; src < 4; ++src) {
-    if (wv == src) {
-#pragma unroll
-      for (int mq = 0; mq < MQ; ++mq)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xch[(4 * (16 * mq + 4 * kk + r) + e) * NC + nt * 16 + i] = acc[mq][e][nt][r];
-      if (kk == 0)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) xch[KN + nt * 16 + i] = bsum[nt];
-    }
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-      for (int mq = 0; mq < MQ; ++mq)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[mq][e][nt][r] += xch[(4 * (16 * mq + 4 * kk + r) + e) * NC + nt * 16 + i];
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) bsum[nt] += xch[KN + nt * 16 + i];
-    }
-    __syncthreads();
-  }
+  // waves 1..3 hand their blocks to wave 0 one after the other; K index of accumulator (mq, e), D row 4 kk + r:  4 * (16 mq + 4 kk + r) + e
+  ColumnSums<NT> cols{bsum, Blk::KN + i, kk == 0};
+  cols.across_row_groups();
+  auto slot = [i, kk](int j, int r) {
+    const int nt = j % NT, e = (j / NT) % 4, mq = j / (NT * 4);
+    return (4 * (16 * mq + 4 * kk + r) + e) * Blk::NC + nt * 16 + i;
+  };
+  wave_order_sum(xch, wv, acc, slot, cols);
   if (wv) return;
-  float* dst = w.ws + (size_t)ms * (KN + NC);
-#pragma unroll
-  for (int mq = 0; mq < MQ; ++mq)
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[(4 * (16 * mq + 4 * kk + r) + e) * NC + nt * 16 + i] = acc[mq][e][nt][r];
-  if (kk == 0)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) dst[KN + nt * 16 + i] = bsum[nt];
+  float* dst = w.ws + (size_t)ms * Blk::PER;
+  store_block(dst, acc, slot);
+  cols.put(dst);
 }
 
 // Pass 2: 32 entries of the [K pad][N pad] block (+ the column sums) per workgroup: thread (q, g) adds the slices g, g + 32, ...
@@ -464,7 +267,8 @@ __global__ __launch_bounds__(256) void wgrad_narrowq_kernel(WN w) {
 template <int MODE, int MT, int NT>
 __global__ __launch_bounds__(256) void wgrad_narrow_reduce_kernel(WN w) {
   __shared__ __attribute__((aligned(16))) float part[32][32];
-  constexpr int NC = NT * 16, KN = MT * 16 * NC, PER = KN + NC;          // PER is a multiple of 16
+  using Blk = NarrowBlock<MT, NT>;
+  constexpr int NC = Blk::NC, KN = Blk::KN, PER = Blk::PER;             // PER is a multiple of 16
   const ConvP& p = w.c;
   const int q = threadIdx.x & 7, g = threadIdx.x >> 3;
   const int base = blockIdx.x * 32 + 4 * q;
@@ -500,7 +304,7 @@ __global__ __launch_bounds__(256) void wgrad_narrow_reduce_kernel(WN w) {
     const int kidx = idx / NC, n = idx - kidx * NC;
     if (kidx >= w.K || n >= w.N) return;
     const int tap = kidx / cin, c = kidx - tap * cin;
-    w.dw[keras_widx_n<MODE>(tap, c, n, cin, p.cout)] += s;
+    w.dw[nlt_keras_widx<MODE>(tap, c, n, cin, p.cout, p.cout, 0)] += s;
   } else if (w.db) {
     const int n = idx - KN;
     if (n >= w.N) return;
@@ -512,21 +316,26 @@ __global__ __launch_bounds__(256) void wgrad_narrow_reduce_kernel(WN w) {
 // Conv2DTranspose k2s2 bias: db[o] = sum_ab colsum[ab * cout + o]
 template <int MT, int NT>
 __global__ void wgrad_narrow_bias_k2s2_kernel(WN w) {
-  constexpr int NC = NT * 16, KN = MT * 16 * NC, PER = KN + NC;
   const int o = threadIdx.x;
   if (o >= w.c.cout) return;
-  const float* tot = w.ws + (size_t)w.msplits * PER;
+  const float* tot = w.ws + (size_t)w.msplits * NarrowBlock<MT, NT>::PER;
   w.db[o] += (tot[o] + tot[w.c.cout + o]) + (tot[2 * w.c.cout + o] + tot[3 * w.c.cout + o]);
+}
+
+// Pass 2 and what follows it, after any of the slice kernels
+template <int MODE, int MT, int NT>
+int narrow_tail(WN& w, hipStream_t s) {
+  hipLaunchKernelGGL((wgrad_narrow_reduce_kernel<MODE, MT, NT>), dim3((NarrowBlock<MT, NT>::PER + 31) / 32), dim3(256), 0, s, w);
+  if (MODE == NLT_DECONV_K2S2 && w.db) hipLaunchKernelGGL((wgrad_narrow_bias_k2s2_kernel<MT, NT>), dim3(1), dim3(64), 0, s, w);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
 }
 
 template <int MODE, int MT, int NT>
 int run_narrow(WN& w, hipStream_t s) {
-  constexpr int PER = MT * 16 * NT * 16 + NT * 16;
-  hipLaunchKernelGGL((wgrad_narrow_kernel<MODE, MT, NT>), dim3((unsigned)w.msplits), dim3(256), PER * sizeof(float), s, w);
-  hipLaunchKernelGGL((wgrad_narrow_reduce_kernel<MODE, MT, NT>), dim3((PER + 31) / 32), dim3(256), 0, s, w);
-  if (MODE == NLT_DECONV_K2S2 && w.db) hipLaunchKernelGGL((wgrad_narrow_bias_k2s2_kernel<MT, NT>), dim3(1), dim3(64), 0, s, w);
-  NLT_CHECK_LAUNCH();
-  return NLT_OK;
+  constexpr size_t lds = NarrowBlock<MT, NT>::PER * sizeof(float);
+  hipLaunchKernelGGL((wgrad_narrow_kernel<MODE, MT, NT>), dim3((unsigned)w.msplits), dim3(256), lds, s, w);
+  return narrow_tail<MODE, MT, NT>(w, s);
 }
 
 // The row-walking loop pays for every shape except the k2s1 families at K = 128, N = 32 (two A quads x two column tiles: 260 VALU
@@ -538,16 +347,13 @@ inline bool narrow_walks(int mode, int K, int N, int gw) {
 
 template <int MODE, int MQ, int NT>
 int run_narrowq(WN& w, hipStream_t s) {
-  constexpr int MT = 4 * MQ, PER = MT * 16 * NT * 16 + NT * 16;
+  constexpr size_t lds = NarrowBlock<4 * MQ, NT>::PER * sizeof(float);
   w.zeros = narrow_walks(MODE, w.K, w.N, w.c.gw) ? nlt_zero_page() : nullptr;
   if (w.zeros)
-    hipLaunchKernelGGL((wgrad_narrowq_kernel<MODE, MQ, NT, true>), dim3((unsigned)w.msplits), dim3(256), PER * sizeof(float), s, w);
+    hipLaunchKernelGGL((wgrad_narrowq_kernel<MODE, MQ, NT, true>), dim3((unsigned)w.msplits), dim3(256), lds, s, w);
   else
-    hipLaunchKernelGGL((wgrad_narrowq_kernel<MODE, MQ, NT, false>), dim3((unsigned)w.msplits), dim3(256), PER * sizeof(float), s, w);
-  hipLaunchKernelGGL((wgrad_narrow_reduce_kernel<MODE, MT, NT>), dim3((PER + 31) / 32), dim3(256), 0, s, w);
-  if (MODE == NLT_DECONV_K2S2 && w.db) hipLaunchKernelGGL((wgrad_narrow_bias_k2s2_kernel<MT, NT>), dim3(1), dim3(64), 0, s, w);
-  NLT_CHECK_LAUNCH();
-  return NLT_OK;
+    hipLaunchKernelGGL((wgrad_narrowq_kernel<MODE, MQ, NT, false>), dim3((unsigned)w.msplits), dim3(256), lds, s, w);
+  return narrow_tail<MODE, 4 * MQ, NT>(w, s);
 }
 
 template <int MODE>
@@ -558,12 +364,17 @@ int dispatchq(WN& w, int mq, int nt, hipStream_t s) {
 
 template <int MODE>
 int dispatch(WN& w, int mt, int nt, hipStream_t s) {
-#define NLT_WN(M_, N_) if (mt == M_ && nt == N_) return run_narrow<MODE, M_, N_>(w, s);
-  NLT_WN(2, 1) NLT_WN(4, 1) NLT_WN(8, 1) NLT_WN(2, 2) NLT_WN(4, 2) NLT_WN(8, 2)
-#undef NLT_WN
+  if (nt == 1) {
+    if (mt == 2) return run_narrow<MODE, 2, 1>(w, s);
+    if (mt == 4) return run_narrow<MODE, 4, 1>(w, s);
+    if (mt == 8) return run_narrow<MODE, 8, 1>(w, s);
+  } else if (nt == 2) {
+    if (mt == 2) return run_narrow<MODE, 2, 2>(w, s);
+    if (mt == 4) return run_narrow<MODE, 4, 2>(w, s);
+    if (mt == 8) return run_narrow<MODE, 8, 2>(w, s);
+  }
   return NLT_ERR_UNSUPPORTED;
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // r05: the stride-1 k2 layers with 16 / 32 channels in and out (levels 1 and 2 of both paths, the 16- and 32-channel expanding
@@ -593,7 +404,8 @@ template <int MODE, int C>
 __global__ __launch_bounds__(256) void wgrad_s1t_kernel(WN w, int tiles_x, int tiles_y, int ntiles) {
   using TT = S1T<C>;
   constexpr int Q = TT::Q, NX = TT::NX, ND = TT::ND, T = TT::T, S1_TW = TT::TW, S1_XW = TT::XW;
-  constexpr int NC = C, KN = 4 * C * NC, PER = KN + NC;
+  using Blk = NarrowBlock<4 * T, T>;
+  constexpr int NC = Blk::NC, KN = Blk::KN;
   extern __shared__ __attribute__((aligned(16))) float s1_lds[];
   float* const xs = s1_lds;
   float* const ds = s1_lds + TT::XF;
@@ -648,17 +460,17 @@ __global__ __launch_bounds__(256) void wgrad_s1t_kernel(WN w, int tiles_x, int t
     }
   };
 
-  f32x4 acc[4][T][T];
+  f32x4 acc[4 * T * T];                                                 // [tap][mt][nt]
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int mt = 0; mt < T; ++mt)
 #pragma unroll
-      for (int nt = 0; nt < T; ++nt) acc[t][mt][nt] = zero4;
+      for (int nt = 0; nt < T; ++nt) acc[(t * T + mt) * T + nt] = zero4;
   f32x4 bsum = zero4;                                                   // column sums of dP: this thread's channel quad (tid % Q)
 
   // LDS read offsets of this lane (texel = step * 4 + kk of row wv)
-  int a_off[4], sw_a[T], sw_b[T];
+  int a_off[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int a = t >> 1, b = t & 1;
@@ -700,51 +512,22 @@ __global__ __launch_bounds__(256) void wgrad_s1t_kernel(WN w, int tiles_x, int t
           const int c = 16 * mt + i;
           const float av = xs[at * C + (C == 32 ? (c ^ ((at & 1) << 4)) : c)];
 #pragma unroll
-          for (int nt = 0; nt < T; ++nt) acc[t][mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[nt], acc[t][mt][nt], 0, 0, 0);
+          for (int nt = 0; nt < T; ++nt) acc[(t * T + mt) * T + nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[nt], acc[(t * T + mt) * T + nt], 0, 0, 0);
         }
       }
     }
     __syncthreads();                                                   // the tile is consumed: LDS may be overwritten
   }
-  (void)sw_a; (void)sw_b;
 
   // ---- the four waves' blocks, added in wave order (fixed -> deterministic), then the workgroup's block to the workspace
   float* const xch = s1_lds;                                           // [K][NC] + column sums
-  for (int src = 1; src < 4; ++src) {
-    if (wv == src) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mt = 0; mt < T; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < T; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xch[(t * C + 16 * mt + 4 * kk + r) * NC + 16 * nt + i] = acc[t][mt][nt][r];
-    }
-    __syncthreads();
-    if (wv == 0) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int mt = 0; mt < T; ++mt)
-#pragma unroll
-          for (int nt = 0; nt < T; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][mt][nt][r] += xch[(t * C + 16 * mt + 4 * kk + r) * NC + 16 * nt + i];
-    }
-    __syncthreads();
-  }
-  float* dst = w.ws + (size_t)blockIdx.x * PER;
-  if (wv == 0) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int mt = 0; mt < T; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < T; ++nt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dst[(t * C + 16 * mt + 4 * kk + r) * NC + 16 * nt + i] = acc[t][mt][nt][r];
-  }
+  auto slot = [i, kk](int j, int r) {                                  // accumulator (t, mt, nt), D row 4 kk + r
+    const int nt = j % T, mt = (j / T) % T, t = j / (T * T);
+    return (t * C + 16 * mt + 4 * kk + r) * NC + 16 * nt + i;
+  };
+  wave_order_sum(xch, wv, acc, slot, NoColumnSums{});
+  float* dst = w.ws + (size_t)blockIdx.x * Blk::PER;
+  if (wv == 0) store_block(dst, acc, slot);
   // column sums: thread t holds the sums of channel quad t % Q over its texels; added over the 256 / Q threads of a quad in thread order
   *reinterpret_cast<f32x4*>(xch + KN + 4 * tid) = bsum;                 // (K * NC <= the X tile: room for 1024 floats behind it)
   __syncthreads();
@@ -787,12 +570,22 @@ int run_s1t(WN& w, hipStream_t s) {
   }();
   if (!attr) return NLT_ERR_LAUNCH;
   hipLaunchKernelGGL((wgrad_s1t_kernel<MODE, C>), dim3((unsigned)w.msplits), dim3(256), lds, s, w, tx, ty, ntiles);
-  hipLaunchKernelGGL((wgrad_narrow_reduce_kernel<MODE, MT, NT>), dim3((MT * 16 * NT * 16 + NT * 16 + 31) / 32), dim3(256), 0, s, w);
-  NLT_CHECK_LAUNCH();
-  return NLT_OK;
+  return narrow_tail<MODE, MT, NT>(w, s);
 }
 
 int tiles_m(int K) { return K <= 32 ? 2 : (K <= 64 ? 4 : 8); }
+
+// f(std::integral_constant<int, MODE>) for the four families of the narrow entry point
+template <class F>
+int with_mode(int mode, F&& f) {
+  switch (mode) {
+    case NLT_CONV_K2S2: return f(std::integral_constant<int, NLT_CONV_K2S2>{});
+    case NLT_CONV_K2S1: return f(std::integral_constant<int, NLT_CONV_K2S1>{});
+    case NLT_DECONV_K2S2: return f(std::integral_constant<int, NLT_DECONV_K2S2>{});
+    case NLT_DECONV_K2S1: return f(std::integral_constant<int, NLT_DECONV_K2S1>{});
+  }
+  return NLT_ERR_BAD_ARG;
+}
 
 int prepare_narrow(WN& w, int mode, const float* src0, int ld0, int c0, const float* src1, int ld1, int c1, int n, int h, int wd,
                    const float* dpre, int ldp, int cout, float* dw, float* db, long* ws_floats) {
@@ -852,27 +645,15 @@ extern "C" int nlt_conv_backward_weights_narrow(int mode,
   if (workspace_floats < need || !nlt_aligned16(workspace)) return NLT_ERR_BAD_ARG;
   t.ws = workspace;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (t.rows_per_split == 0) {                                          // (prepare_narrow chose the LDS-tiled form)
-    if (mode == NLT_CONV_K2S1) return cout == 16 ? run_s1t<NLT_CONV_K2S1, 16>(t, s) : run_s1t<NLT_CONV_K2S1, 32>(t, s);
-    return cout == 16 ? run_s1t<NLT_DECONV_K2S1, 16>(t, s) : run_s1t<NLT_DECONV_K2S1, 32>(t, s);
-  }
   const int mt = tiles_m(t.K), nt = t.N <= 16 ? 1 : 2;
   const bool quads = !(c0 & 3) && !(c1 & 3) && !(ld0 & 3) && (c1 == 0 || !(ld1 & 3)) && nlt_aligned16(src0) &&
                      (c1 == 0 || nlt_aligned16(src1));
-  if (quads && t.K > 32) {                                           // (K <= 32: two scalar row tiles beat four half-empty quad tiles)
-    const int mq = t.K <= 64 ? 1 : 2;
-    switch (mode) {
-      case NLT_CONV_K2S2: return dispatchq<NLT_CONV_K2S2>(t, mq, nt, s);
-      case NLT_CONV_K2S1: return dispatchq<NLT_CONV_K2S1>(t, mq, nt, s);
-      case NLT_DECONV_K2S2: return dispatchq<NLT_DECONV_K2S2>(t, mq, nt, s);
-      case NLT_DECONV_K2S1: return dispatchq<NLT_DECONV_K2S1>(t, mq, nt, s);
-    }
-  }
-  switch (mode) {
-    case NLT_CONV_K2S2: return dispatch<NLT_CONV_K2S2>(t, mt, nt, s);
-    case NLT_CONV_K2S1: return dispatch<NLT_CONV_K2S1>(t, mt, nt, s);
-    case NLT_DECONV_K2S2: return dispatch<NLT_DECONV_K2S2>(t, mt, nt, s);
-    case NLT_DECONV_K2S1: return dispatch<NLT_DECONV_K2S1>(t, mt, nt, s);
-  }
-  return NLT_ERR_BAD_ARG;
+  return with_mode(mode, [&](auto m) {
+    constexpr int MODE = decltype(m)::value;
+    if constexpr (MODE == NLT_CONV_K2S1 || MODE == NLT_DECONV_K2S1)
+      if (t.rows_per_split == 0)                                         // (prepare_narrow chose the LDS-tiled form)
+        return cout == 16 ? run_s1t<MODE, 16>(t, s) : run_s1t<MODE, 32>(t, s);
+    if (quads && t.K > 32) return dispatchq<MODE>(t, t.K <= 64 ? 1 : 2, nt, s);   // (K <= 32: two scalar row tiles beat four half-empty quad tiles)
+    return dispatch<MODE>(t, mt, nt, s);
+  });
 }

@@ -10,17 +10,10 @@
 // Row slices write their partial blocks to a workspace with 16-byte stores; a second launch adds the slices in
 // order and accumulates into the Keras-layout gradient -- deterministic, and no atomics (the first-generation
 // kernel's thousands of waves adding into the 64 addresses of a 4 -> 4 layer were its bottleneck).
-#include "nlt_common.h"
+#include "wgrad_common.h"
 #include <cstdlib>
 
 namespace {
-
-template <int MODE>
-__device__ __forceinline__ long keras_widx(int t, int c, int ncol, int cin, int cout) {
-  if (MODE == NLT_CONV1X1 || MODE == NLT_CONV_K2S2 || MODE == NLT_CONV_K2S1) return ((long)t * cin + c) * cout + ncol;
-  if (MODE == NLT_DECONV_K2S1) return ((long)t * cout + ncol) * cin + c;
-  return (long)ncol * cin + c;   // DECONV_K2S2: ncol = (a*2+b)*cout + o
-}
 
 struct WT {
   ConvP c;            // geometry + X sources
@@ -54,284 +47,122 @@ __device__ __forceinline__ bool wgrad_block(const WT& w, int& ms, int& kb, int& 
   return ms < w.msplits;
 }
 
-template <int MODE>
-__global__ __launch_bounds__(256) void wgrad_tile_kernel(WT w) {
-  __shared__ __attribute__((aligned(16))) f32x4 part[3][17][64];      // waves 1..3 -> wave 0 (16 blocks + bias sums)
-  const ConvP& p = w.c;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  int ms, kb, nb;                                                    // one workgroup = one (row slice, kb, nb)
-  if (!wgrad_block(w, ms, kb, nb)) return;
-  const int i = lane & 15, kk = lane >> 4;
-  const int q0 = p.c0 >> 2, qpt = (p.c0 + p.c1) >> 2;
-
-  // A role: this lane's k-quad = (tap, channel quad of the virtual concat)
-  const int kq = kb * 16 + i;
-  const bool a_ok = kq < w.kq;
-  const int tap = a_ok ? kq / qpt : 0;
-  const int cq = a_ok ? kq - tap * qpt : 0;
-  const bool from1 = cq >= q0;
-  const float* asrc = from1 ? p.src1 + 4 * (cq - q0) : p.src0 + 4 * cq;
-  const int ald = from1 ? p.ld1 : p.ld0;
-  // B role: this lane's n-quad
-  const int nq = nb * 16 + i;
-  const bool b_ok = nq < w.nq;
-  const int ncol = b_ok ? 4 * nq : 0;
-  const int ab = MODE == NLT_DECONV_K2S2 ? ncol / p.cout : 0;
-  const int oc = MODE == NLT_DECONV_K2S2 ? ncol - ab * p.cout : ncol;
-
-  f32x4 acc[4][4];
+// What both kernels of a block share: 16 accumulators acc[e * 4 + f] + bias sums per lane, the MFMA step, and the way out
+// (waves 1..3 -> wave 0 in wave order -> workspace [ms][kb][nb][e][f][lane], f32x4 = the 4 D rows this lane holds).
+__device__ __forceinline__ void tile_mfma(f32x4 (&acc)[16], f32x4& bsum, const f32x4& av, const f32x4& bv) {
+  bsum += bv;
 #pragma unroll
   for (int e = 0; e < 4; ++e)
 #pragma unroll
-    for (int f = 0; f < 4; ++f) acc[e][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  f32x4 bsum = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int f4 = 0; f4 < 4; ++f4)
+      acc[e * 4 + f4] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[f4], acc[e * 4 + f4], 0, 0, 0);
+}
 
-  // The slice's rows are dealt to the 4 waves in steps of 4 rows (wave wv takes steps wv, wv + 4, ...).  Operand
-  // loads run two steps ahead of the MFMAs (three register sets), and the (frame, y, x) of a lane's row is advanced
-  // incrementally instead of being re-derived by integer division every step.
-  const int m_begin = ms * w.rows_per_split;
-  int m_end = m_begin + w.rows_per_split;
-  if (m_end > p.M) m_end = p.M;
-  int m = m_begin + 4 * wv + kk;                                   // this lane's row of the NEXT step to be loaded
-  int rx, ry, rf;
-  {
-    const int mc = m < p.M ? m : p.M - 1;
-    rx = mc % p.gw; ry = (mc / p.gw) % p.gh; rf = mc / (p.gw * p.gh);
-  }
-  auto issue = [&](f32x4& av, f32x4& bv) {
-    const bool rv = m < m_end;
-    const int tex = conv_tap_texel<MODE>(p, rf, ry, rx, tap);
-    const size_t tx = (rv && tex >= 0) ? (size_t)tex : 0;
-    av = *reinterpret_cast<const f32x4*>(asrc + tx * ald);                      // unconditional, clamped address
-    if (!(rv && a_ok && tex >= 0)) av = (f32x4){0.f, 0.f, 0.f, 0.f};
-    size_t otex = rv ? ((size_t)rf * p.gh + ry) * p.gw + rx : 0;
-    if (MODE == NLT_DECONV_K2S2) otex = rv ? ((size_t)rf * p.oh + 2 * ry + (ab >> 1)) * p.ow + 2 * rx + (ab & 1) : 0;
-    bv = *reinterpret_cast<const f32x4*>(w.dp + otex * w.ldp + oc);
-    if (!(rv && b_ok)) bv = (f32x4){0.f, 0.f, 0.f, 0.f};
-    m += 16; rx += 16;                                               // the wave's next step is 16 rows further
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {                                    // gw >= 4 (checked by the host): at most 4 wraps, branch-free
-      const bool wx = rx >= p.gw;
-      rx -= wx ? p.gw : 0;
-      ry += wx ? 1 : 0;
-      const bool wy = ry >= p.gh;
-      ry = wy ? 0 : ry;
-      rf += wy ? 1 : 0;
-    }
-  };
-  auto compute = [&](const f32x4& av, const f32x4& bv) {
-    bsum += bv;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int f4 = 0; f4 < 4; ++f4)
-        acc[e][f4] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[f4], acc[e][f4], 0, 0, 0);
-  };
-  const int first = m_begin + 4 * wv;
-  const int nsteps = first < m_end ? (m_end - first + 15) / 16 : 0;
-  f32x4 a0, b0, a1, b1, a2, b2;
-  issue(a0, b0);
-  issue(a1, b1);
-  for (int s3 = 0; s3 < nsteps; s3 += 3) {                           // steps past nsteps carry zero operands
-    issue(a2, b2); compute(a0, b0);
-    issue(a0, b0); compute(a1, b1);
-    issue(a1, b1); compute(a2, b2);
-  }
-
-  // the 4 waves' partial blocks are added in wave order (fixed -> deterministic) through LDS ...
-  if (wv > 0) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int f = 0; f < 4; ++f) part[wv - 1][e * 4 + f][lane] = acc[e][f];
-    part[wv - 1][16][lane] = bsum;
-  }
-  __syncthreads();
+__device__ __forceinline__ void tile_finish(const WT& w, f32x4* part, int wv, int lane, int ms, int kb, int nb, f32x4 (&acc)[16],
+                                            f32x4& bsum) {
+  auto slot = [lane](int j) { return j * 64 + lane; };
+  wave_order_sum(part, wv, lane, acc, bsum, slot);
   if (wv > 0) return;
-#pragma unroll
-  for (int o = 0; o < 3; ++o) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int f = 0; f < 4; ++f) acc[e][f] += part[o][e * 4 + f][lane];
-    bsum += part[o][16][lane];
-  }
-  // ... and the slice's block goes to the workspace [ms][kb][nb][e][f][lane] (f32x4 = the 4 D rows this lane holds)
-  f32x4* dst = reinterpret_cast<f32x4*>(w.ws) + ((((size_t)ms * w.kblocks + kb) * w.nblocks + nb) * 16) * 64 + lane;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-#pragma unroll
-    for (int f = 0; f < 4; ++f) dst[(e * 4 + f) * 64] = acc[e][f];
+  store_block(reinterpret_cast<f32x4*>(w.ws) + (((size_t)ms * w.kblocks + kb) * w.nblocks + nb) * 16 * 64, acc, slot);
   if (w.wsb && kb == 0) {                                                       // column sums of dP for the bias
 #pragma unroll
     for (int f = 0; f < 4; ++f) {
       bsum[f] += __shfl_xor(bsum[f], 16);
       bsum[f] += __shfl_xor(bsum[f], 32);
     }
-    if (kk == 0) reinterpret_cast<f32x4*>(w.wsb)[((size_t)ms * w.nblocks + nb) * 16 + i] = bsum;
+    if ((lane >> 4) == 0) reinterpret_cast<f32x4*>(w.wsb)[((size_t)ms * w.nblocks + nb) * 16 + (lane & 15)] = bsum;
   }
 }
 
-// The same block, with the rows WALKED instead of re-derived (the form used whenever the row grid is a multiple of 4
-// texels wide -- every released shape).  The generic kernel above spends ~70 VALU instructions per 16-MFMA step on
-// (frame, y, x) bookkeeping, 64-bit multiplies for two addresses and exec-masked loads; with two waves per SIMD that
-// address arithmetic, not the matrix pipe, set its speed.  Here a wave takes a contiguous run of its slice, 4 rows per
-// step, and because 4 | gw those 4 rows never straddle an image row: the position (x0, y) of a step is WAVE-UNIFORM
-// (scalar registers), each lane keeps two pointers advanced by lane-constant increments (a second constant on the
-// steps that wrap to the next image row, where the stride-2 families jump), the loads are unconditional, and padding
-// validity (k2s1 families only) is two compares against lane constants.
+// The rows re-derived per step (RowCursor): any row grid at least 4 texels wide.
+template <int MODE>
+__global__ __launch_bounds__(256) void wgrad_tile_kernel(WT w) {
+  __shared__ __attribute__((aligned(16))) f32x4 part[3 * 17 * 64];   // waves 1..3 -> wave 0 (16 blocks + bias sums)
+  const ConvP& p = w.c;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  int ms, kb, nb;                                                    // one workgroup = one (row slice, kb, nb)
+  if (!wgrad_block(w, ms, kb, nb)) return;
+  const int i = lane & 15, kk = lane >> 4;
+  const ARole<4> ar(kb * 16 + i, w.kq, p);                           // this lane's k-quad = (tap, channel quad of the virtual concat)
+  const BRole<MODE> br(4 * (nb * 16 + i), p.N, p);                   // this lane's n-quad
+
+  f32x4 acc[16], bsum = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+  RowCursor c;
+  c.init(ms * w.rows_per_split, w.rows_per_split, wv, kk, p);
+  auto issue = [&](f32x4& av, f32x4& bv) {
+    const bool rv = c.valid();
+    const int tex = conv_tap_texel<MODE>(p, c.rf, c.ry, c.rx, ar.tap);
+    const size_t tx = (rv && tex >= 0) ? (size_t)tex : 0;
+    av = *reinterpret_cast<const f32x4*>(ar.src + tx * ar.ld);                 // unconditional, clamped address
+    if (!(rv && ar.ok && tex >= 0)) av = (f32x4){0.f, 0.f, 0.f, 0.f};
+    size_t otex = rv ? ((size_t)c.rf * p.gh + c.ry) * p.gw + c.rx : 0;
+    if (MODE == NLT_DECONV_K2S2) otex = rv ? ((size_t)c.rf * p.oh + 2 * c.ry + (br.ab >> 1)) * p.ow + 2 * c.rx + (br.ab & 1) : 0;
+    bv = *reinterpret_cast<const f32x4*>(w.dp + otex * w.ldp + br.off);
+    if (!(rv && br.ok)) bv = (f32x4){0.f, 0.f, 0.f, 0.f};
+    c.advance16(p);
+  };
+  c.rotate3<f32x4, f32x4>(issue, [&](const f32x4& av, const f32x4& bv) { tile_mfma(acc, bsum, av, bv); });
+  tile_finish(w, part, wv, lane, ms, kb, nb, acc, bsum);
+}
+
+// The same block, with the rows WALKED (RowWalk) instead of re-derived: the form used whenever the row grid is a multiple of 4
+// texels wide -- every released shape.  The kernel above spends ~70 VALU instructions per 16-MFMA step on (frame, y, x)
+// bookkeeping, 64-bit multiplies for two addresses and exec-masked loads; with two waves per SIMD that address arithmetic, not
+// the matrix pipe, set its speed.  Here the loads are unconditional and a step's bookkeeping is scalar.
 constexpr int WALK_PF = 6;
 
 template <int MODE>
 __global__ __launch_bounds__(256) void wgrad_walk_kernel(WT w) {
-  __shared__ __attribute__((aligned(16))) f32x4 part[3][17][64];
+  __shared__ __attribute__((aligned(16))) f32x4 part[3 * 17 * 64];
   const ConvP& p = w.c;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int ms, kb, nb;                                                    // one workgroup = one (row slice, kb, nb)
   if (!wgrad_block(w, ms, kb, nb)) return;
   const int i = lane & 15, kk = lane >> 4;
-  const int q0 = p.c0 >> 2, qpt = (p.c0 + p.c1) >> 2;
+  const ARole<4> ar(kb * 16 + i, w.kq, p);
+  const BRole<MODE> br(4 * (nb * 16 + i), p.N, p);
+  using Walk = RowWalk<MODE>;
 
-  const int kq = kb * 16 + i;
-  const bool a_ok = kq < w.kq;
-  const int tap = a_ok ? kq / qpt : 0;
-  const int cq = a_ok ? kq - tap * qpt : 0;
-  const bool from1 = cq >= q0;
-  const float* asrc = from1 ? p.src1 + 4 * (cq - q0) : p.src0 + 4 * cq;
-  const int ald = from1 ? p.ld1 : p.ld0;
-  const int ta = tap >> 1, tb = tap & 1;
-  const int nq = nb * 16 + i;
-  const bool b_ok = nq < w.nq;
-  const int ncol = b_ok ? 4 * nq : 0;
-  const int ab = MODE == NLT_DECONV_K2S2 ? ncol / p.cout : 0;
-  const int oc = MODE == NLT_DECONV_K2S2 ? ncol - ab * p.cout : ncol;
-
-  // the wave's run of rows [m0, m1): a quarter of the slice, a multiple of 4 rows (rows_per_split % 16 == 0, M % 4 == 0)
-  const int chunk = w.rows_per_split >> 2;
-  const int m0 = __builtin_amdgcn_readfirstlane(ms * w.rows_per_split + wv * chunk);
-  int m1 = m0 + chunk;
-  if (m1 > p.M) m1 = p.M;
-  const int nsteps = m1 > m0 ? (m1 - m0) >> 2 : 0;
-  // wave-uniform position of the step's first row: x0 (multiple of 4), y; R = image row index over all frames
-  int x0 = m0 % p.gw;
-  const int R0 = m0 / p.gw;
-  int y = R0 % p.gh;
-
-  // lane pointers at the step-0 row m0 + kk (unclamped tap position; validity is tracked separately)
-  long atex, btex;
-  if (MODE == NLT_CONV_K2S2) atex = ((long)(2 * R0 + ta)) * p.w + 2 * (x0 + kk) + tb;
-  else if (MODE == NLT_CONV_K2S1) atex = (long)m0 + kk + ta * p.w + tb;
-  else if (MODE == NLT_DECONV_K2S1) atex = (long)m0 + kk - ta * p.w - tb;
-  else atex = (long)m0 + kk;
-  if (MODE == NLT_DECONV_K2S2) btex = ((long)(2 * R0 + (ab >> 1))) * p.ow + 2 * (x0 + kk) + (ab & 1);
-  else btex = (long)m0 + kk;
-  const float* pa = nsteps > 0 ? asrc + atex * ald : asrc;          // an empty run (slice past M) must not form an address past the buffer
-  const float* pb = w.dp + btex * w.ldp + oc;
-  // per-step pointer increments (floats): plain step / step that wraps to the next image row
-  const int a_inc = (MODE == NLT_CONV_K2S2 ? 8 : 4) * ald;
-  const int a_inc_wrap = MODE == NLT_CONV_K2S2 ? (8 + p.w) * ald : a_inc;          // p.w = 2 gw
-  const int b_inc = (MODE == NLT_DECONV_K2S2 ? 8 : 4) * w.ldp;
-  const int b_inc_wrap = MODE == NLT_DECONV_K2S2 ? (8 + p.ow) * w.ldp : b_inc;
-  // padding validity of this lane's tap, as bounds on the uniform (x0, y)
-  //   k2s1:           x0 + kk + tb < gw  and  y + ta < gh        ->  x0 < xlim, y < ylim
-  //   transposed k2s1: x0 + kk - tb >= 0 and  y - ta >= 0        ->  x0 >= xlo (only x0 = 0, kk = 0, tb = 1 fails), y >= ta
-  const int xlim = p.gw - kk - tb, ylim = p.gh - ta;
-  const int xlo = tb - kk;
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-#pragma unroll
-    for (int f = 0; f < 4; ++f) acc[e][f] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  f32x4 bsum = (f32x4){0.f, 0.f, 0.f, 0.f};
+  Walk k;
+  k.start(ms, wv, w.rows_per_split, p);                              // (rows_per_split % 16 == 0, M % 4 == 0: runs of whole steps)
+  const float* const zpage = w.zeros;
+  // an empty run (slice past M) must not form an address past the buffer
+  const float* pa = k.nsteps > 0 ? ar.src + k.a_start_texel(ar.ta(), ar.tb(), kk, p) * ar.ld : ar.src;
+  const float* pb = k.nsteps > 0 ? w.dp + k.b_start_texel(br.ab, kk, p) * w.ldp + br.off : zpage;
+  const int a_inc = Walk::a_inc(ar.ld), a_inc_wrap = Walk::a_inc_wrap(ar.ld, p);
+  const int b_inc = Walk::b_inc(w.ldp), b_inc_wrap = Walk::b_inc_wrap(w.ldp, p);
+  const typename Walk::TapBounds tb = Walk::tap_bounds(ar.ta(), ar.tb(), kk, p);
   const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // Steps past the end of the run (the pipeline issues two ahead; a run clipped by M may not fill its last triple) read
-  // dP from a zero page, so their products vanish without a select on the data; X is re-read where the walk stopped.
-  const float* const zpage = w.zeros;
-  int issued = 0;
+  f32x4 acc[16], bsum = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 16; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
   auto issue = [&](f32x4& av, f32x4& bv) {
-    bool ok = a_ok;
-    if (MODE == NLT_CONV_K2S1) ok = ok && x0 < xlim && y < ylim;
-    if (MODE == NLT_DECONV_K2S1) ok = ok && x0 >= xlo && y >= ta;
+    bool ok = ar.ok;
+    if (MODE == NLT_CONV_K2S1) ok = ok && k.x0 < tb.xlim && k.y < tb.ylim;
+    if (MODE == NLT_DECONV_K2S1) ok = ok && k.x0 >= tb.xlo && k.y >= tb.ylo;
     const float* la = pa;
-    if (MODE == NLT_CONV_K2S1 || MODE == NLT_DECONV_K2S1) la = ok ? pa : asrc;       // a padded tap must not be dereferenced
+    if (Walk::PADS) la = ok ? pa : ar.src;                                       // a padded tap must not be dereferenced
     av = *reinterpret_cast<const f32x4*>(la);
     bv = *reinterpret_cast<const f32x4*>(pb);
-    if (MODE == NLT_CONV_K2S1 || MODE == NLT_DECONV_K2S1) av = ok ? av : zero4;
-    ++issued;
-    const bool adv = issued < nsteps;                                  // everything below is wave-uniform
-    const int xn = x0 + 4;
-    const bool wrap = xn >= p.gw;
+    if (Walk::PADS) av = ok ? av : zero4;
+    const bool adv = k.advances(), wrap = k.wraps(p);
     const float* pan = pa + (wrap ? a_inc_wrap : a_inc);
     const float* pbn = pb + (wrap ? b_inc_wrap : b_inc);
     pa = adv ? pan : pa;
     pb = adv ? pbn : zpage;
-    const int yn = y + 1 >= p.gh ? 0 : y + 1;
-    y = (adv && wrap) ? yn : y;
-    x0 = adv ? (wrap ? 0 : xn) : x0;
+    k.move_on(adv, wrap, p);
   };
-  auto compute = [&](const f32x4& av, const f32x4& bv) {
-    bsum += bv;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int f4 = 0; f4 < 4; ++f4)
-        acc[e][f4] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[f4], acc[e][f4], 0, 0, 0);
-  };
-  if (nsteps == 0) pb = zpage;
-  {
-    // operand loads run PF - 1 steps ahead of the MFMAs (PF register sets; the host sizes the runs to multiples of PF steps)
-    constexpr int PF = WALK_PF;
-    f32x4 av[PF], bv[PF];
-#pragma unroll
-    for (int j = 0; j < PF - 1; ++j) issue(av[j], bv[j]);
-    for (int s0 = 0; s0 < nsteps; s0 += PF) {
-#pragma unroll
-      for (int j = 0; j < PF; ++j) {
-        // (the scheduler would otherwise hoist every load of the iteration to its top and drain them together)
-        issue(av[(j + PF - 1) % PF], bv[(j + PF - 1) % PF]);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(av[j], bv[j]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
+  k.template pipeline<WALK_PF, f32x4, f32x4>(issue, [&](const f32x4& av, const f32x4& bv) { tile_mfma(acc, bsum, av, bv); });
   // lanes whose k-quad / n-quad is padding carry garbage operands (their loads are unconditional): the rows / columns
   // they produce are dropped by the reduce pass (kq >= w.kq || nq >= w.nq), but the bias sums need real zeros
-  if (!b_ok) bsum = zero4;
-
-  if (wv > 0) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int f = 0; f < 4; ++f) part[wv - 1][e * 4 + f][lane] = acc[e][f];
-    part[wv - 1][16][lane] = bsum;
-  }
-  __syncthreads();
-  if (wv > 0) return;
-#pragma unroll
-  for (int o = 0; o < 3; ++o) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-#pragma unroll
-      for (int f = 0; f < 4; ++f) acc[e][f] += part[o][e * 4 + f][lane];
-    bsum += part[o][16][lane];
-  }
-  f32x4* dst = reinterpret_cast<f32x4*>(w.ws) + ((((size_t)ms * w.kblocks + kb) * w.nblocks + nb) * 16) * 64 + lane;
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-#pragma unroll
-    for (int f = 0; f < 4; ++f) dst[(e * 4 + f) * 64] = acc[e][f];
-  if (w.wsb && kb == 0) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-      bsum[f] += __shfl_xor(bsum[f], 16);
-      bsum[f] += __shfl_xor(bsum[f], 32);
-    }
-    if (kk == 0) reinterpret_cast<f32x4*>(w.wsb)[((size_t)ms * w.nblocks + nb) * 16 + i] = bsum;
-  }
+  if (!br.ok) bsum = zero4;
+  tile_finish(w, part, wv, lane, ms, kb, nb, acc, bsum);
 }
 
 // Pass 2: 64 dW elements of the block layout per workgroup; the slices are dealt to 16 thread groups (16-byte loads, 8 in
@@ -351,7 +182,7 @@ __device__ __forceinline__ void wgrad_scatter(const WT& w, long idx, float s) {
   const int tap = kq / qpt;
   const int c = 4 * (kq - tap * qpt) + (ef >> 2);
   const int ncol = 4 * nq + (ef & 3);
-  w.dw[keras_widx<MODE>(tap, c, ncol, p.c0 + p.c1, p.cout)] += s;
+  w.dw[nlt_keras_widx<MODE>(tap, c, ncol, p.c0 + p.c1, p.cout, p.cout, 0)] += s;
 }
 
 // FEW = true (<= 8 slices: the mid-network layers, whose 64 x 64 blocks of dW are many and whose slices are few): one
@@ -432,6 +263,8 @@ __device__ void wgrad_bias_block(const WT& w, int ocq) {
   }
 }
 
+inline bool tile_walks(const ConvP& p) { return p.gw % 4 == 0 && !nlt_wgrad_generic_only(); }
+
 bool fill(WT& w, int mode, long* ws_floats) {
   const ConvP& p = w.c;
   const int taps = (mode == NLT_CONV1X1 || mode == NLT_DECONV_K2S2) ? 1 : 4;
@@ -445,7 +278,7 @@ bool fill(WT& w, int mode, long* ws_floats) {
   if (want < 1) want = 1;
   long rows = (p.M + want - 1) / want;
   if (rows < 256) rows = 256;                                 // >= 16 MFMA steps per wave
-  const bool walk = p.gw % 4 == 0 && !nlt_wgrad_generic_only();
+  const bool walk = tile_walks(p);
   const long unit = walk ? 16 * WALK_PF : 16;                 // the walk kernel's runs: whole pipeline rounds
   rows = (rows + unit - 1) / unit * unit;
   w.msplits = (int)((p.M + rows - 1) / rows);
@@ -463,7 +296,7 @@ bool fill(WT& w, int mode, long* ws_floats) {
 template <int MODE>
 int run(WT& w, hipStream_t s) {
   const long groups = (long)w.kblocks * w.nblocks * (w.xcd_order ? (w.msplits + 7) / 8 * 8 : w.msplits);   // (whole XCD rounds)
-  w.zeros = (w.c.gw % 4 == 0 && !nlt_wgrad_generic_only()) ? nlt_zero_page() : nullptr;
+  w.zeros = tile_walks(w.c) ? nlt_zero_page() : nullptr;
   if (w.zeros)
     hipLaunchKernelGGL(wgrad_walk_kernel<MODE>, dim3((unsigned)groups), dim3(256), 0, s, w);
   else

@@ -1,5 +1,5 @@
-"""CPU: NumPy emulation of the ADDRESS WALK that is new in csrc/wgrad_tile.hip (wgrad_walk_kernel) and in the WALK form of
-csrc/wgrad_narrow.hip: a wave's run of rows, 4 per step, with wave-uniform (x0, y), lane pointers advanced by two constants
+"""CPU: NumPy emulation of the ADDRESS WALK of csrc/wgrad_tile.hip (wgrad_walk_kernel) and of the WALK form of
+csrc/wgrad_narrow.hip (both on RowWalk, csrc/wgrad_common.h): a wave's run of rows, 4 per step, with wave-uniform (x0, y), lane pointers advanced by two constants
 (plain step / step that wraps to the next image row) and padding validity from lane-constant bounds.  Every step must read exactly
 the texels nlt_common.h's conv_tap_texel() derives from the row index -- for all five conv families, several frames, narrow grids,
 runs that start in the middle of an image row and runs clipped by M -- and must never form an address outside the tensors."""
