@@ -1,5 +1,6 @@
-// Tile geometry, packed-blob offsets and small helpers shared by the fused front kernels (fused.hip: first generation,
-// also the training variant; front3.hip: LDS-staged raw tiles, float and uint8-store inputs).
+// Shared by the fused front kernels.  The workgroup tile geometry (TH ... PATH), lrelu4 and xcd_tile: fused.hip only (the first
+// generation, its training variant and front2).  The packed-blob offsets: written by fused.hip's pack kernels, read by its front
+// kernels and, through front_strip.h, by the wave-per-strip kernels (front4.hip, front_ovr.hip), which have their own geometry there.
 #pragma once
 #include "nlt_common.h"
 

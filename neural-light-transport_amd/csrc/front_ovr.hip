@@ -12,59 +12,29 @@
 //   stage 2  q1 = lrelu(W_L1s1 * y1 + b)                     -> fm1[..., 0:16]  (the [16:32) half is the given ovr1)
 //   stage 3  qtmp2 = lrelu(W_L2s2[q rows] * q1 + P2[texel])  P2 [h/4,w/4,32] = W_L2s2[o rows] * ovr1 + bias
 //   skip3 = Wskip * raw5 + S0[texel] (+ base)                S0 [h,w,4]     = W_head[o rows] * ovr0 + folded bias
-// with the maps as the INITIAL VALUES of the MFMA accumulator chains (no add).  Same organisation as front4: persistent
-// 8-wave workgroups, a wave owns a 4 x 16 strip of level-1 texels, raw rows staged through wave-private LDS by 16-byte
-// row-contiguous loads, the next strip's raw rows and map values in flight in registers under the current strip's MFMAs,
-// no workgroup barrier after the prologue.
-#include <type_traits>
-#include "front_common.h"
+// with the maps as the INITIAL VALUES of the MFMA accumulator chains (no add).  The organisation is front4's, and its pieces are
+// the same text (front_strip.h): persistent 8-wave workgroups, a wave owns a 4 x 16 strip of level-1 texels, raw rows staged
+// through wave-private LDS by 16-byte row-contiguous loads, no workgroup barrier after the prologue.  This file keeps what
+// front4 does not do: the split into interior and border strips, the map loads, the lane-constant geometry of interior
+// strips and the software pipeline across them (the next strip's raw rows and map values in flight in registers under the
+// current strip's MFMAs).
+#include "front_strip.h"
 
 namespace {
 
-constexpr int SH = 4, SW = 16;
-constexpr int AH = SH + 1, AW = SW + 1;
-constexpr int AT = AH * AW;
-constexpr int NC = (AT + 15) / 16;         // 6 column tiles
-constexpr int SLOTS = NC * 16;
-constexpr int XH = 2 * AH;                 // raw rows: 10
-constexpr int R3 = 104, R1 = 40;           // floats per staged 3- / 1-channel raw row (34 texels)
-constexpr int W_RQ = 0;
-constexpr int W_RC = W_RQ + XH * R3;
-constexpr int W_RL = W_RC + XH * R1;
-constexpr int W_OT = W_RL + XH * R1;       // stage-1 tile [4 channel quads][96 slots][4]; then the level-1 tile of stage 3
-constexpr int W_END = W_OT + 4 * SLOTS * 4;            // 3376 floats per wave
-constexpr int W_AQ3 = 0;                   // workgroup-shared: level 2's query-row fragments [rt 2][c4 4][lane 64][4]
-constexpr int W_AQ1 = W_AQ3 + 2 * 4 * 64 * 4;          // stride-1 fragments [tap 4][lane 64][4]
-constexpr int W_BQ1 = W_AQ1 + 4 * 64 * 4;              // stride-1 bias [16]
-constexpr int W_WAVES = W_BQ1 + 16;
-
-template <int NW> constexpr int lds_floats() { return W_WAVES + NW * W_END; }
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x4 lrelu4m(f32x4 v, f32x2 alpha2) {   // front4.hip: max(v, alpha v) for 0 <= alpha <= 1
-  const f32x2 plo = (f32x2){v[0], v[1]} * alpha2, phi = (f32x2){v[2], v[3]} * alpha2;
-  const float top = 3.4028234663852886e38f;
-  return (f32x4){__builtin_amdgcn_fmed3f(v[0], plo[0], top), __builtin_amdgcn_fmed3f(v[1], plo[1], top),
-                 __builtin_amdgcn_fmed3f(v[2], phi[0], top), __builtin_amdgcn_fmed3f(v[3], phi[1], top)};
-}
+using L = StripLds<false>;
 
 struct OvrMaps { const float *p1, *s0, *p2; };
 
 // U8 = true reads the resident uint8 capture store (nlt/datasets/nlt.py:131-136,173-181: diffuse / cvis / lvis stores, frame id per
-// sample) and stages the raw BYTE values, like front4_kernel<true>: the 1 / 255 lives in the stage-1 A operands, in the head's skip
-// rows (OFF_WSK8) and in `+ base`; <= 3e-7 rel-L2 from the float variant on the assembled batch (fl(W / 255) . u vs W . fl(u / 255)).
+// sample) and stages the raw BYTE values, like front4_kernel<true> (see u8x4_unit).
 template <int NW, bool U8>
 __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
     const void* __restrict__ base, const void* __restrict__ cvis, const void* __restrict__ lvis, const int* __restrict__ ids, int h, int w,
     int tiles_y, int tiles_x, int ntiles, const float* __restrict__ blob, const float* __restrict__ blob3, OvrMaps maps,
     int add_base, float alpha, float* __restrict__ q1, int ldq, float* __restrict__ skip3, float* __restrict__ qtmp2) {
-  __shared__ __attribute__((aligned(16))) float lds_all[lds_floats<NW>()];
+  static_assert(NW == NWAVES, "the strip walk and the LDS plan are laid out for the eight waves of a CU");
+  __shared__ __attribute__((aligned(16))) float lds_all[L::FLOATS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int kk = lane >> 4, j = lane & 15;
   const int h2 = h >> 1, w2 = w >> 1;
@@ -75,86 +45,50 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
   // ---- level 2's query-row fragments (slab 0 of OFF3_AQ), the stride-1 fragments and bias: once per workgroup
   for (int u = tid; u < 2 * 4 * 64; u += 64 * NW) {
     const int rt = u >> 8, r = u & 255;                                  // r = c4 * 64 + lane
-    *reinterpret_cast<f32x4*>(lds_all + W_AQ3 + u * 4) = *reinterpret_cast<const f32x4*>(blob3 + OFF3_AQ + ((rt * 8) * 64 + r) * 4);
+    *reinterpret_cast<f32x4*>(lds_all + L::W_AQ3 + u * 4) = *reinterpret_cast<const f32x4*>(blob3 + OFF3_AQ + ((rt * 8) * 64 + r) * 4);
   }
   for (int u = tid; u < 256; u += 64 * NW)
-    *reinterpret_cast<f32x4*>(lds_all + W_AQ1 + u * 4) = *reinterpret_cast<const f32x4*>(blob + OFF_AQ1 + u * 4);
-  if (tid < 16) lds_all[W_BQ1 + tid] = blob[OFF_BQ1 + tid];
+    *reinterpret_cast<f32x4*>(lds_all + L::W_AQ1 + u * 4) = *reinterpret_cast<const f32x4*>(blob + OFF_AQ1 + u * 4);
+  if (tid < 16) lds_all[L::W_BIAS + tid] = blob[OFF_BQ1 + tid];
   __syncthreads();
 
-  // ---- this wave's strips (front4.hip: one contiguous run of tiles per XCD, its waves round-robin)
+  // ---- this wave's strips
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int per_xcd = (ntiles + 7) >> 3;
-  const int t_lo = (blockIdx.x & 7) * per_xcd;
-  const int t_hi = min(t_lo + per_xcd, ntiles);
-  const int stride = (gridDim.x >> 3) * NW;
-  int tile = t_lo + wv * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-  if (tile >= t_hi) return;
-  float* const lds = lds_all + W_WAVES + wv * W_END;
+  const StripWalk walk(ntiles, tiles_y, tiles_x, wv);
+  if (walk.done()) return;
+  float* const lds = lds_all + L::W_WAVES + wv * L::W_END;
 
-  // ---- staging of the raw rows (float inputs): item = pass * 64 + lane -> (raw row, 16-byte piece of the row).
-  // This kernel has registers to spare (front4 has none): everything that depends on the lane only is computed ONCE --
-  // byte offsets of the lane's pieces inside a strip, LDS offsets, map offsets -- and a strip whose haloed tile lies inside
-  // the image (all but the last row / column of strips) adds wave-uniform bases to them; border strips re-derive with clamps.
-  constexpr int N3 = U8 ? 13 : 26, P3 = U8 ? 3 : 5, E3 = U8 ? 8 : 4;    // pieces per 3-channel row, passes, texel-floats per piece
-  constexpr int N1 = U8 ? 5 : 9, P1 = U8 ? 1 : 2, E1 = U8 ? 8 : 4;
-  constexpr unsigned BPE = U8 ? 1u : 4u;                                  // bytes per stored element
+  // ---- staging of the raw rows.  This kernel has registers to spare (front4 has none): everything that depends on the lane
+  // only is computed ONCE -- byte offsets of the lane's pieces inside a strip, LDS offsets, map offsets -- and a strip whose
+  // haloed tile lies inside the image (all but the last row / column of strips) adds wave-uniform bases to them; border strips
+  // re-derive with clamps (Pieces::stage_geom).
+  using P = Pieces<U8>;
+  using Piece = typename P::Piece;
+  constexpr int P3 = P::P3, P1 = P::P1;
   unsigned g3[P3], g1[P1];                                               // byte offsets inside a frame, strip being loaded
   unsigned c3[P3], c1[P1];                                               // their lane-constant parts (interior strips)
   int l1o[P1];                                                           // LDS offset of the lane's 1-channel pieces
 #pragma unroll
   for (int p = 0; p < P3; ++p) {
     const int item = p * 64 + lane;
-    const int r = item / N3, i = item - r * N3;
-    c3[p] = item < XH * N3 ? (unsigned)((r * w) * 3 + E3 * i) * BPE : 0u;
+    const int r = item / P::N3, i = item - r * P::N3;
+    c3[p] = item < XH * P::N3 ? (unsigned)((r * w) * 3 + P::E3 * i) * P::BPE : 0u;
   }
 #pragma unroll
   for (int p = 0; p < P1; ++p) {
     const int item = p * 64 + lane;
-    const int r = item / N1, i = item - r * N1;
-    c1[p] = item < XH * N1 ? (unsigned)(r * w + E1 * i) * BPE : 0u;
-    l1o[p] = r * R1 + E1 * i;
+    const int r = item / P::N1, i = item - r * P::N1;
+    c1[p] = item < XH * P::N1 ? (unsigned)(r * w + P::E1 * i) * P::BPE : 0u;
+    l1o[p] = P::off1(p, lane);
   }
-  int lf = 0;
-  auto opaque = [](int v) { asm volatile("" : "+v"(v)); return v; };
-  auto load_geom = [&](int t) {
-    const int tx0 = (t % tiles_x) * SW; t /= tiles_x;
-    const int ty0 = (t % tiles_y) * SH;
-    lf = t / tiles_y;
-    if (ty0 + AH <= h2 && tx0 + AW <= w2) {                              // interior (wave-uniform)
-      const unsigned b3 = (unsigned)((2 * ty0 * w + 2 * tx0) * 3) * BPE, b1 = (unsigned)(2 * ty0 * w + 2 * tx0) * BPE;
-#pragma unroll
-      for (int p = 0; p < P3; ++p) g3[p] = (p + 1) * 64 > XH * N3 && p * 64 + lane >= XH * N3 ? 0u : b3 + c3[p];
-#pragma unroll
-      for (int p = 0; p < P1; ++p) g1[p] = (p + 1) * 64 > XH * N1 && p * 64 + lane >= XH * N1 ? 0u : b1 + c1[p];
-      return;
-    }
-    const int ln = opaque(lane);
-#pragma unroll
-    for (int p = 0; p < P3; ++p) {
-      const int item = p * 64 + ln;
-      const int r = item / N3, i = item - r * N3;
-      const int gy = 2 * ty0 + r;
-      const bool ok = item < XH * N3 && gy < h && 3 * (2 * tx0) + E3 * i < 3 * w;
-      g3[p] = ok ? (unsigned)((gy * w + 2 * tx0) * 3 + E3 * i) * BPE : 0u;
-    }
-#pragma unroll
-    for (int p = 0; p < P1; ++p) {
-      const int item = p * 64 + ln;
-      const int r = item / N1, i = item - r * N1;
-      const int gy = 2 * ty0 + r;
-      const bool ok = item < XH * N1 && gy < h && 2 * tx0 + E1 * i < w;
-      g1[p] = ok ? (unsigned)(gy * w + 2 * tx0 + E1 * i) * BPE : 0u;
-    }
-  };
-  using Piece = typename std::conditional<U8, uint2, f32x4>::type;
+  int lf = 0;                                                            // sample (frame of the batch) of the strip being loaded
   Piece st[P3 + 2 * P1];     // the staged item: 16-byte (float) / 8-byte (uint8) pieces
   auto load_query = [&]() {
     long fr = lf;
     if constexpr (U8) fr = ids[lf];
-    const unsigned char* pb = static_cast<const unsigned char*>(base) + fr * hw * (3 * BPE);
-    const unsigned char* pc = static_cast<const unsigned char*>(cvis) + fr * hw * BPE;
-    const unsigned char* pl = static_cast<const unsigned char*>(lvis) + fr * hw * BPE;
+    const unsigned char* pb = static_cast<const unsigned char*>(base) + fr * hw * (3 * P::BPE);
+    const unsigned char* pc = static_cast<const unsigned char*>(cvis) + fr * hw * P::BPE;
+    const unsigned char* pl = static_cast<const unsigned char*>(lvis) + fr * hw * P::BPE;
 #pragma unroll
     for (int p = 0; p < P3; ++p) st[p] = *reinterpret_cast<const Piece*>(pb + g3[p]);
 #pragma unroll
@@ -163,73 +97,39 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
       st[P3 + P1 + p] = *reinterpret_cast<const Piece*>(pl + g1[p]);
     }
   };
-  auto put = [&](float* dst, int at) {                                   // one staged piece -> E floats in LDS (bytes stay byte VALUES)
-    if constexpr (U8) {
-      const unsigned lo = st[at].x, hi = st[at].y;
-      *reinterpret_cast<f32x4*>(dst) = (f32x4){(float)(lo & 255u), (float)((lo >> 8) & 255u), (float)((lo >> 16) & 255u), (float)(lo >> 24)};
-      *reinterpret_cast<f32x4*>(dst + 4) = (f32x4){(float)(hi & 255u), (float)((hi >> 8) & 255u), (float)((hi >> 16) & 255u), (float)(hi >> 24)};
-    } else {
-      *reinterpret_cast<f32x4*>(dst) = st[at];
-    }
-  };
-  auto store_query = [&]() {
-#pragma unroll
-    for (int p = 0; p < P3; ++p) {
-      const int item = p * 64 + lane;
-      if ((p + 1) * 64 > XH * N3 && item >= XH * N3) continue;
-      put(lds + W_RQ + item * E3, p);
-    }
-#pragma unroll
-    for (int p = 0; p < P1; ++p) {
-      if ((p + 1) * 64 > XH * N1 && p * 64 + lane >= XH * N1) continue;
-      put(lds + W_RC + l1o[p], P3 + p);
-      put(lds + W_RL + l1o[p], P3 + P1 + p);
-    }
-  };
+  auto store_query = [&]() { P::store_query(lds + L::W_RQ, lds + L::W_RC, lds + L::W_RL, st, lane, l1o); };
 
   // ---- weights held in registers: the folded stage-1 rows of the five query channels (the three observation rows of
   // the blob are zero: it was packed with a zero observation L0)
-  constexpr float INV255 = 1.0f / 255.0f;
   float aq2[5];
 #pragma unroll
   for (int m = 0; m < 5; ++m) aq2[m] = blob[OFF_AQ2 + m * 64 + lane] * (U8 ? INV255 : 1.0f);
 
-  // ---- this lane's six stage-1 positions: haloed level-1 texel t = c * 16 + j, tap kk
   int rd3[NC], rd1[NC];                                                  // LDS offsets of the lane's raw texel (3- / 1-channel tiles)
   unsigned mo1[NC], tex0[NC];                                            // interior strips: P1 offset (floats), raw texel index, minus the strip's base
-  unsigned live_m = 0, own_m = 0;
+  unsigned live_m, own_m;
+  lane_slots(j, kk, rd3, live_m, own_m);
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    const int t = c * 16 + j;
-    const bool live = t < AT;
-    const int hy = live ? t / AW : 0, hx = live ? t % AW : 0;
-    rd3[c] = (2 * hy + (kk >> 1)) * R3 + (2 * hx + (kk & 1)) * 3;
-    rd1[c] = (2 * hy + (kk >> 1)) * R1 + 2 * hx + (kk & 1);
-    mo1[c] = (unsigned)((hy * w2 + hx) * 16 + 4 * kk);
-    const bool own = live && hy < SH && hx < SW;
-    tex0[c] = own ? (unsigned)((2 * hy + (kk >> 1)) * w + 2 * hx + (kk & 1)) : 0u;
-    live_m |= (unsigned)live << c;
-    own_m |= (unsigned)own << c;
+    const bool live = (live_m >> c) & 1;
+    const Slot s(c * 16 + j, live);
+    rd1[c] = s.raw1(kk);
+    mo1[c] = live ? (unsigned)((s.hy * w2 + s.hx) * 16 + 4 * kk) : 0u;   // (dead slots read the strip's first texel: no select per strip)
+    tex0[c] = (own_m >> c) & 1 ? (unsigned)((2 * s.hy + (kk >> 1)) * w + 2 * s.hx + (kk & 1)) : 0u;
   }
-  float* const ot = lds + W_OT;
-  const int Y = j >> 3, X = j & 7;
+  float* const ot = lds + L::W_OT;
+  const L1Tile l1(kk, j);
   const int h4 = h2 >> 1, w4 = w2 >> 1;
-  const int l1_rd = ((kk & 1) * 32 + ((((2 * Y + (kk >> 1)) * 8) + X) ^ ((kk & 1) * 8))) * 4;
-  auto l1_wr = [&](int row) { return (kk * 64 + (j & 1) * 32 + (((row * 8) + (j >> 1)) ^ ((j & 1) * 8))) * 4; };
 
   // ---- the override maps of a strip: P1 at the lane's six haloed level-1 texels, S0 at its six raw texels, P2 at its
   // level-2 texel.  Texels beyond the image read the map's first texel: their results are masked / never stored.
   f32x4 mp1[NC], ms0[NC], mp2[2];
-  const unsigned mo2 = (unsigned)((Y * w4 + X) * 32 + 4 * kk);
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-    if (!((live_m >> c) & 1)) mo1[c] = 0u;                               // (dead slots read the strip's first texel: no select per strip)
+  const unsigned mo2 = (unsigned)((l1.Y * w4 + l1.X) * 32 + 4 * kk);
   auto maps_fast = [&](int t) {                                          // interior strips: wave-uniform bases + lane constants
-    const int tx0 = (t % tiles_x) * SW; t /= tiles_x;
-    const int ty0 = (t % tiles_y) * SH;
-    const float* b1 = maps.p1 + (size_t)(ty0 * w2 + tx0) * 16;
-    const float* b0 = maps.s0 + (size_t)(2 * ty0 * w + 2 * tx0) * 4;
-    const float* b2 = maps.p2 + (size_t)((ty0 >> 1) * w4 + (tx0 >> 1)) * 32;
+    const Strip s = walk.decode(t);
+    const float* b1 = maps.p1 + (size_t)(s.ty0 * w2 + s.tx0) * 16;
+    const float* b0 = maps.s0 + (size_t)(2 * s.ty0 * w + 2 * s.tx0) * 4;
+    const float* b2 = maps.p2 + (size_t)((s.ty0 >> 1) * w4 + (s.tx0 >> 1)) * 32;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       mp1[c] = *reinterpret_cast<const f32x4*>(b1 + mo1[c]);
@@ -238,24 +138,21 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
     mp2[0] = *reinterpret_cast<const f32x4*>(b2 + mo2);
     mp2[1] = *reinterpret_cast<const f32x4*>(b2 + mo2 + 16);
   };
-  auto maps_slow = [&](int t) {
-    const int tx0 = (t % tiles_x) * SW; t /= tiles_x;
-    const int ty0 = (t % tiles_y) * SH;
+  auto maps_slow = [&](Strip s) {
     const int jo = opaque(j);
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-      const int tt = c * 16 + jo;
       const bool live = (live_m >> c) & 1;
-      const int hy = live ? tt / AW : 0, hx = live ? tt % AW : 0;
-      const int y1 = ty0 + hy, x1 = tx0 + hx;
+      const Slot q(c * 16 + jo, live);
+      const int y1 = s.ty0 + q.hy, x1 = s.tx0 + q.hx;
       const bool in1 = live && y1 < h2 && x1 < w2;
       const unsigned o1 = in1 ? (unsigned)((y1 * w2 + x1) * 16 + 4 * kk) : 0u;
       mp1[c] = *reinterpret_cast<const f32x4*>(maps.p1 + o1);
-      const bool own = in1 && hy < SH && hx < SW;
+      const bool own = in1 && q.hy < SH && q.hx < SW;
       const unsigned o0 = own ? (unsigned)(((2 * y1 + (kk >> 1)) * w + 2 * x1 + (kk & 1)) * 4) : 0u;
       ms0[c] = *reinterpret_cast<const f32x4*>(maps.s0 + o0);
     }
-    const int gy2 = (ty0 >> 1) + Y, gx2 = (tx0 >> 1) + X;
+    const int gy2 = (s.ty0 >> 1) + l1.Y, gx2 = (s.tx0 >> 1) + l1.X;
     const unsigned o2 = (gy2 < h4 && gx2 < w4) ? (unsigned)((gy2 * w4 + gx2) * 32 + 4 * kk) : 0u;
     mp2[0] = *reinterpret_cast<const f32x4*>(maps.p2 + o2);
     mp2[1] = *reinterpret_cast<const f32x4*>(maps.p2 + o2 + 16);
@@ -267,26 +164,12 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
 
   // ---- one strip: stage 1 -> [`between`: the staging of later strips] -> stage 2 -> stage 3.  FAST = the strip's haloed tile
   // lies inside the image: no masks, and NO CONDITION AROUND A GLOBAL STORE OR LOAD (see the loop below for why that matters).
-  auto strip = [&](auto fast_tag, int t, auto&& between) {
+  auto strip = [&](auto fast_tag, Strip s, auto&& between) {
     constexpr bool FAST = decltype(fast_tag)::value;
-    const int tx0 = (t % tiles_x) * SW; t /= tiles_x;
-    const int ty0 = (t % tiles_y) * SH;
-    const int f = t / tiles_y;
+    const int tx0 = s.tx0, ty0 = s.ty0, f = s.f;
     unsigned inside_m = live_m, owned_m = own_m;
-    if constexpr (!FAST) {
-      inside_m = owned_m = 0;
-      const int jo = opaque(j);
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        const int tt = c * 16 + jo;
-        const bool live = (live_m >> c) & 1;
-        const int hy = live ? tt / AW : 0, hx = live ? tt % AW : 0;
-        const bool inside = live && ty0 + hy < h2 && tx0 + hx < w2;
-        inside_m |= (unsigned)inside << c;
-        owned_m |= (unsigned)(inside && hy < SH && hx < SW) << c;
-      }
-    }
-    const int gy2 = (ty0 >> 1) + Y, gx2 = (tx0 >> 1) + X;
+    if constexpr (!FAST) border_masks(live_m, opaque(j), s, h2, w2, inside_m, owned_m);
+    const int gy2 = (ty0 >> 1) + l1.Y, gx2 = (tx0 >> 1) + l1.X;
     const bool in2 = FAST || (gy2 < h4 && gx2 < w4);
     const long tex2 = (long)gy2 * w4 + gx2;
     const f32x4 p2a = mp2[0], p2b = mp2[1];                              // (mp2 is refilled for a later strip in `between`)
@@ -299,14 +182,11 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
       float raw[3][5];
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float* sp = lds + W_RQ + rd3[c0 + c];
+        const float* sp = lds + L::W_RQ + rd3[c0 + c];
         raw[c][0] = sp[0]; raw[c][1] = sp[1]; raw[c][2] = sp[2];
-        raw[c][3] = lds[W_RC + rd1[c0 + c]]; raw[c][4] = lds[W_RL + rd1[c0 + c]];
+        raw[c][3] = lds[L::W_RC + rd1[c0 + c]]; raw[c][4] = lds[L::W_RL + rd1[c0 + c]];
       }
-#pragma unroll
-      for (int m = 0; m < 5; ++m)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(aq2[m], raw[c][m], acc[c], 0, 0, 0);
+      stage1_chain(aq2, raw, acc);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         f32x4 v = lrelu4m(acc[c], alpha2);
@@ -316,16 +196,7 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
         *reinterpret_cast<f32x4*>(ot + (kk * SLOTS + (c0 + c) * 16 + j) * 4) = v;
         // every lane forms its three sums (a lane that owns no texel wastes nothing: SIMD); only the 12-byte store is predicated
         float s0 = ms0[c0 + c][0], s1 = ms0[c0 + c][1], s2 = ms0[c0 + c][2];
-#pragma unroll
-        for (int rr = 0; rr < 5; ++rr) {
-          s0 = fmaf(raw[c][rr], wsk[rr * 3], s0);
-          s1 = fmaf(raw[c][rr], wsk[rr * 3 + 1], s1);
-          s2 = fmaf(raw[c][rr], wsk[rr * 3 + 2], s2);
-        }
-        if (add_base) {
-          if constexpr (U8) { s0 = fmaf(raw[c][0], INV255, s0); s1 = fmaf(raw[c][1], INV255, s1); s2 = fmaf(raw[c][2], INV255, s2); }
-          else { s0 += raw[c][0]; s1 += raw[c][1]; s2 += raw[c][2]; }
-        }
+        skip_sums<5, U8>(raw[c], wsk, add_base, s0, s1, s2);
         if ((owned_m >> (c0 + c)) & 1) {
           unsigned at;
           if constexpr (FAST) at = tex0[c0 + c];
@@ -340,26 +211,9 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
     }
     wave_sync();                                                         // every lane has its raw values: the raw tile is free
     between();
-    // stage 2: L1 stride-1 conv
     f32x4 qv[SH];
-    {
-      const float* tilep = ot + kk * SLOTS * 4;
-      const f32x4 bias = *reinterpret_cast<const f32x4*>(lds_all + W_BQ1 + 4 * kk);
-      f32x4 acc[SH] = {bias, bias, bias, bias};
-#pragma unroll
-      for (int tp = 0; tp < 4; ++tp) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(lds_all + W_AQ1 + (tp * 64 + lane) * 4);
-        f32x4 bb[SH];
-#pragma unroll
-        for (int r = 0; r < SH; ++r) bb[r] = *reinterpret_cast<const f32x4*>(tilep + ((r + (tp >> 1)) * AW + j + (tp & 1)) * 4);
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4)
-#pragma unroll
-          for (int r = 0; r < SH; ++r) acc[r] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4], bb[r][s4], acc[r], 0, 0, 0);
-      }
-#pragma unroll
-      for (int r = 0; r < SH; ++r) qv[r] = lrelu4m(acc[r], alpha2);
-    }
+    stage2(ot, kk, j, [&](int tp) { return *reinterpret_cast<const f32x4*>(lds_all + L::W_AQ1 + (tp * 64 + lane) * 4); },
+           *reinterpret_cast<const f32x4*>(lds_all + L::W_BIAS + 4 * kk), alpha2, qv);
     {
       const long hw2 = (long)h2 * w2;
       const int gx = tx0 + j;
@@ -371,26 +225,14 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
     wave_sync();                                                         // stage-2 reads of `ot` are done: it becomes the level-1 tile
     // stage 3: level 2's stride-2 conv, query rows only
 #pragma unroll
-    for (int r = 0; r < SH; ++r) *reinterpret_cast<f32x4*>(ot + l1_wr(r)) = qv[r];
+    for (int r = 0; r < SH; ++r) *reinterpret_cast<f32x4*>(ot + l1.wr(r)) = qv[r];
     wave_sync();
     {
       f32x4 a3[2] = {p2a, p2b};
-#pragma unroll
-      for (int c4 = 0; c4 < 4; ++c4) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(ot + c4 * 256 + l1_rd);
-        const f32x4 w0 = *reinterpret_cast<const f32x4*>(lds_all + W_AQ3 + ((0 * 4 + c4) * 64 + lane) * 4);
-        const f32x4 w1 = *reinterpret_cast<const f32x4*>(lds_all + W_AQ3 + ((1 * 4 + c4) * 64 + lane) * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          a3[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[e], v[e], a3[0], 0, 0, 0);
-          a3[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[e], v[e], a3[1], 0, 0, 0);
-        }
-      }
-      if (in2) {
-        float* o = qtmp2 + ((long)f * h4 * w4 + tex2) * 32 + 4 * kk;
-        *reinterpret_cast<f32x4*>(o) = lrelu4m(a3[0], alpha2);
-        *reinterpret_cast<f32x4*>(o + 16) = lrelu4m(a3[1], alpha2);
-      }
+      level2_chain(ot, l1.rd, [&](int rt, int c4) {
+        return *reinterpret_cast<const f32x4*>(lds_all + L::W_AQ3 + ((rt * 4 + c4) * 64 + lane) * 4);
+      }, a3);
+      if (in2) level2_store(qtmp2 + ((long)f * h4 * w4 + tex2) * 32 + 4 * kk, a3, alpha2);
     }
     wave_sync();                                                         // the level-1 tile is consumed: `ot` is free again
   };
@@ -407,61 +249,60 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
   // count is 0 for every iteration.  Hence: every memory operation of this loop body is unconditional (prefetches past the last
   // strip are clamped to a valid strip and simply unused; border strips run in the second loop), and the first iteration is
   // PEELED so that both predecessors of the loop header have issued the same sequence.
-  auto is_interior = [&](int t) {
-    const int tx0 = (t % tiles_x) * SW; t /= tiles_x;
-    const int ty0 = (t % tiles_y) * SH;
-    return ty0 + AH <= h2 && tx0 + AW <= w2;
-  };
+  // (the haloed tile lies inside the image.  Spelled here, not as a function of front_strip.h that front4 could share: through one,
+  // forced inline or not, this loop comes out with other wait counts and twice the SGPR spills -- profiles/README.md r11_a)
+  auto is_interior = [&](int t) { const Strip s = walk.decode(t); return s.ty0 + AH <= h2 && s.tx0 + AW <= w2; };
   auto next_interior = [&](int t) {
-    do { t += stride; } while (t < t_hi && !is_interior(t));
+    do { t += walk.stride; } while (t < walk.t_hi && !is_interior(t));
     return t;
   };
   auto geom_fast = [&](int t) {
-    const int tx0 = (t % tiles_x) * SW; t /= tiles_x;
-    const int ty0 = (t % tiles_y) * SH;
-    lf = t / tiles_y;
-    const unsigned b3 = (unsigned)((2 * ty0 * w + 2 * tx0) * 3) * BPE, b1 = (unsigned)(2 * ty0 * w + 2 * tx0) * BPE;
+    const Strip s = walk.decode(t);
+    lf = s.f;
+    const unsigned b3 = (unsigned)((2 * s.ty0 * w + 2 * s.tx0) * 3) * P::BPE, b1 = (unsigned)(2 * s.ty0 * w + 2 * s.tx0) * P::BPE;
 #pragma unroll
     for (int p = 0; p < P3; ++p) g3[p] = b3 + c3[p];                     // (lanes without a piece: c3 = 0, the strip's first bytes)
 #pragma unroll
     for (int p = 0; p < P1; ++p) g1[p] = b1 + c1[p];
   };
-  int cur = is_interior(tile) ? tile : next_interior(tile);
-  if (cur < t_hi) {
+  int cur = is_interior(walk.tile) ? walk.tile : next_interior(walk.tile);
+  if (cur < walk.t_hi) {
     geom_fast(cur);
     load_query();
     maps_fast(cur);
     store_query();
     int nx = next_interior(cur);
-    geom_fast(nx < t_hi ? nx : cur);
+    geom_fast(nx < walk.t_hi ? nx : cur);
     load_query();
     wave_sync();
     auto iteration = [&](int c_, int n_) {
-      strip(std::true_type{}, c_, [&]() {
+      strip(std::true_type{}, walk.decode(c_), [&]() {
         store_query();                                                   // raw rows of the next strip: registers -> LDS
-        const int pf = n_ < t_hi ? n_ : c_;
+        const int pf = n_ < walk.t_hi ? n_ : c_;
         maps_fast(pf);                                                   // its maps
         const int n2 = next_interior(pf);
-        geom_fast(n2 < t_hi ? n2 : pf);                                  // the raw rows of the strip after it
+        geom_fast(n2 < walk.t_hi ? n2 : pf);                             // the raw rows of the strip after it
         load_query();
       });
     };
     iteration(cur, nx);                                                  // peeled (see above)
-    while (nx < t_hi) {
+    while (nx < walk.t_hi) {
       cur = nx;
       nx = next_interior(cur);
       iteration(cur, nx);
     }
   }
   // ---- border strips (halo beyond the image): one at a time, masks and clamps, no pipelining across strips
-  for (int t = tile; t < t_hi; t += stride) {
+  for (int t = walk.tile; t < walk.t_hi; t += walk.stride) {
     if (is_interior(t)) continue;
-    load_geom(t);
+    const Strip s = walk.decode(t);
+    lf = s.f;
+    P::stage_geom(s, opaque(lane), h, w, g3, g1);
     load_query();
-    maps_slow(t);
+    maps_slow(s);
     store_query();
     wave_sync();
-    strip(std::false_type{}, t, []() {});
+    strip(std::false_type{}, s, []() {});
   }
 }
 
@@ -470,32 +311,20 @@ __global__ __launch_bounds__(64 * NW, 1) void front_ovr_kernel(
 static int front_ovr_launch(bool u8, const void* base, const void* cvis, const void* lvis, const int* ids, int n, int h, int w,
                             const float* packed, const float* packed_l2, const float* p1, const float* s0, const float* p2,
                             int add_base, float alpha, float* q1, int ldq, float* skip3, float* qtmp2, void* stream) {
-  if (!base || !cvis || !lvis || !packed || !packed_l2 || !p1 || !s0 || !p2 || !q1 || !skip3 || !qtmp2) return NLT_ERR_BAD_ARG;
-  if (u8 && !ids) return NLT_ERR_BAD_ARG;
-  if (n <= 0 || h <= 0 || w <= 0 || ldq < 16 || (ldq & 3)) return NLT_ERR_BAD_ARG;
-  if ((h | w) & 3) return NLT_ERR_UNSUPPORTED;
-  if (u8 && (w & 7)) return NLT_ERR_UNSUPPORTED;                        // 8-byte pieces of a uint8 row
-  if (!(alpha >= 0.f && alpha <= 1.f)) return NLT_ERR_UNSUPPORTED;
-  if (!nlt_aligned16(packed) || !nlt_aligned16(packed_l2) || !nlt_aligned16(q1) || !nlt_aligned16(qtmp2) || !nlt_aligned16(p1) ||
-      !nlt_aligned16(s0) || !nlt_aligned16(p2))
-    return NLT_ERR_BAD_ARG;
-  if (!nlt_aligned16(base) || !nlt_aligned16(cvis) || !nlt_aligned16(lvis)) return NLT_ERR_UNSUPPORTED;
-  if ((long long)n * h * w * 3 >= (1ll << 31) || (long long)h * w * 16 >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
-  const int ty = (h / 2 + SH - 1) / SH, tx = (w / 2 + SW - 1) / SW;
-  const long tiles = (long)n * ty * tx;
-  if (tiles >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
-  constexpr int NW = 8;
-  const long per_xcd = (tiles + 7) / 8;
-  long groups = per_xcd;
-  if (groups > 32) groups = 32;
+  StripGrid g;
+  const int rc = front_strip_check(
+      front_all_set(base, cvis, lvis, packed, packed_l2, p1, s0, p2, q1, skip3, qtmp2) && (!u8 || ids),
+      n > 0 && h > 0 && w > 0 && ldq >= 16 && !(ldq & 3), u8, n, h, w, alpha, front_all_aligned16(packed, packed_l2, q1, qtmp2, p1, s0, p2),
+      front_all_aligned16(base, cvis, lvis), (long long)n * h * w * 3 < (1ll << 31) && (long long)h * w * 16 < (1ll << 31), g);
+  if (rc != NLT_OK) return rc;
   OvrMaps maps = {p1, s0, p2};
-  const dim3 grid((unsigned)(8 * groups)), block(64 * NW);
+  const dim3 grid(g.blocks), block(64 * NWAVES);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (u8)
-    hipLaunchKernelGGL((front_ovr_kernel<NW, true>), grid, block, 0, s, base, cvis, lvis, ids, h, w, ty, tx, (int)tiles, packed, packed_l2,
+    hipLaunchKernelGGL((front_ovr_kernel<NWAVES, true>), grid, block, 0, s, base, cvis, lvis, ids, h, w, g.ty, g.tx, g.tiles, packed, packed_l2,
                        maps, add_base, alpha, q1, ldq, skip3, qtmp2);
   else
-    hipLaunchKernelGGL((front_ovr_kernel<NW, false>), grid, block, 0, s, base, cvis, lvis, ids, h, w, ty, tx, (int)tiles, packed, packed_l2,
+    hipLaunchKernelGGL((front_ovr_kernel<NWAVES, false>), grid, block, 0, s, base, cvis, lvis, ids, h, w, g.ty, g.tx, g.tiles, packed, packed_l2,
                        maps, add_base, alpha, q1, ldq, skip3, qtmp2);
   NLT_CHECK_LAUNCH();
   return NLT_OK;

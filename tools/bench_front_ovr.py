@@ -34,5 +34,4 @@ torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / reps
 moved = 4 * n * h * w * (5 + 3) + 4 * n * (h // 2) * (w // 2) * 16 + 4 * n * (h // 4) * (w // 4) * 32 + 4 * (p1.numel() + s0.numel() + p2.numel())
 flops = 2 * n * (h // 2) * (w // 2) * (20 + 64) * 16 + 2 * n * h * w * 15 + 2 * n * (h // 4) * (w // 4) * 64 * 32
-print("front_ovr %dx%d^2: %.4f ms  %.1f GB/s of its own traffic  %.1f TFLOP/s  (NLT_FRONT_OVR=%s)"
-      % (n, uv, ms, moved / ms / 1e6, flops / ms / 1e9, os.environ.get('NLT_FRONT_OVR', '')))
+print("front_ovr %dx%d^2: %.4f ms  %.1f GB/s of its own traffic  %.1f TFLOP/s" % (n, uv, ms, moved / ms / 1e6, flops / ms / 1e9))
