@@ -17,6 +17,7 @@
 // lane ends up with 4 consecutive output channels of one texel), and hand the stride-2 results to the
 // stride-1 stage through LDS.
 #include "front_common.h"
+#include "tail_tile.h"
 
 namespace {
 
@@ -123,10 +124,8 @@ __global__ __launch_bounds__(256) void front_kernel(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int kk = lane >> 4, j = lane & 15;
   const int h2 = h >> 1, w2 = w >> 1;
-  int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int tx0 = (tile % tiles_x) * TW; tile /= tiles_x;
-  const int ty0 = (tile % tiles_y) * TH;
-  const int f = tile / tiles_y;
+  const TileAt at(tiles_y, tiles_x);
+  const int tx0 = at.tx0, ty0 = at.ty0, f = at.f;
   const long hw = (long)h * w;
 
   // ---- stage 1: folded stride-2 convs on the haloed tile, straight from the raw buffers
@@ -151,12 +150,10 @@ __global__ __launch_bounds__(256) void front_kernel(
 
   constexpr int KU = 4;                                                // observations whose loads are issued together
   for (int mt = wave; mt < NT; mt += 4) {
-    const int t = mt * 16 + j;
-    const bool live = t < HT;
-    const int hy = live ? t / HW : 0, hx = live ? t % HW : 0;
-    const int gy = ty0 + hy, gx = tx0 + hx;
-    const bool inside = live && gy < h2 && gx < w2;                    // beyond the image: the s1 conv's zero padding
-    const bool owned = inside && hy < TH && hx < TW;
+    const HaloTexel<0> ht(mt, j, ty0, tx0, h2, w2);                          // halo below / right: TF 'same' reads (y + a, x + b)
+    const int t = ht.t, gy = ht.gy, gx = ht.gx;
+    const bool live = ht.live, inside = ht.inside;
+    const bool owned = inside && ht.hy < TH && ht.hx < TW;
     const int fy = inside ? 2 * gy + (kk >> 1) : 0, fx = inside ? 2 * gx + (kk & 1) : 0;
     const long pix = (long)fy * w + fx;
     const long tex = (long)f * hw + pix;                               // this lane's full-resolution texel (tap kk)
@@ -354,8 +351,6 @@ __global__ __launch_bounds__(256) void front_kernel(
 // virtual concat [x | fm1], 16 columns = (a,b,o)), its 2x2x4 outputs go to a full-resolution LDS tile;
 // stage 2 = Conv2DTranspose k2s1 (4 -> 4), head (4 -> 3) + skip3, per full-resolution texel on the VALU.
 // ---------------------------------------------------------------------------------------
-constexpr int FH = 2 * TH + 1, FW = 2 * TW + 1;        // 17 x 33 full-resolution texels incl. top/left halo
-
 // OVR (nlt_back_forward_map: the reference's inference mode, engine_infer.py): `fm1` is the interleaved level-1 map of which
 // only the 16 QUERY channels are read (per-texel stride ld1), w_s2 is the Keras (2,2,4,24) slice over [x 8 | query 16], and what
 // the given half adds to the first conv's pre-activation (+ its bias) arrives as bmap [1,2 h2,2 w2,4], shared by all frames.
@@ -370,10 +365,8 @@ __global__ __launch_bounds__(256) void back_kernel(
   __shared__ __attribute__((aligned(16))) float tile_lds[FH * FW * 4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int kk = lane >> 4, j = lane & 15;
-  int tile = xcd_tile(blockIdx.x, gridDim.x);
-  const int tx0 = (tile % tiles_x) * TW; tile /= tiles_x;
-  const int ty0 = (tile % tiles_y) * TH;
-  const int f = tile / tiles_y;
+  const TileAt at(tiles_y, tiles_x);
+  const int tx0 = at.tx0, ty0 = at.ty0, f = at.f;
   const long hw2 = (long)h2 * w2;
 
   // A operands: column i = (ab = i >> 2, o = i & 3) of the Keras (2,2,Cout=4,Cin=40) kernel = row i of [16][40]
@@ -394,12 +387,8 @@ __global__ __launch_bounds__(256) void back_kernel(
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int mt = wave + 4 * it;
-    const int t = mt * 16 + j;
-    const bool live = mt < NT && t < HT;
-    const int hy = live ? t / HW : 0, hx = live ? t % HW : 0;
-    const int gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
-    const bool inside = live && gy >= 0 && gx >= 0 && gy < h2 && gx < w2;
-    const long tex = (long)f * hw2 + (inside ? (long)gy * w2 + gx : 0);
+    const HaloTexel<-1> ht(mt < NT ? mt : NT, j, ty0, tx0, h2, w2);    // (the wave has no third column tile: not live)
+    const long tex = (long)f * hw2 + (ht.inside ? (long)ht.gy * w2 + ht.gx : 0);
 #pragma unroll
     for (int c = 0; c < NCK; ++c) {
       const int c0 = 16 * c + 4 * kk;                                  // channel of the virtual concat [x 8 | fm1 32 (OVR: its query 16)]
@@ -413,7 +402,7 @@ __global__ __launch_bounds__(256) void back_kernel(
     if constexpr (OVR) {
       mq[it] = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (mt < NT)
-        mq[it] = *reinterpret_cast<const f32x4*>(bmap + (inside ? ((long)(2 * gy + (kk >> 1)) * (2 * w2) + 2 * gx + (kk & 1)) * 4 : 0));
+        mq[it] = *reinterpret_cast<const f32x4*>(bmap + (ht.inside ? ((long)(2 * ht.gy + (kk >> 1)) * (2 * w2) + 2 * ht.gx + (kk & 1)) * 4 : 0));
     }
   }
   const int h = 2 * h2, w = 2 * w2;
@@ -429,11 +418,9 @@ __global__ __launch_bounds__(256) void back_kernel(
   for (int it = 0; it < NIT; ++it) {
     const int mt = wave + 4 * it;
     if (mt >= NT) break;
-    const int t = mt * 16 + j;
-    const bool live = t < HT;
-    const int hy = live ? t / HW : 0, hx = live ? t % HW : 0;
-    const int gy = ty0 - 1 + hy, gx = tx0 - 1 + hx;
-    const bool inside = live && gy >= 0 && gx >= 0 && gy < h2 && gx < w2;
+    const HaloTexel<-1> ht(mt, j, ty0, tx0, h2, w2);
+    const int gy = ht.gy, gx = ht.gx;
+    const bool inside = ht.inside;
     f32x4 acc = OVR ? mq[it] : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NCK; ++c) {
@@ -442,9 +429,9 @@ __global__ __launch_bounds__(256) void back_kernel(
     }
     acc = lrelu4(acc + bs2, alpha);
     if (!inside) acc = (f32x4){0.f, 0.f, 0.f, 0.f};                    // zero padding above / left of the image
-    const int ly = 2 * hy + (kk >> 1) - 1, lx = 2 * hx + (kk & 1) - 1;  // lane kk holds output sub-texel (a,b) = kk
-    if (live && ly >= 0 && lx >= 0) *reinterpret_cast<f32x4*>(tile_lds + (ly * FW + lx) * 4) = acc;
-    if (usave && inside && hy >= 1 && hx >= 1)                          // training: the block's own texels of the 4-channel map
+    int slot;                                                          // lane kk holds output sub-texel (a,b) = kk
+    if (ht.scatter(kk, slot)) *reinterpret_cast<f32x4*>(tile_lds + slot * 4) = acc;
+    if (usave && inside && ht.hy >= 1 && ht.hx >= 1)                    // training: the block's own texels of the 4-channel map
       *reinterpret_cast<f32x4*>(usave + (((long)f * 2 * h2 + 2 * gy + (kk >> 1)) * 2 * w2 + 2 * gx + (kk & 1)) * 4) = acc;
   }
   __syncthreads();
@@ -566,17 +553,19 @@ extern "C" int nlt_front2_forward(const float* base, const float* cvis, const fl
   return NLT_OK;
 }
 
-static int back_launch(const float* x, const float* fm1, const float* skip3, int n, int h2, int w2,
-                       const float* w_s2, const float* b_s2, const float* w_s1, const float* b_s1,
-                       const float* w_head, float alpha, float* pred, float* u, float* v, void* stream) {
-  if (!x || !fm1 || !skip3 || !w_s2 || !b_s2 || !w_s1 || !b_s1 || !w_head || !pred) return NLT_ERR_BAD_ARG;
-  if (n <= 0 || h2 <= 0 || w2 <= 0) return NLT_ERR_BAD_ARG;
-  if (!nlt_aligned16(x) || !nlt_aligned16(fm1) || !nlt_aligned16(w_s2) || !nlt_aligned16(b_s2)) return NLT_ERR_BAD_ARG;
+// back_forward / back_forward_train (OVR = false: ld1 = 32, no map) and back_forward_map (OVR: b_s2 is not read)
+template <bool OVR>
+static int back_launch(const float* x, const float* fm1, int ld1, const float* skip3, int n, int h2, int w2,
+                       const float* w_s2, const float* b_s2, const float* w_s1, const float* b_s1, const float* w_head,
+                       float alpha, const float* bmap, float* pred, float* u, float* v, void* stream) {
+  if (!x || !fm1 || !skip3 || !w_s2 || !b_s2 || !w_s1 || !b_s1 || !w_head || !pred || (OVR && !bmap)) return NLT_ERR_BAD_ARG;
+  if (n <= 0 || h2 <= 0 || w2 <= 0 || ld1 < 16 || (ld1 & 3)) return NLT_ERR_BAD_ARG;
+  if (!nlt_aligned16(x) || !nlt_aligned16(fm1) || !nlt_aligned16(w_s2) || !nlt_aligned16(OVR ? bmap : b_s2)) return NLT_ERR_BAD_ARG;
   if ((long long)n * h2 * w2 * 4 * 8 >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
   const int ty = (h2 + TH - 1) / TH, tx = (w2 + TW - 1) / TW;
   const long blocks = (long)n * ty * tx;
-  hipLaunchKernelGGL(back_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     x, fm1, skip3, h2, w2, ty, tx, w_s2, b_s2, w_s1, b_s1, w_head, alpha, pred, u, v, 32, nullptr);
+  hipLaunchKernelGGL(back_kernel<OVR>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     x, fm1, skip3, h2, w2, ty, tx, w_s2, b_s2, w_s1, b_s1, w_head, alpha, pred, u, v, ld1, bmap);
   NLT_CHECK_LAUNCH();
   return NLT_OK;
 }
@@ -584,27 +573,19 @@ static int back_launch(const float* x, const float* fm1, const float* skip3, int
 extern "C" int nlt_back_forward_map(const float* x, const float* q1, int ldq, const float* skip3, int n, int h2, int w2,
                                     const float* w_s2q, const float* w_s1, const float* b_s1, const float* w_head, float alpha,
                                     const float* bias_map, float* pred, void* stream) {
-  if (!x || !q1 || !skip3 || !w_s2q || !w_s1 || !b_s1 || !w_head || !bias_map || !pred) return NLT_ERR_BAD_ARG;
-  if (n <= 0 || h2 <= 0 || w2 <= 0 || ldq < 16 || (ldq & 3)) return NLT_ERR_BAD_ARG;
-  if (!nlt_aligned16(x) || !nlt_aligned16(q1) || !nlt_aligned16(w_s2q) || !nlt_aligned16(bias_map)) return NLT_ERR_BAD_ARG;
-  if ((long long)n * h2 * w2 * 4 * 8 >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
-  const int ty = (h2 + TH - 1) / TH, tx = (w2 + TW - 1) / TW;
-  const long blocks = (long)n * ty * tx;
-  hipLaunchKernelGGL(back_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     x, q1, skip3, h2, w2, ty, tx, w_s2q, b_s1, w_s1, b_s1, w_head, alpha, pred, nullptr, nullptr, ldq, bias_map);
-  NLT_CHECK_LAUNCH();
-  return NLT_OK;
+  return back_launch<true>(x, q1, ldq, skip3, n, h2, w2, w_s2q, b_s1, w_s1, b_s1, w_head, alpha, bias_map, pred, nullptr, nullptr,
+                           stream);
 }
 
 extern "C" int nlt_back_forward(const float* x, const float* fm1, const float* skip3, int n, int h2, int w2,
                                 const float* w_s2, const float* b_s2, const float* w_s1, const float* b_s1,
                                 const float* w_head, float alpha, float* pred, void* stream) {
-  return back_launch(x, fm1, skip3, n, h2, w2, w_s2, b_s2, w_s1, b_s1, w_head, alpha, pred, nullptr, nullptr, stream);
+  return back_launch<false>(x, fm1, 32, skip3, n, h2, w2, w_s2, b_s2, w_s1, b_s1, w_head, alpha, nullptr, pred, nullptr, nullptr, stream);
 }
 
 extern "C" int nlt_back_forward_train(const float* x, const float* fm1, const float* skip3, int n, int h2, int w2,
                                       const float* w_s2, const float* b_s2, const float* w_s1, const float* b_s1,
                                       const float* w_head, float alpha, float* pred, float* u, float* v, void* stream) {
   if (!u || !v || !nlt_aligned16(u) || !nlt_aligned16(v)) return NLT_ERR_BAD_ARG;
-  return back_launch(x, fm1, skip3, n, h2, w2, w_s2, b_s2, w_s1, b_s1, w_head, alpha, pred, u, v, stream);
+  return back_launch<false>(x, fm1, 32, skip3, n, h2, w2, w_s2, b_s2, w_s1, b_s1, w_head, alpha, nullptr, pred, u, v, stream);
 }

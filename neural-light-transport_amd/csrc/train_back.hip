@@ -13,12 +13,10 @@
 // bwd.L12.q.s2.{wgrad,dgrad.x,dgrad.skip}: seven launches over 4-channel full-resolution tensors (the weight-gradient
 // kernel alone took 0.43 ms on the 4 -> 4 layer at 4 x 1024^2).  Deterministic: per-workgroup partial sums, then a
 // fixed-order reduction.
-#include "nlt_common.h"
+#include "tail_tile.h"
 
 namespace {
 
-constexpr int BTH = 8, BTW = 16;                                       // half-resolution tile
-constexpr int BFH = 2 * BTH, BFW = 2 * BTW;                            // 16 x 32 full-resolution texels
 constexpr int BB_DW2 = 0, BB_DW1 = 640, BB_DWH = 704, BB_DBH = 716, BB_DB1 = 719, BB_DB2 = 723, BB_TOT = 728;
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -27,31 +25,29 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// PARTS: 3 = everything, the only form launched.  (r05 also launched 1 = backward-data only on the chain + 2 = the weight / bias
-// sums on the weight-gradient stream: 3.16 vs 3.06 ms per l2 step -- the second launch re-reads (v, dpred, u) beside the chain's
-// full-resolution launches -- so the split entry point was removed in r06; profiles/README.md r05.)
-template <int PARTS>
+// One launch does everything.  (r05 also split it into backward-data only on the chain + the weight / bias sums on the weight-
+// gradient stream: 3.16 vs 3.06 ms per l2 step -- the second launch re-reads (v, dpred, u) beside the chain's full-resolution
+// launches -- so the split form was removed in r06; profiles/README.md r05.)
 __global__ __launch_bounds__(256) void back_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ fm1, const float* __restrict__ u, const float* __restrict__ v,
     const float* __restrict__ dpred, int h2, int w2, int tiles_y, int tiles_x, long tiles,
     const float* __restrict__ w_s2, const float* __restrict__ w_s1, const float* __restrict__ w_head, float alpha,
     float* __restrict__ dx, float* __restrict__ dfm1, float* __restrict__ ws) {
-  __shared__ __attribute__((aligned(16))) float dvp[(BFH + 1) * (BFW + 1) * 4];
-  __shared__ __attribute__((aligned(16))) float dup[BFH * BFW * 4];
-  __shared__ __attribute__((aligned(16))) float utile[(BFH + 1) * (BFW + 1) * 4];   // u with its top / left halo: u(Y0 - 1 + ly, X0 - 1 + lx)
+  __shared__ __attribute__((aligned(16))) float dvp[FH * FW * 4];
+  __shared__ __attribute__((aligned(16))) float dup[2 * TH * 2 * TW * 4];
+  __shared__ __attribute__((aligned(16))) float utile[FH * FW * 4];   // u with its top / left halo: u(Y0 - 1 + ly, X0 - 1 + lx)
   __shared__ float red[4][BB_TOT];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int kk = lane >> 4, j = lane & 15;
   const int h = 2 * h2, w = 2 * w2;
 
-  constexpr bool DG = (PARTS & 1) != 0, WG = (PARTS & 2) != 0;
   float wa[3][4];                                                      // dgrad A operands: W_s2[n = 4 kk + ks][c = 16 mt + j]
 #pragma unroll
   for (int mt = 0; mt < 3; ++mt)
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       const int c = 16 * mt + j;
-      wa[mt][ks] = (DG && c < 40) ? w_s2[(4 * kk + ks) * 40 + c] : 0.f;
+      wa[mt][ks] = c < 40 ? w_s2[(4 * kk + ks) * 40 + c] : 0.f;
     }
   float wh[12];
 #pragma unroll
@@ -67,9 +63,9 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
   f32x4 accw2[3] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
 
   for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int tx0 = (int)(tile % tiles_x) * BTW;
+    const int tx0 = (int)(tile % tiles_x) * TW;
     const long tr = tile / tiles_x;
-    const int ty0 = (int)(tr % tiles_y) * BTH, f = (int)(tr / tiles_y);
+    const int ty0 = (int)(tr % tiles_y) * TH, f = (int)(tr / tiles_y);
     const int Y0 = 2 * ty0, X0 = 2 * tx0;
 
     // ---- every global load of the tile is issued HERE, before the first barrier: the three phases used to fetch their own
@@ -82,21 +78,20 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
 #pragma unroll
     for (int it = 0; it < 3; ++it) {
       const int e = threadIdx.x + 256 * it;
-      const int ec = e < (BFH + 1) * (BFW + 1) ? e : 0;
-      const int ly = ec / (BFW + 1), lx = ec - ly * (BFW + 1);
+      const int ec = e < FH * FW ? e : 0;
+      const int ly = ec / FW, lx = ec - ly * FW;
       const int y = Y0 + ly, xg = X0 + lx;
-      in_v[it] = e < (BFH + 1) * (BFW + 1) && y < h && xg < w;
+      in_v[it] = e < FH * FW && y < h && xg < w;
       const long tex = in_v[it] ? ((long)f * h + y) * w + xg : 0;
       pv[it] = *reinterpret_cast<const f32x4*>(v + tex * 4);
       pg[it][0] = dpred[tex * 3]; pg[it][1] = dpred[tex * 3 + 1]; pg[it][2] = dpred[tex * 3 + 2];
       const int yu = y - 1, xu = xg - 1;
-      in_u[it] = e < (BFH + 1) * (BFW + 1) && yu >= 0 && xu >= 0 && yu < h && xu < w;
+      in_u[it] = e < FH * FW && yu >= 0 && xu >= 0 && yu < h && xu < w;
       const long texu = in_u[it] ? ((long)f * h + yu) * w + xu : 0;
       pu[it] = *reinterpret_cast<const f32x4*>(u + texu * 4);
     }
     float pb[8][3];                                                    // phase 3a's B operands (x | fm1 channels 16 mt + j of texel (gi, kk))
     const int na = j >> 3, nb = (j >> 2) & 1, no = j & 3;
-    if constexpr (WG) {
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) {
       const int gi = wave + 4 * g8;
@@ -112,9 +107,7 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
         pb[g8][mt] = !inside ? 0.f : (c < 8 ? vx : (c < 40 ? vf : 0.f));
       }
     }
-    }
     f32x4 pxv[2];                                                      // phase 3b: x at channels 4 kk (kk < 2) of texel (ty0 + wave + 4 r, tx0 + j)
-    if constexpr (DG) {
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int gy = ty0 + wave + 4 * r, gx = tx0 + j;
@@ -122,14 +115,13 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
       const long tex2 = inside ? ((long)f * h2 + gy) * w2 + gx : 0;
       pxv[r] = *reinterpret_cast<const f32x4*>(x + tex2 * 8 + (kk < 2 ? 4 * kk : 0));
     }
-    }
 
     // ---- phase 1
 #pragma unroll
     for (int it = 0; it < 3; ++it) {
       const int e = threadIdx.x + 256 * it;
-      if (e >= (BFH + 1) * (BFW + 1)) break;
-      const int ly = e / (BFW + 1), lx = e - ly * (BFW + 1);
+      if (e >= FH * FW) break;
+      const int ly = e / FW, lx = e - ly * FW;
       const int y = Y0 + ly, xg = X0 + lx;
       f32x4 d = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (in_v[it]) {
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
           const float dl = wh[o * 3] * g[0] + wh[o * 3 + 1] * g[1] + wh[o * 3 + 2] * g[2];
           d[o] = vv[o] > 0.f ? dl : alpha * dl;
         }
-        if (WG && ly < BFH && lx < BFW) {
+        if (ly < 2 * TH && lx < 2 * TW) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
 #pragma unroll
@@ -165,11 +157,11 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
       f32x4 dp = (f32x4){0.f, 0.f, 0.f, 0.f};
       if (y < h && xg < w) {
         const f32x4 zero = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const f32x4 u0 = *reinterpret_cast<const f32x4*>(utile + ((ly + 1) * (BFW + 1) + lx + 1) * 4);
+        const f32x4 u0 = *reinterpret_cast<const f32x4*>(utile + ((ly + 1) * FW + lx + 1) * 4);
         f32x4 du = zero;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const f32x4 dv = *reinterpret_cast<const f32x4*>(dvp + ((ly + (t >> 1)) * (BFW + 1) + lx + (t & 1)) * 4);
+          const f32x4 dv = *reinterpret_cast<const f32x4*>(dvp + ((ly + (t >> 1)) * FW + lx + (t & 1)) * 4);
 #pragma unroll
           for (int o = 0; o < 4; ++o)
 #pragma unroll
@@ -178,43 +170,40 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           dp[c] = u0[c] > 0.f ? du[c] : alpha * du[c];
-          if (WG) accb2[c] += dp[c];
+          accb2[c] += dp[c];
         }
       }
       *reinterpret_cast<f32x4*>(dup + e * 4) = dp;
     }
     // dW_s1[t][o][c] += sum_texels u(y - a, x - b)[c] dv(y, x)[o]: rows (t, c) = lane & 15, columns o = lane & 15 (< 4), K = 4
     // texels per MFMA; the wave takes a quarter of the tile (dv is zero outside the image, so clipped tiles need no mask)
-    if constexpr (WG) {
+    {
       const int ta = (j >> 3) & 1, tb = (j >> 2) & 1, cc = j & 3;
 #pragma unroll 4
       for (int m = 0; m < 32; ++m) {
         const int k = wave * 128 + 4 * m + kk;
         const int ly = k >> 5, lx = k & 31;
-        const float av = utile[((ly + 1 - ta) * (BFW + 1) + lx + 1 - tb) * 4 + cc];
-        const float bv = j < 4 ? dvp[(ly * (BFW + 1) + lx) * 4 + j] : 0.f;
+        const float av = utile[((ly + 1 - ta) * FW + lx + 1 - tb) * 4 + cc];
+        const float bv = j < 4 ? dvp[(ly * FW + lx) * 4 + j] : 0.f;
         acc1m = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc1m, 0, 0, 0);
       }
     }
     __syncthreads();
 
     // ---- phase 3a: dW_s2^T, rows n = (a, b, o), columns c, K = half-resolution texels
-    if constexpr (WG) {
 #pragma unroll
     for (int g8 = 0; g8 < 8; ++g8) {
       const int gi = wave + 4 * g8;
       const int ii = gi >> 2, jj = (gi & 3) * 4 + kk;
-      const float av = dup[((2 * ii + na) * BFW + 2 * jj + nb) * 4 + no];
+      const float av = dup[((2 * ii + na) * (2 * TW) + 2 * jj + nb) * 4 + no];
 #pragma unroll
       for (int mt = 0; mt < 3; ++mt) accw2[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, pb[g8][mt], accw2[mt], 0, 0, 0);
     }
-    }
     // ---- phase 3b: d_in = W_s2^T du, 16 texels (one tile row) per MFMA column block
-    if constexpr (DG) {
-    for (int ii = wave; ii < BTH; ii += 4) {
+    for (int ii = wave; ii < TH; ii += 4) {
       const int gy = ty0 + ii, gx = tx0 + j;
       const bool inside = gy < h2 && gx < w2;
-      const f32x4 bvec = *reinterpret_cast<const f32x4*>(dup + ((2 * ii + (kk >> 1)) * BFW + 2 * j + (kk & 1)) * 4);
+      const f32x4 bvec = *reinterpret_cast<const f32x4*>(dup + ((2 * ii + (kk >> 1)) * (2 * TW) + 2 * j + (kk & 1)) * 4);
       const long tex2 = ((long)f * h2 + gy) * w2 + gx;
 #pragma unroll
       for (int mt = 0; mt < 3; ++mt) {
@@ -234,10 +223,8 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
         }
       }
     }
-    }
     __syncthreads();
   }
-  if constexpr (!WG) return;
 
   // ---- block partial sums -> workspace
   float* r = red[wave];
@@ -271,26 +258,10 @@ __global__ __launch_bounds__(256) void back_bwd_kernel(
 struct BackBwdOut { float *dw_s2, *db_s2, *dw_s1, *db_s1, *dw_head, *db_head; };
 
 __global__ __launch_bounds__(256) void back_bwd_reduce_kernel(const float* __restrict__ ws, int nblocks, BackBwdOut out) {
-  __shared__ float part[16][17];                                       // 16 entries x 16 row groups (x 4 running sums), fixed order
-  const int e = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + e;
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int bl = g;
-  if (idx < BB_TOT - 1) {
-    for (; bl + 48 < nblocks; bl += 64) {
-      s0 += ws[(long)bl * BB_TOT + idx];
-      s1 += ws[(long)(bl + 16) * BB_TOT + idx];
-      s2 += ws[(long)(bl + 32) * BB_TOT + idx];
-      s3 += ws[(long)(bl + 48) * BB_TOT + idx];
-    }
-    for (; bl < nblocks; bl += 16) s0 += ws[(long)bl * BB_TOT + idx];
-  }
-  part[g][e] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (g || idx >= BB_TOT - 1) return;
-  float t = 0.f;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) t += part[q][e];
+  __shared__ float part[16][17];
+  const int idx = blockIdx.x * 16 + (threadIdx.x & 15);
+  const float t = ordered_row_sum(ws, idx < BB_TOT - 1 ? nblocks : 0, BB_TOT, idx, part);   // (the last entry is padding)
+  if ((threadIdx.x >> 4) || idx >= BB_TOT - 1) return;
   if (idx < BB_DW1) out.dw_s2[idx] += t;
   else if (idx < BB_DWH) out.dw_s1[idx - BB_DW1] += t;
   else if (idx < BB_DBH) out.dw_head[idx - BB_DWH] += t;
@@ -300,7 +271,7 @@ __global__ __launch_bounds__(256) void back_bwd_reduce_kernel(const float* __res
 }
 
 long back_bwd_blocks(int n, int h2, int w2) {
-  const long tiles = (long)n * ((h2 + BTH - 1) / BTH) * ((w2 + BTW - 1) / BTW);
+  const long tiles = (long)n * ((h2 + TH - 1) / TH) * ((w2 + TW - 1) / TW);
   return tiles < 1024 ? tiles : 1024;
 }
 
@@ -311,40 +282,25 @@ extern "C" long nlt_back_backward_workspace_floats(int n, int h2, int w2) {
   return back_bwd_blocks(n, h2, w2) * BB_TOT;
 }
 
-namespace {
-int back_backward_launch(const float* x, const float* fm1, const float* u, const float* v, const float* dpred,
-                         int n, int h2, int w2, const float* w_s2, const float* w_s1, const float* w_head,
-                         float alpha, float* dx, float* dfm1, float* dw_s2, float* db_s2, float* dw_s1,
-                         float* db_s1, float* dw_head, float* db_head, float* workspace, void* stream) {
-  constexpr int parts = 3;
-  if (!x || !fm1 || !u || !v || !dpred || !w_s2 || !w_s1 || !w_head) return NLT_ERR_BAD_ARG;
-  if ((parts & 1) && (!dx || !dfm1)) return NLT_ERR_BAD_ARG;
-  if ((parts & 2) && (!dw_s2 || !db_s2 || !dw_s1 || !db_s1 || !dw_head || !db_head || !workspace)) return NLT_ERR_BAD_ARG;
-  if (n <= 0 || h2 <= 0 || w2 <= 0) return NLT_ERR_BAD_ARG;
-  if (!nlt_aligned16(u) || !nlt_aligned16(v) || ((parts & 1) && (!nlt_aligned16(dx) || !nlt_aligned16(dfm1)))) return NLT_ERR_BAD_ARG;
-  if ((long long)n * h2 * w2 * 4 * 8 >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int ty = (h2 + BTH - 1) / BTH, tx = (w2 + BTW - 1) / BTW;
-  const long tiles = (long)n * ty * tx;
-  const int blocks = (int)back_bwd_blocks(n, h2, w2);
-#define NLT_BB(P_) hipLaunchKernelGGL(back_bwd_kernel<P_>, dim3(blocks), dim3(256), 0, s, x, fm1, u, v, dpred, h2, w2, ty, tx, tiles, \
-                                      w_s2, w_s1, w_head, alpha, dx, dfm1, workspace)
-  NLT_BB(3);
-#undef NLT_BB
-  NLT_CHECK_LAUNCH();
-  if (parts & 2) {
-    BackBwdOut out = {dw_s2, db_s2, dw_s1, db_s1, dw_head, db_head};
-    hipLaunchKernelGGL(back_bwd_reduce_kernel, dim3((BB_TOT + 15) / 16), dim3(256), 0, s, workspace, blocks, out);
-    NLT_CHECK_LAUNCH();
-  }
-  return NLT_OK;
-}
-}  // namespace
-
 extern "C" int nlt_back_backward(const float* x, const float* fm1, const float* u, const float* v, const float* dpred,
                                  int n, int h2, int w2, const float* w_s2, const float* w_s1, const float* w_head,
                                  float alpha, float* dx, float* dfm1, float* dw_s2, float* db_s2, float* dw_s1,
                                  float* db_s1, float* dw_head, float* db_head, float* workspace, void* stream) {
-  return back_backward_launch(x, fm1, u, v, dpred, n, h2, w2, w_s2, w_s1, w_head, alpha, dx, dfm1, dw_s2, db_s2, dw_s1, db_s1, dw_head,
-                              db_head, workspace, stream);
+  if (!x || !fm1 || !u || !v || !dpred || !w_s2 || !w_s1 || !w_head || !dx || !dfm1 || !dw_s2 || !db_s2 || !dw_s1 || !db_s1 ||
+      !dw_head || !db_head || !workspace)
+    return NLT_ERR_BAD_ARG;
+  if (n <= 0 || h2 <= 0 || w2 <= 0) return NLT_ERR_BAD_ARG;
+  if (!nlt_aligned16(u) || !nlt_aligned16(v) || !nlt_aligned16(dx) || !nlt_aligned16(dfm1)) return NLT_ERR_BAD_ARG;
+  if ((long long)n * h2 * w2 * 4 * 8 >= (1ll << 31)) return NLT_ERR_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int ty = (h2 + TH - 1) / TH, tx = (w2 + TW - 1) / TW;
+  const long tiles = (long)n * ty * tx;
+  const int blocks = (int)back_bwd_blocks(n, h2, w2);
+  hipLaunchKernelGGL(back_bwd_kernel, dim3(blocks), dim3(256), 0, s, x, fm1, u, v, dpred, h2, w2, ty, tx, tiles,
+                     w_s2, w_s1, w_head, alpha, dx, dfm1, workspace);
+  NLT_CHECK_LAUNCH();
+  BackBwdOut out = {dw_s2, db_s2, dw_s1, db_s1, dw_head, db_head};
+  hipLaunchKernelGGL(back_bwd_reduce_kernel, dim3((BB_TOT + 15) / 16), dim3(256), 0, s, workspace, blocks, out);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
 }

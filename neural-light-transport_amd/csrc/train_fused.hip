@@ -17,7 +17,7 @@
 // the products.  Replaces, of the unfused backward plan (engine.py): bwd.L1.{q,o}.s2.{wgrad,dgrad}, the query half's
 // accumulate into dfm0, bwd.L0.stem and the skip rows of bwd.head; reads 5 + 6k + 3 floats per texel instead of
 // ~100 (the 32-channel full-resolution gradient alone is written and read once each in the unfused plan).
-#include "nlt_common.h"
+#include "tail_tile.h"
 
 namespace {
 
@@ -28,7 +28,31 @@ constexpr int T_GO = 1024;     // [row tap*3+c 16 (12 used)][o 16]
 constexpr int T_SQ = 1280, T_SO = 1296, T_P = 1312;   // [16] each (P: col tap'*3+o)
 constexpr int T_TOT = 1328;
 
-template <bool PIPE>
+// The end of both kernels below: a wave's accumulators -- lane (kk, i) holds rows 4kk..4kk+3, column i of each -- go to part[wave],
+// the four waves are added in a fixed order and the sum is the workgroup's row of the workspace.
+__device__ __forceinline__ void front_bwd_store_row(float (&part)[4][T_TOT], const f32x4 (&gq)[2], const f32x4 (&rr)[2], f32x4 go,
+                                                    float sq, float so, float sp, float* __restrict__ ws) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, kk = lane >> 4;
+  float* p = part[wave];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+      p[T_GQ + (a * 16 + 4 * kk + r) * 16 + i] = gq[a][r];
+      p[T_R + (a * 16 + 4 * kk + r) * 16 + i] = rr[a][r];
+    }
+    p[T_GO + (4 * kk + r) * 16 + i] = go[r];
+  }
+  sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
+  so += __shfl_xor(so, 16); so += __shfl_xor(so, 32);
+  sp += __shfl_xor(sp, 16); sp += __shfl_xor(sp, 32);
+  if (kk == 0) { p[T_SQ + i] = sq; p[T_SO + i] = so; p[T_P + i] = sp; }
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < T_TOT; idx += 256)
+    ws[(long)blockIdx.x * T_TOT + idx] = (part[0][idx] + part[1][idx]) + (part[2][idx] + part[3][idx]);
+}
+
 __global__ __launch_bounds__(256) void front_bwd_kernel(
     const float* __restrict__ base, const float* __restrict__ cvis, const float* __restrict__ lvis,
     const float* __restrict__ nn_rgb, const float* __restrict__ nn_base, const float* __restrict__ dy1q,
@@ -121,37 +145,16 @@ __global__ __launch_bounds__(256) void front_bwd_kernel(
     const long stride = (long)gridDim.x * 4;
     long g = (long)blockIdx.x * 4 + wave;
     Ops cur, nxt;
-    if (PIPE) {
-      if (g < groups) fetch(g, cur);
-      while (g < groups) {
-        const long gn = g + stride;
-        if (gn < groups) fetch(gn, nxt);
-        consume(g, cur);
-        cur = nxt;
-        g = gn;
-      }
-    } else {
-      for (; g < groups; g += stride) { fetch(g, cur); consume(g, cur); }
+    if (g < groups) fetch(g, cur);
+    while (g < groups) {
+      const long gn = g + stride;
+      if (gn < groups) fetch(gn, nxt);
+      consume(g, cur);
+      cur = nxt;
+      g = gn;
     }
   }
-  // lane (kk, i) holds rows 4kk..4kk+3, column i of every accumulator
-  float* p = part[wave];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      p[T_GQ + (a * 16 + 4 * kk + r) * 16 + i] = gq[a][r];
-      p[T_R + (a * 16 + 4 * kk + r) * 16 + i] = rr[a][r];
-    }
-    p[T_GO + (4 * kk + r) * 16 + i] = go[r];
-  }
-  sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
-  so += __shfl_xor(so, 16); so += __shfl_xor(so, 32);
-  sp += __shfl_xor(sp, 16); sp += __shfl_xor(sp, 32);
-  if (kk == 0) { p[T_SQ + i] = sq; p[T_SO + i] = so; p[T_P + i] = sp; }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < T_TOT; idx += 256)
-    ws[(long)blockIdx.x * T_TOT + idx] = (part[0][idx] + part[1][idx]) + (part[2][idx] + part[3][idx]);
+  front_bwd_store_row(part, gq, rr, go, sq, so, sp, ws);
 }
 
 // ---- second generation: operands staged through wave-private LDS ------------------------------------------------------
@@ -307,47 +310,15 @@ __global__ __launch_bounds__(256) void front_bwd2_kernel(
       run = nxt;
     }
   }
-  // lane (kk, i) holds rows 4kk..4kk+3, column i of every accumulator
-  float* p = part[wave];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-      p[T_GQ + (a * 16 + 4 * kk + r) * 16 + i] = gq[a][r];
-      p[T_R + (a * 16 + 4 * kk + r) * 16 + i] = rr[a][r];
-    }
-    p[T_GO + (4 * kk + r) * 16 + i] = go[r];
-  }
-  sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
-  so += __shfl_xor(so, 16); so += __shfl_xor(so, 32);
-  sp += __shfl_xor(sp, 16); sp += __shfl_xor(sp, 32);
-  if (kk == 0) { p[T_SQ + i] = sq; p[T_SO + i] = so; p[T_P + i] = sp; }
-  __syncthreads();
-  for (int idx = threadIdx.x; idx < T_TOT; idx += 256)
-    ws[(long)blockIdx.x * T_TOT + idx] = (part[0][idx] + part[1][idx]) + (part[2][idx] + part[3][idx]);
+  front_bwd_store_row(part, gq, rr, go, sq, so, sp, ws);
 }
 
-// totals[idx] = sum over the nblocks partial rows: 16 entries per workgroup, rows dealt to 16 thread groups x 4 running sums
-// (a serial walk over ~1000 rows is pure load latency), combined in a fixed order
+// totals[idx] = sum over the nblocks partial rows, 16 entries per workgroup
 __global__ __launch_bounds__(256) void front_bwd_reduce_kernel(const float* __restrict__ ws, int nblocks, float* __restrict__ totals) {
   __shared__ float part[16][17];
-  const int e = threadIdx.x & 15, g = threadIdx.x >> 4;
-  const int idx = blockIdx.x * 16 + e;                                 // T_TOT is a multiple of 16
-  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-  int bl = g;
-  for (; bl + 48 < nblocks; bl += 64) {
-    s0 += ws[(long)bl * T_TOT + idx];
-    s1 += ws[(long)(bl + 16) * T_TOT + idx];
-    s2 += ws[(long)(bl + 32) * T_TOT + idx];
-    s3 += ws[(long)(bl + 48) * T_TOT + idx];
-  }
-  for (; bl < nblocks; bl += 16) s0 += ws[(long)bl * T_TOT + idx];
-  part[g][e] = (s0 + s1) + (s2 + s3);
-  __syncthreads();
-  if (g) return;
-  float s = 0.f;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) s += part[q][e];
+  const int idx = blockIdx.x * 16 + (threadIdx.x & 15);                // T_TOT is a multiple of 16
+  const float s = ordered_row_sum(ws, nblocks, T_TOT, idx, part);
+  if (threadIdx.x >> 4) return;
   totals[idx] = s;
 }
 
@@ -464,7 +435,6 @@ extern "C" int nlt_front_backward(const float* base, const float* cvis, const fl
   const long groups = (long)n * (h / 2) * (w / 8);
   const int blocks = front_bwd_blocks(groups);
   float* totals = workspace + (long)blocks * T_TOT;
-  static const bool pipe = [] { const char* e = getenv("NLT_FRONT_BWD_PIPE"); return !(e && e[0] == '0'); }();
   static const bool staged = [] { const char* e = getenv("NLT_FRONT_BWD_STAGED"); return !(e && e[0] == '0'); }();
   const bool aligned = nlt_aligned16(base) && nlt_aligned16(cvis) && nlt_aligned16(lvis) && nlt_aligned16(nn_rgb) &&
                        nlt_aligned16(nn_base) && nlt_aligned16(dy1q) && nlt_aligned16(dy1o) && nlt_aligned16(dpred);
@@ -475,11 +445,8 @@ extern "C" int nlt_front_backward(const float* base, const float* cvis, const fl
                                        dy1q, dy1o, dpred, h, w, runs, workspace)
     if (k == 1) NLT_FB2(1); else if (k == 2) NLT_FB2(2); else if (k == 3) NLT_FB2(3); else NLT_FB2(4);
 #undef NLT_FB2
-  } else if (pipe)
-    hipLaunchKernelGGL(front_bwd_kernel<true>, dim3(blocks), dim3(256), 0, s, base, cvis, lvis, nn_rgb, nn_base, dy1q, dy1o, dpred,
-                       k, h, w, groups, workspace);
-  else
-    hipLaunchKernelGGL(front_bwd_kernel<false>, dim3(blocks), dim3(256), 0, s, base, cvis, lvis, nn_rgb, nn_base, dy1q, dy1o, dpred,
+  } else
+    hipLaunchKernelGGL(front_bwd_kernel, dim3(blocks), dim3(256), 0, s, base, cvis, lvis, nn_rgb, nn_base, dy1q, dy1o, dpred,
                        k, h, w, groups, workspace);
   NLT_CHECK_LAUNCH();
   static_assert(T_TOT % 16 == 0, "reduce kernel: 16 entries per workgroup");
