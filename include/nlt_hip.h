@@ -973,6 +973,18 @@ int nlt_conv_tile3r_forward(int mode, int nprod, const float* src, int ld, int c
                             const unsigned short* packed, const float* bias, int cout, int tn,
                             float* out, int ldo, float* mean_out, int ldm, int act, float alpha, int max_workgroups, void* stream);
 /*
+ * The TEXELS-DIRECT form of nlt_conv_tile3_forward for the stride-2 conv (mode = NLT_CONV_K2S2, nprod = 6 / 9): a 2 x 2 stride-2
+ * conv on an even map has no halo and no tap overlap, so a lane's B operand of v_mfma_f32_16x16x32_bf16 is 32 contiguous bytes of
+ * `src`; it is loaded straight into registers two micro-stages ahead and split there, with no LDS texel stage.  The weights
+ * stream through the double-buffered LDS stage as in nlt_conv_tile3_forward (one barrier per 16-channel slab).  Same arguments,
+ * same `packed`, the same additions per output element in the same order: `out` is bit-identical to nlt_conv_tile3_forward's.
+ * NLT_ERR_UNSUPPORTED, nothing launched: any other mode, an odd h or w, nprod = 1 / 3, or a mean_out request (the stride-2
+ * launches have no observation mean): the caller takes nlt_conv_tile3_forward.
+ */
+int nlt_conv_tile3d_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                            const unsigned short* packed, const float* bias, int cout, int tn,
+                            float* out, int ldo, float* mean_out, int ldm, int act, float alpha, void* stream);
+/*
  * Two encoder convs of the observation path in ONE launch (nprod = 6 / 9): the wave-private stride-1 conv of
  * nlt_conv_tile3r_forward at cin = cout = 32 (4 x 16 tiles), and the NEXT level's stride-2 conv (32 -> cout2 = 64) on the wave's
  * own results.  The stride-1 stage keeps its four MFMA column tiles by tap class (ty, tx) of the stride-2 conv -- column (y', x')

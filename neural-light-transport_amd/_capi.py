@@ -140,6 +140,8 @@ SIGNATURES = {
                                         _vp, _c_int, _vp, _c_int, _c_int, _c_float, _vp]),
     'nlt_conv_tile3r_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int,
                                          _vp, _c_int, _vp, _c_int, _c_int, _c_float, _c_int, _vp]),
+    'nlt_conv_tile3d_forward': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_int, _c_int,
+                                         _vp, _c_int, _vp, _c_int, _c_int, _c_float, _vp]),
     'nlt_conv_tile3w_s2_packed_elems': (_c_long, [_c_int] * 2),
     'nlt_pack_conv_tile3w_s2_weights': (_c_int, [_vp, _c_int, _c_int, _vp, _vp]),
     'nlt_conv_tile3w_s2_lds_bytes': (_c_long, [_c_int] * 3),
@@ -1171,6 +1173,14 @@ def conv_tile3r_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, co
     """conv_tile3_forward by persistent workgroups with the group's split weights resident in LDS: the same bits."""
     _call('nlt_conv_tile3r_forward', mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
           _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha), max_workgroups)
+
+
+def conv_tile3d_forward(mode, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm,
+                        act=True, alpha=0.3, nprod=6):
+    """conv_tile3_forward's stride-2 conv with the texels loaded straight into MFMA operands (no LDS texel stage): the same bits.
+    mean_out must be None."""
+    _call('nlt_conv_tile3d_forward', mode, nprod, _ptr(src), ld, cin, frames, kobs, h, w, packed.data_ptr(), _ptr(bias), cout, tn,
+          _ptr(out), ldo, _ptr(mean_out), ldm, 1 if act else 0, float(alpha))
 
 
 def pack_conv_tile3w_s2_weights(w_keras, cin2, cout2):

@@ -21,13 +21,15 @@
 // Layout of this file: the STAGE PIECES, each defined once -- gather_unit (two 16-byte loads of a copy unit), split8 /
 // split_store_unit (the three terms, and their LDS stores), read_a (A fragments), ORDER9 + term_products (the MFMAs of a K block),
 // bias_act + epilogue (bias, LeakyReLU, out, observation mean), unit_slot / unit_source / stage_products (the shared 8 x 16 stage),
-// wave_sync -- and FOUR SCHEDULES around them, which differ only in who stages what, when, and between which barriers:
+// wave_sync -- and FIVE SCHEDULES around them, which differ only in who stages what, when, and between which barriers:
 //   conv_tile3_kernel      streaming: a tile per workgroup, weights and texels through the double-buffered stage;
+//   conv_tile3d_kernel     streaming, texels direct (stride 2): gather_b_s2 / terms_b_s2 in place of the texel stage;
 //   conv_tile3r_kernel     resident, shared stage: persistent workgroups, a group's weights stay in LDS;
 //   conv_tile3w_kernel     resident, wave-private: every wave stages its own RT x 16 tile, no workgroup barrier;
 //   conv_tile3w_s2_kernel  level hand-off: the wave-private schedule by tap class + the next level's stride-2 conv in registers.
-// Per output element all four issue the same floating-point operations in the same order because they call the same pieces:
-// slabs in order, tap pairs in order, ORDER9, bias, LeakyReLU, mean (tests/test_gpu_tile3_bits.py holds them to recorded bits).
+// Per output element all five issue the same floating-point operations in the same order because they call the same pieces:
+// slabs in order, tap pairs in order, ORDER9, bias, LeakyReLU, mean (tests/test_gpu_tile3_bits.py holds them to recorded bits,
+// tests/test_gpu_tile3_s2direct.py the texels-direct schedule to the streaming kernel's).
 #include "nlt_common.h"
 #include "pack_common.h"
 
@@ -380,6 +382,155 @@ __global__ __launch_bounds__(256, 2) void conv_tile3_kernel(Tile3P p) {
       }
     }
   }
+}
+
+// B fragments of the stride-2 conv WITHOUT a texel stage: a 2 x 2 stride-2 conv on an even map has no halo and no tap overlap, so
+// lane (kk, j)'s operand of output texel (y, x = x0 + j) in slab (cc, a) is channels 16 cc + 8 (kk & 1) ... + 8 of input texel
+// (2y + a, 2x + (kk >> 1)): 32 contiguous bytes of global memory.  gather_b_s2 is the two 16-byte loads at `q8` (the caller's
+// clamped address: always readable, so the loads are unconditional and can be issued slabs ahead of their use); terms_b_s2 runs
+// when the values are needed: zeros where the output texel lies outside the map, split8 in registers, and the three terms ARE the
+// B fragments term_products takes.
+__device__ __forceinline__ void gather_b_s2(const float* q8, f32x4& v0, f32x4& v1) {
+  v0 = *reinterpret_cast<const f32x4*>(q8);
+  v1 = *reinterpret_cast<const f32x4*>(q8 + 4);
+}
+__device__ __forceinline__ void terms_b_s2(bool ok, const f32x4& v0, const f32x4& v1, bf16x8& hi, bf16x8& mid, bf16x8& lo) {
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  u32x4 t[3];
+  split8(ok ? v0 : z, ok ? v1 : z, t[0], t[1], t[2]);
+  hi = __builtin_bit_cast(bf16x8, t[0]);
+  mid = __builtin_bit_cast(bf16x8, t[1]);
+  lo = __builtin_bit_cast(bf16x8, t[2]);
+}
+
+// TEXELS DIRECT, streaming (stride 2 only): conv_tile3_kernel<NLT_CONV_K2S2> with gather_b_s2 in place of load_b / store_b / the B
+// planes.  The weights still go through the double-buffered A stage, with ONE barrier per slab (not per micro-stage: nothing else
+// is shared); LDS is the two A buffers (24.6 KB at TN = 64).  Every wave takes RT = 2 rows of the 8 x 16 tile and ALL of the group's
+// TNT column tiles, so no two waves of a workgroup load the same texel.  A wave's texel loads sit in a register ring of two
+// micro-stages: a slot is split into its terms, then refilled at once with the loads of micro-stage q + 2, so the loads of q + 1
+// and q + 2 are in flight under the MFMAs of q, on the wave's own count and whatever the barrier does.  The slab's weight
+// loads are issued BEFORE that refill: memory returns in order, and the wait before the LDS store of the weights then covers the
+// loads issued earlier, not the ring's newest.  All loads are unconditional: past the last micro-stage the cursor stays on the
+// last (group, slab) and the values are dropped.  Slabs s = 2 cc + a: the parity of s is the tap row a (and the A buffer), so the
+// body unrolls over (a, io) and every ring slot and accumulator set has a static index.  Per output element: slabs in order,
+// ORDER9, bias, LeakyReLU -- conv_tile3_kernel's bits.  No observation mean (the stride-2 launches have none).
+// Launch bound = the workgroups per CU the registers allow without scratch (found by compiling): 3 (110-166 VGPRs), 2 where
+// TNT x KO accumulator sets reach 8 (180-200 VGPRs).
+template <int TNT, int NPROD, int KO>
+__global__ __launch_bounds__(256, TNT * KO >= 8 ? 2 : 3) void conv_tile3d_kernel(Tile3P p) {
+  constexpr int WM = 4, RT = TH / WM, CT = TNT;
+  constexpr int A_SLOTS = TNT * 3 * 64;                                 // 16-byte slots of one slab's weights
+  constexpr int NA = (A_SLOTS + 255) / 256;                             // (TN = 32: 384 slots -> the last pass is half full)
+  constexpr int NM = 2 * KO;                                            // micro-stages of the unrolled body: (a, io)
+  __shared__ u32x4 lds[2 * A_SLOTS];                                    // [A of tap row 0 | 1]
+  p.mean_out = nullptr;                                                 // (known here: the shared epilogue's mean folds away)
+
+  const int tid = threadIdx.x, lane = tid & 63, wm = tid >> 6;
+  const int kk = lane >> 4, j = lane & 15;
+  int tile = xcd_tile3(blockIdx.x, gridDim.x);
+  const int tx0 = (tile % p.tiles_x) * TW; tile /= p.tiles_x;
+  const int ty0 = (tile % p.tiles_y) * TH;
+  const int f = tile / p.tiles_y;
+  const int g = blockIdx.y;
+  const int groups = p.kobs / KO;
+  const int nouter = groups * p.ncc;                                    // (observation group gi, channel slab cc), gi outermost
+  const long in_frame = (long)p.h * p.w;
+
+  // the lane's texel of tap row 0 per output row, as an element offset from the slab's base (tile3_params bounds the whole map
+  // below 2^31 elements); outside the map: texel (0, 0) of the frame
+  int b_off[RT]; bool b_ok[RT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    const int y = ty0 + wm * RT + rt, x = tx0 + j;
+    b_ok[rt] = y < p.oh && x < p.ow;
+    b_off[rt] = (b_ok[rt] ? (2 * y * p.w + 2 * x + (kk >> 1)) * p.ld : 0) + 8 * (kk & 1);
+  }
+
+  u32x4 ra[NA];
+  f32x4 rb[2][RT][2];                                                   // the ring: micro-stage parity
+  auto load_a = [&](int cc, int a) {
+    const u32x4* ap = reinterpret_cast<const u32x4*>(p.packed) + (((long)g * p.ncc + cc) * 2 + a) * A_SLOTS;
+#pragma unroll
+    for (int n = 0; n < NA; ++n) ra[n] = ap[(A_SLOTS % 256 == 0 || tid + 256 * n < A_SLOTS) ? tid + 256 * n : tid];
+  };
+  auto store_a = [&](int buf) {
+    u32x4* base = lds + buf * A_SLOTS;
+#pragma unroll
+    for (int n = 0; n < NA; ++n)
+      if (A_SLOTS % 256 == 0 || tid + 256 * n < A_SLOTS) base[tid + 256 * n] = ra[n];
+  };
+  auto load_b = [&](int u, int gi, int cc, int a, int io) {
+    const float* sp = p.src + ((long)(f * p.kobs + gi * KO + io) * in_frame + (long)a * p.w) * p.ld + cc * 16;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) gather_b_s2(sp + b_off[rt], rb[u][rt][0], rb[u][rt][1]);
+  };
+
+  f32x4 acc[KO][RT][CT], mean[RT][CT];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      mean[rt][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int io = 0; io < KO; ++io) acc[io][rt][ct] = mean[rt][ct];
+    }
+
+  // peeled start: slab 0's weights, then the ring's two slots (micro-stages 0 and 1 of the first body)
+  load_a(0, 0);
+  load_b(0, 0, 0, 0, 0);
+  load_b(1, 0, 0, 1 / KO, 1 % KO);
+  store_a(0);
+  __syncthreads();
+  int gi = 0, cc = 0;
+  for (int o = 0; o < nouter; ++o) {
+    int ngi = gi, nc = cc + 1;                                          // the next (gi, cc); after the last one: itself again
+    if (nc == p.ncc) { nc = 0; ++ngi; }
+    if (o + 1 == nouter) { ngi = gi; nc = cc; }
+#pragma unroll
+    for (int m = 0; m < NM; ++m) {
+      const int a = m / KO, io = m % KO, u = m & 1;
+      bf16x8 bt[3][RT], at[3][CT];
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) terms_b_s2(b_ok[rt], rb[u][rt][0], rb[u][rt][1], bt[0][rt], bt[1][rt], bt[2][rt]);
+      if (io == 0) {                                                    // the next slab's weights: tap row 1 of cc, else row 0 of the next
+        if (a == 0) load_a(cc, 1);
+        else load_a(nc, 0);
+      }
+      if (m + 2 < NM) load_b(u, gi, cc, (m + 2) / KO, (m + 2) % KO);    // micro-stage q + 2 into the slot just emptied
+      else load_b(u, ngi, nc, (m + 2 - NM) / KO, (m + 2 - NM) % KO);
+      // (the loads stay ABOVE the MFMAs: left alone, the scheduler sinks them to their uses to save registers, and the weight
+      // store then waits out a whole memory latency behind the MFMAs instead of under them)
+      __builtin_amdgcn_sched_barrier(0);
+      read_a(lds + a * A_SLOTS, 0, lane, at);
+      term_products<NPROD>(at, [&](int t, int rt) { return bt[t][rt]; }, acc[io]);
+      if (m == NM - 1 && cc == p.ncc - 1) {                             // the group's KO observation frames are complete
+#pragma unroll
+        for (int e = 0; e < KO; ++e) epilogue<false>(p, f, gi * KO + e, g * TNT * 16 + 4 * kk, ty0 + wm * RT, tx0 + j, acc[e], mean);
+      }
+      if (io == KO - 1) {
+        store_a(a ^ 1);
+        __syncthreads();
+      }
+    }
+    gi = ngi; cc = nc;
+  }
+}
+
+template <int TNT, int KO>
+int launch3d_k(const Tile3P& p, int nprod, hipStream_t s) {
+  const dim3 grid((unsigned)((long)p.frames * p.tiles_y * p.tiles_x), (unsigned)(p.cout / (16 * TNT)));
+  if (nprod == 9) hipLaunchKernelGGL((conv_tile3d_kernel<TNT, 9, KO>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((conv_tile3d_kernel<TNT, 6, KO>), grid, dim3(256), 0, s, p);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+// KO as the streaming kernel takes it: 4 at 32 channels per workgroup, 2 at 64, where kobs divides
+template <int TNT>
+int launch3d(const Tile3P& p, int nprod, hipStream_t s) {
+  if (TNT == 2 && p.kobs % 4 == 0) return launch3d_k<TNT, (TNT == 2 ? 4 : 1)>(p, nprod, s);
+  if (p.kobs % 2 == 0) return launch3d_k<TNT, 2>(p, nprod, s);
+  return launch3d_k<TNT, 1>(p, nprod, s);
 }
 
 // RESIDENT form (stride 2, and 64 channels per group; the stride-1 conv at 32 channels per group: conv_tile3w_kernel below):
@@ -997,6 +1148,20 @@ extern "C" int nlt_conv_tile3r_forward(int mode, int nprod, const float* src, in
   if (max_workgroups < 0) return NLT_ERR_BAD_ARG;
   return tile3_forward(mode, nprod, src, ld, cin, frames, kobs, h, w, packed, bias, cout, tn, out, ldo, mean_out, ldm, act, alpha,
                        max_workgroups, stream);
+}
+
+extern "C" int nlt_conv_tile3d_forward(int mode, int nprod, const float* src, int ld, int cin, int frames, int kobs, int h, int w,
+                                       const unsigned short* packed, const float* bias, int cout, int tn,
+                                       float* out, int ldo, float* mean_out, int ldm, int act, float alpha, void* stream) {
+  // (stride 2 on an even map only: that is what makes a lane's operand 32 contiguous bytes; the stride-2 launches have no mean)
+  const bool supported = mode == NLT_CONV_K2S2 && nlt_conv_tile3_packed_elems(mode, cin, cout, tn) > 0 && !((h | w) & 1) &&
+                         (nprod == 6 || nprod == 9) && !mean_out;
+  Tile3P p;
+  const int st = tile3_params(p, out != nullptr, supported, true, ldo, true, src, ld, cin, frames, kobs, h, w, packed, bias, cout,
+                              out, ldo, mean_out, ldm, act, alpha);
+  if (st != NLT_OK) return st;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return tn == 64 ? launch3d<4>(p, nprod, s) : launch3d<2>(p, nprod, s);
 }
 
 extern "C" long nlt_conv_tile3w_s2_packed_elems(int cin2, int cout2) {

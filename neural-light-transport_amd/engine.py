@@ -74,11 +74,13 @@ def hint_word(hint):
     +256: the observations run as separate frames and their mean in a launch of its own; +512: csrc/conv_tile3.hip's resident
     form, its split weights kept in LDS (lds only); +1024 (`FOLD_S2`, with +512, inference plans only): the stride-1 observation
     conv also runs the NEXT level's stride-2 observation conv on its own results (conv_tile3w_s2_kernel), which is then not
-    launched and whose input map is never stored."""
+    launched and whose input map is never stored; +2048 (`DIRECT_S2`, stride-2 launches of the split precisions only): the texels
+    go straight from global memory into the MFMA operands (conv_tile3d_kernel: no LDS texel stage)."""
     return hint & 255, bool(hint & 256), bool(hint & 512)
 
 
 FOLD_S2 = 1024
+DIRECT_S2 = 2048
 FOLD_HINT = FOLD_S2 + 512 + 32          # the one hint the level hand-off kernel runs under
 
 
@@ -404,10 +406,15 @@ class RenderPlan(OverrideMixin):
         if ok and unfold and kobs == 1:
             ok = not trial                              # nothing to unfold here: a trial leaves this launch to the other trials
             unfold = False
+        direct = bool(hint & DIRECT_S2)
+        if ok and direct and not (self.precision in ('f32x3', 'f32x3_9') and layer.mode == C.CONV_K2S2 and ((h | w) & 1) == 0
+                                  and (mean_out is None or unfold)):
+            ok = not trial                              # texels direct: stride-2 convs of the split precisions, no folded mean;
+            direct = False                              # a trial leaves the rest to the others, a plan takes the streaming kernel
         if ok and self.precision in ('f32x3', 'f32x3_9'):
             # fp32 operands as three bf16 terms on the bf16 matrix cores (csrc/conv_tile3.hip): 6 or all 9 term products
-            self._enc_launch(C.conv_tile3r_forward if resident else C.conv_tile3_forward, layer.packed_tile3(tn), (tn,),
-                             'lds', unfold, *conv, nprod=9 if self.precision == 'f32x3_9' else 6)
+            fn = C.conv_tile3d_forward if direct else (C.conv_tile3r_forward if resident else C.conv_tile3_forward)
+            self._enc_launch(fn, layer.packed_tile3(tn), (tn,), 'lds', unfold, *conv, nprod=9 if self.precision == 'f32x3_9' else 6)
         elif ok:
             self._enc_launch(C.conv_tile_forward, layer.packed_tile(tn), (tn,), 'lds', unfold, *conv)
         else:
@@ -441,6 +448,8 @@ class RenderPlan(OverrideMixin):
             trials += [('lds', 32), ('lds', 64), ('lds', 256 + 32), ('lds', 256 + 64)]
             if self.precision in ('f32x3', 'f32x3_9'):
                 trials += [('lds', 512 + 32), ('lds', 512 + 64)]    # the three-term split with its weights resident in LDS
+                if self._direct_trial():                            # ... and its stride-2 convs with the texels direct
+                    trials += [('lds', DIRECT_S2 + u + tn) for u in (0, 256) for tn in (32, 64)]
                 if self.fold_s2 and self._fold_trial():
                     trials.append(('lds', FOLD_HINT))               # ... and the next level's stride-2 conv on the same launch
         elif self.tile_dgrad:
@@ -501,6 +510,11 @@ class RenderPlan(OverrideMixin):
 
     def _fold_trial(self):
         """Is the level hand-off kernel a candidate of this plan's trials at all?  (Its launches exist on the GPU only.)"""
+        k = getattr(self.q.layers[0], 'kernel', None)
+        return k is not None and k.is_cuda
+
+    def _direct_trial(self):
+        """... and the texels-direct form of the stride-2 convs?  (The same: a kernel of the GPU only.)"""
         k = getattr(self.q.layers[0], 'kernel', None)
         return k is not None and k.is_cuda
 
