@@ -514,6 +514,26 @@ def _dense(t, what):
     return t
 
 
+def dense_obs_weights(obs_weights, n, k, device):
+    """The `obs_weights` argument of Model.call / _call / RenderPlan.forward / backward / generic.forward as the kernels read it:
+    a dense float32 [n, k] array on `device`, element (frame, observation) at f * k + i.  The reference takes whatever
+    `tf.reshape(obs_weights, (N, 1, 1, 1, -1))` takes and broadcasts against the [N, H, W, C, k] stack (nlt.py:143-145,162-163):
+    shape[0] == N and N * k elements.  None passes through; a strided view (a slice of a wider tensor, a transposed storage) is
+    copied dense; anything else raises ValueError before any launch -- the kernels would read it at the wrong places or past
+    its end."""
+    if obs_weights is None:
+        return None
+    t = obs_weights
+    ok = (torch.is_tensor(t) and t.dtype == torch.float32 and t.device == torch.device(device) and t.dim() >= 1
+          and t.shape[0] == n and t.numel() == n * k)
+    if not ok:
+        got = ("a %s of shape %s, dtype %s on %s" % (type(t).__name__, tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t)
+               else "a %s" % type(t).__name__)
+        raise ValueError("obs_weights must be a float32 tensor on %s with shape[0] == %d frames and %d x %d elements "
+                         "(one factor per frame and observation), got %s" % (torch.device(device), n, n, k, got))
+    return t.detach().reshape(n, k).contiguous()
+
+
 def _call(name, *args):
     """Launches entry point `name` with `args` + the current stream; a non-zero status raises NLTError under that name.  (Looked up
     on `lib()`, so an open tape records the call.)"""

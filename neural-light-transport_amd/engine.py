@@ -625,6 +625,7 @@ class RenderPlan(OverrideMixin):
         n, h, w, _ = base.shape
         k = nn_rgb.shape[1]
         dev = base.device
+        obs_weights = C.dense_obs_weights(obs_weights, n, k, dev)      # (dense [n, k] or ValueError, before any launch)
         # the reference's inference mode (one given map per level for every frame): the fused query-only plan, no observation buffers
         use_ovr = (obs_override is not None and inference and obs_weights is None
                    and self.can_fuse_override(self._level_channels(), obs_override, h, w, (base, cvis, lvis)))
@@ -1143,6 +1144,7 @@ class RenderPlan(OverrideMixin):
                                % (generation, self.generation))
         n, h, w, _ = base.shape
         k = nn_rgb.shape[1]
+        obs_weights = C.dense_obs_weights(obs_weights, n, k, base.device)
         b = self._buffers(n, k, h, w, base.device)
         g = self._grad_buffers(b)
         reg = self._begin_pass(bump=False, refresh=False)      # (this pass has always ticked the registry and never refreshed it)

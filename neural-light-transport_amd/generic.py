@@ -154,6 +154,7 @@ def run_layer(tape, layer, x):
 def forward(model, query_x, obs_xs, obs_weights=None, obs_override=None, record=False):
     """Model._call (nlt.py:141-199).  Returns (output Node, Tape)."""
     q, o = model.net['query'], model.net['obs']
+    obs_weights = C.dense_obs_weights(obs_weights, query_x.shape[0], len(obs_xs), query_x.device)
     tape = Tape(record)
     qx = tape.leaf(query_x)
     ox = [tape.leaf(x) for x in obs_xs]

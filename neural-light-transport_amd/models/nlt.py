@@ -401,15 +401,15 @@ class Model(BaseModel):
             C.warp_backward(d_pred_c, warp, n, self.uvh, self.uvw, hc, wc, dpred)
             self.plan.backward(dpred, base, cvis, lvis, nn_rgb, nn_base, obs_weights, generation=generation)
 
-    def train_forward_backward(self, batch, global_bs):
+    def train_forward_backward(self, batch, global_bs, obs_weights=None):
         """One train step's forward + loss + backward WITHOUT the torch.autograd tape around the network (only the loss
         is differentiated, with autograd.grad -- no AccumulateGrad node, so the whole thing can be captured in a
         hipGraph): returns (loss summed over this rank's examples / global_bs, to_vis) and leaves the gradients in
-        `flat_grads`.  Same arithmetic as `call(batch, 'train')` + `compute_loss` + `.backward()`."""
+        `flat_grads`.  Same arithmetic as `call(batch, 'train', obs_weights=...)` + `compute_loss` + `.backward()`."""
         with C.deterministic_scope(self.deterministic):
-            return self._train_forward_backward(batch, global_bs)
+            return self._train_forward_backward(batch, global_bs, obs_weights)
 
-    def _train_forward_backward(self, batch, global_bs):
+    def _train_forward_backward(self, batch, global_bs, obs_weights=None):
         id_, base, cvis, lvis, warp, rgb, rgb_camspc, nn_id, nn_base, nn_rgb, nn_rgb_camspc = batch
         if isinstance(base, ResidentTexels):                     # load_batch(resident=True): training reads the float buffers
             m = base.materialize()
@@ -418,8 +418,9 @@ class Model(BaseModel):
         if nn_rgb.dim() == 4:
             nn_rgb, nn_base = nn_rgb.unsqueeze(1), nn_base.unsqueeze(1)
         nn_rgb, nn_base = nn_rgb.contiguous(), nn_base.contiguous()
+        obs_weights = C.dense_obs_weights(obs_weights, base.shape[0], nn_rgb.shape[1], base.device)
         with torch.no_grad():
-            pred, pred_camspc, base_camspc, fg_camspc, _ = self._render(base, cvis, lvis, warp, nn_rgb, nn_base, None, None,
+            pred, pred_camspc, base_camspc, fg_camspc, _ = self._render(base, cvis, lvis, warp, nn_rgb, nn_base, obs_weights, None,
                                                                         False, inference=False)
             # (the fused train forward wrote `pred` into a tensor of this call: no 50 MB copy of the plan's buffer at the step's end)
             pred_vis = pred if self._pred_fresh else pred.clone()
@@ -449,7 +450,7 @@ class Model(BaseModel):
                 loss = self.compute_loss(leaf, gt_camspc, keep_batch=True).sum() / global_bs
                 (d_pred_c,) = torch.autograd.grad(loss, leaf)
         with torch.no_grad():
-            self._render_backward(d_pred_c, (base, cvis, lvis, warp, nn_rgb, nn_base, None), gen)
+            self._render_backward(d_pred_c, (base, cvis, lvis, warp, nn_rgb, nn_base, obs_weights), gen)
             to_vis = {'id': id_, 'nn_id': nn_id, 'base_camspc': base_camspc, 'pred': pred_vis, 'pred_camspc': pred_camspc,
                       'nn_camspc': nn_rgb_camspc, 'gt': rgb, 'gt_camspc': gt_camspc}
         return loss.detach(), to_vis
@@ -491,6 +492,13 @@ class Model(BaseModel):
     def call(self, batch, mode, obs_override=None, obs_weights=None, want_indices=False):
         self._validate_mode(mode)
         id_, base, cvis, lvis, warp, rgb, rgb_camspc, nn_id, nn_base, nn_rgb, nn_rgb_camspc = batch
+        if obs_weights is not None:
+            # checked and made dense [N, k] before anything is launched; the forward and the backward of a step (`_RenderFn`
+            # keeps this tensor, not the caller's view) read the same array
+            if isinstance(base, ResidentTexels):
+                obs_weights = C.dense_obs_weights(obs_weights, base.n, base.k, base.cvis.device)
+            else:
+                obs_weights = C.dense_obs_weights(obs_weights, base.shape[0], 1 if nn_rgb.dim() == 4 else nn_rgb.shape[1], base.device)
         differentiable = (mode == 'train' and torch.is_grad_enabled() and obs_override is None
                           and getattr(self, 'flat_params', None) is not None)
         resident = None
@@ -551,6 +559,7 @@ class Model(BaseModel):
         """Layer-by-layer form with the reference's exact structure (materialised concats),
         built on the generic layer objects; `call` uses the fused RenderPlan instead."""
         q, o = self.net['query'], self.net['obs']
+        obs_weights = C.dense_obs_weights(obs_weights, query_x.shape[0], len(obs_xs), query_x.device)
         stack, query_y = [], None
         for i, (layer_q, is_c) in enumerate(zip(q.layers, q.is_contracting)):
             if is_c:

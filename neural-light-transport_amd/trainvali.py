@@ -92,8 +92,10 @@ def _world(group):
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
 
 
-def distributed_train_step(model, batch, optimizer, global_bs, group=None, overlap=True):
+def distributed_train_step(model, batch, optimizer, global_bs, group=None, overlap=True, obs_weights=None):
     """batch = this rank's shard of the global batch.  Returns (loss summed over ranks, to_vis).
+    obs_weights [N, k] (this rank's frames): `Model.call`'s per-frame, per-observation factors of the aggregate (nlt.py:162-163);
+    such a step runs the layer-by-layer plan, forward and backward.
 
     One rank: per-example loss -> sum / global batch -> autograd backward -> fused Adam.
     Several ranks: the gradient sum is THREE all-reduces of fixed contiguous ranges of the flat bucket, cut in the order
@@ -107,12 +109,12 @@ def distributed_train_step(model, batch, optimizer, global_bs, group=None, overl
     if world == 1 and not AUTOGRAD_STEP and not getattr(model, 'generic', False):     # (branch configs run layer by layer through autograd)
         # same arithmetic without a torch.autograd graph around the network (only the loss is differentiated): no AccumulateGrad
         # copy of the 13.5 MB bucket, no expand / fill launches for the sum and the division
-        loss, to_vis = model.train_forward_backward(batch, global_bs)
+        loss, to_vis = model.train_forward_backward(batch, global_bs, obs_weights=obs_weights)
         model.flat_params.grad = model.flat_grads
         optimizer.step(model.flat_grads)
         return loss.clone(), to_vis
     if world == 1:
-        pred, gt, loss_kwargs, to_vis = model(batch, mode='train')
+        pred, gt, loss_kwargs, to_vis = model(batch, mode='train', obs_weights=obs_weights)
         loss_kwargs['keep_batch'] = True
         per_example_loss = model.compute_loss(pred, gt, **loss_kwargs)
         weighted_loss = per_example_loss.sum() / global_bs         # tf.nn.compute_average_loss
@@ -126,7 +128,7 @@ def distributed_train_step(model, batch, optimizer, global_bs, group=None, overl
         # through its hand-rolled tape (generic.py) into the same flat bucket, then ONE all-reduce of the whole bucket (no
         # backward plan to overlap with).  Batch norm needs no cross-replica statistics: the reference runs it in inference
         # mode (networks/elements.py ChannelNorm).
-        pred, gt, loss_kwargs, to_vis = model(batch, mode='train')
+        pred, gt, loss_kwargs, to_vis = model(batch, mode='train', obs_weights=obs_weights)
         loss_kwargs['keep_batch'] = True
         loss = model.compute_loss(pred, gt, **loss_kwargs).sum() / global_bs
         model.flat_params.grad = None
@@ -149,7 +151,7 @@ def distributed_train_step(model, batch, optimizer, global_bs, group=None, overl
     if overlap:
         model.plan.grad_hook = reduce_range
     try:
-        loss, to_vis = model.train_forward_backward(batch, global_bs)    # gradients land in the flat bucket (no autograd copy)
+        loss, to_vis = model.train_forward_backward(batch, global_bs, obs_weights=obs_weights)    # gradients land in the flat bucket (no autograd copy)
     finally:
         model.plan.grad_hook = None
     for i in range(len(r) - 1):                                         # whatever the backward did not send, in range order

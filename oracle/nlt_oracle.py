@@ -270,16 +270,19 @@ class OracleModel:
             masks = self.act_masks[(path[0], i) + tuple(path[1:])]
         return apply_layer(L, w, x, self.alpha, self.norm, self.pool, self.act, masks=masks)
 
-    def _call(self, query_x, obs_xs, obs_weights=None, obs_override=None, return_feats=False, layer_outputs=None):
-        """layer_outputs: a list that receives the query path's output of every layer (tests of intermediate maps)."""
+    def _call(self, query_x, obs_xs, obs_weights=None, obs_override=None, return_feats=False, layer_outputs=None, obs_outputs=None):
+        """layer_outputs: a list that receives the query path's output of every layer (tests of intermediate maps);
+        obs_outputs: a list that receives, per contracting layer, the list of the observations' own (unweighted) outputs."""
         feats = []
         if obs_weights is not None:
-            obs_weights = obs_weights.reshape(obs_weights.shape[0], 1, 1, 1, -1)
+            obs_weights = obs_weights.reshape(obs_weights.shape[0], 1, 1, 1, -1)   # :143-145
         stack = []
         query_y = None
         for i, (L, c) in enumerate(zip(self.layers, self.is_contracting)):
             if c:
                 obs_ys = [self._layer(i, L, self.wo[i], x, ('o', j)) for j, x in enumerate(obs_xs)]   # :154-155
+                if obs_outputs is not None:
+                    obs_outputs.append(obs_ys)
                 obs_agg = torch.stack(obs_ys, -1)                               # :161
                 if obs_weights is not None:
                     obs_agg = obs_weights * obs_agg                             # :162-163
@@ -308,10 +311,11 @@ class OracleModel:
         return (query_y, feats) if return_feats else query_y
 
     # -- nlt/models/nlt.py:89-139
-    def call(self, batch, mode='train', obs_override=None, nn_list=None):
+    def call(self, batch, mode='train', obs_override=None, nn_list=None, obs_weights=None):
         """batch = the reference 11-tuple (ids may be None).  `nn_list`, if given, is a
         list of (nn_base, nn_rgb) pairs and replaces the single neighbour of the
-        reference (k>1 observation maps; _call already takes a list, nlt.py:154-164)."""
+        reference (k>1 observation maps; _call already takes a list, nlt.py:154-164).  `obs_weights` is handed to `_call`
+        (the reference's `call` has no such parameter; its `_call` has, nlt.py:141)."""
         if mode not in ('train', 'vali', 'test'):
             raise ValueError(mode)
         _, base, cvis, lvis, warp, rgb, rgb_camspc, _, nn_base, nn_rgb, _ = batch
@@ -320,7 +324,7 @@ class OracleModel:
             y_obs = [nn_rgb - nn_base]                                          # :96
         else:
             y_obs = [r - b for b, r in nn_list]
-        pred = self._call(x, y_obs, obs_override=obs_override)
+        pred = self._call(x, y_obs, obs_weights=obs_weights, obs_override=obs_override)
         if self.skip_connect_base:
             pred = pred + base                                                  # :101-102
         warp_px = torch.stack((warp[..., 0] * self.uvw, warp[..., 1] * self.uvh), 3)  # :104-106
@@ -411,10 +415,10 @@ def clip_by_norm(t, clip):
     return (t * clip) / torch.maximum(norm, torch.as_tensor(clip, dtype=t.dtype))
 
 
-def train_step(model, opt, batch, global_bs, nn_list=None, clipnorm=None):
+def train_step(model, opt, batch, global_bs, nn_list=None, clipnorm=None, obs_weights=None):
     """nlt/trainvali.py:272-281 on one replica: per-example loss -> sum/global_bs ->
     grads (-> per-variable clipnorm when mgm > 0) -> Adam-AMSGrad.  Returns (weighted_loss, grads as applied)."""
-    pred, gt, kw, _ = model.call(batch, 'train', nn_list=nn_list)
+    pred, gt, kw, _ = model.call(batch, 'train', nn_list=nn_list, obs_weights=obs_weights)
     per_example = model.compute_loss(pred, gt, keep_batch=True)
     weighted = per_example.sum() / global_bs                 # tf.nn.compute_average_loss
     params = model.parameters()
@@ -453,3 +457,16 @@ def synth_batch(n, uvh, uvw, hc, wc, imh, imw, k=1, seed=0, identity_warp=False,
              tt(nn_list[0][0]), tt(nn_list[0][1]), tt(nn_rgb_c))
     nn_t = [(tt(b), tt(r)) for b, r in nn_list]
     return batch, nn_t
+
+
+# rows of factors that tell right from wrong: they differ per frame and per observation, and hold an exact 0 (an observation
+# switched off), negative values and values > 1 (a sign or a missing 1 / k shows)
+OBS_WEIGHT_ROWS = ((0., 2., -1., .5), (1.5, .25, 3., -.5), (-2., 1., .75, 0.))
+
+
+def synth_obs_weights(n, k):
+    """The `obs_weights` [n, k] of the weighted cases: the first n rows of OBS_WEIGHT_ROWS cut to k columns -- from column 2 for
+    k = 1, so that the single column still holds a negative factor and one > 1 (-1, 3, .75)."""
+    assert 1 <= n <= len(OBS_WEIGHT_ROWS) and 1 <= k <= len(OBS_WEIGHT_ROWS[0])
+    c0 = 2 if k == 1 else 0
+    return torch.tensor([row[c0:c0 + k] for row in OBS_WEIGHT_ROWS[:n]], dtype=torch.float32)

@@ -1,4 +1,4 @@
-"""Generates tests/golden/ref_orchestration.npz by IMPORTING AND RUNNING the reference's own model code:
+"""Generates tests/golden/ref_orchestration{,_2,_3}.npz by IMPORTING AND RUNNING the reference's own model code:
 
     /root/reference/nlt/models/{base,nlt}.py      Model.__init__, call, _call, compute_loss
     /root/reference/nlt/networks/{base,seq,convnet,elements}.py, util/{net,img,tensor}.py, losses.py:L2
@@ -12,6 +12,13 @@ source, executed -- not the TF kernels.
 Run here (needs /root/reference):   python tests/golden/make_ref_orchestration.py
 Consumers: tests/test_oracle_ref_orchestration.py (CPU: OracleModel == this file), tests/test_gpu_model.py (HIP <= 1e-4).
 Stored: float32 outputs (full at 64^2; strided samples + norms at depth 1024 / 256^2), the seeds that regenerate the inputs.
+
+The third file holds the `obs_weights` cases (WEIGHTED): the reference's `call` has no such parameter, so they run its
+`Model._call(x, y_obs, obs_weights=w)` (nlt/models/nlt.py:141-199) directly, on x = concat(base, cvis, lvis) and the k maps
+nn_rgb - nn_base of `O.synth_batch`, with w = `O.synth_obs_weights(n, k)`.
+
+A part whose arrays all equal the file already on disk is left untouched (the zip container carries the time of writing, so a
+rewrite would change bytes without changing content).
 """
 import os
 import sys
@@ -43,6 +50,14 @@ CASES = {
     'd64_train':      dict(depth=64, uv=32, im=32, cam=32, n=3, mode='train', wseed=107, bseed=207),
     'd1024_train':    dict(depth=1024, uv=256, im=32, cam=32, n=1, mode='train', wseed=108, bseed=208, sample=4),
     'd1024_override': dict(depth=1024, uv=256, im=32, cam=32, n=1, mode='test', wseed=109, bseed=209, sample=4, override=True),
+}
+
+
+# `Model._call(x, y_obs, obs_weights=w)`: n frames, k observations; use_obs = False: the weights must change nothing
+WEIGHTED = {
+    'w256_n3k2':   dict(depth=256, uv=64, im=32, n=3, k=2, wseed=110, bseed=210),
+    'w256_n2k3':   dict(depth=256, uv=64, im=32, n=2, k=3, wseed=111, bseed=211),
+    'w256_no_obs': dict(depth=256, uv=64, im=32, n=2, k=3, wseed=112, bseed=212, use_obs=False),
 }
 
 
@@ -137,11 +152,34 @@ def main():
             m.call((None,) * 11, mode)
         except ValueError:
             out['bad_mode_raises_ValueError/' + mode] = np.array(1)
-    # two files, each under the repository's 1 MiB limit for a file: these cases go to the second
+    third = {}
+    for name, c in WEIGHTED.items():
+        om, m = ref_model(c)
+        batch, nn = O.synth_batch(c['n'], c['uv'], c['uv'], 16, 16, c['im'], c['im'], k=c['k'], seed=c['bseed'])
+        x = tf.concat((T_(batch[1]), T_(batch[2]), T_(batch[3])), 3)                 # nlt.py:95
+        y_obs = [T_(r) - T_(b) for b, r in nn]                                       # nlt.py:96, one per observation
+        w = O.synth_obs_weights(c['n'], c['k'])
+        with torch.no_grad():
+            y = m._call(x, y_obs, obs_weights=T_(w))
+        third['%s/call_out' % name] = y.numpy().astype(np.float32)
+        third['%s/obs_weights' % name] = w.numpy()
+        third['%s/meta' % name] = np.array([c['depth'], c['uv'], c['im'], c['n'], c['k'], c['wseed'], c['bseed'],
+                                            int(c.get('use_obs', True))])
+        print(name, 'call_out norm %.6f' % np.linalg.norm(third['%s/call_out' % name].astype(np.float64)), flush=True)
+    # three files, each under the repository's 1 MiB limit for a file: these cases go to the second, the weighted ones to the third
     second = ('d256_override', 'd256_train', 'd256_vali', 'd64_train')
     for fname, part in (('ref_orchestration.npz', {k: v for k, v in out.items() if k.split('/')[0] not in second}),
-                        ('ref_orchestration_2.npz', {k: v for k, v in out.items() if k.split('/')[0] in second})):
+                        ('ref_orchestration_2.npz', {k: v for k, v in out.items() if k.split('/')[0] in second}),
+                        ('ref_orchestration_3.npz', third)):
         path = os.path.join(HERE, fname)
+        if os.path.exists(path):
+            with np.load(path) as z:
+                same = sorted(z.files) == sorted(part) and all(
+                    z[k].dtype == np.asarray(v).dtype and z[k].shape == np.asarray(v).shape and np.array_equal(z[k], v)
+                    for k, v in part.items())
+            if same:
+                print("kept  %s (%d arrays, every one equal to what was generated)" % (path, len(part)))
+                continue
         np.savez_compressed(path, **part)
         print("wrote %s (%.1f KB, %d arrays)" % (path, os.path.getsize(path) / 1024, len(part)))
 

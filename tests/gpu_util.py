@@ -88,10 +88,10 @@ def _set_alpha(om, pm, alpha):
 
 
 def _oracle_grads(loss, uv, cam, n, dtype, batch, nn, alpha=None, masks=None, depth=256, seed=41, uvh=None, uvw=None, imh=None,
-                  imw=None, **model_kw):
+                  imw=None, obs_weights=None, **model_kw):
     """(loss, every kernel / bias gradient) of one train step of a fresh OracleModel(depth, seed) in `dtype`; masks: the
     activation branches to take (OracleModel.act_masks, e.g. `hip_activation_masks`).  uv / cam: the square shorthand for
-    uvh x uvw / imh x imw; model_kw: further OracleModel keywords (kernel = 3, pool, ...)."""
+    uvh x uvw / imh x imw; obs_weights: `OracleModel.call`'s; model_kw: further OracleModel keywords (kernel = 3, pool, ...)."""
     om = O.OracleModel(depth=depth, uvh=uvh or uv, uvw=uvw or uv, imh=imh or cam, imw=imw or cam, loss=loss, seed=seed, dtype=dtype,
                        **model_kw)
     if alpha is not None:
@@ -99,7 +99,7 @@ def _oracle_grads(loss, uv, cam, n, dtype, batch, nn, alpha=None, masks=None, de
     om.act_masks = masks
     b = tuple(t.to(dtype) if torch.is_tensor(t) else t for t in batch)
     nnl = [(a.to(dtype), c.to(dtype)) for a, c in nn]
-    po, go, _, _ = om.call(b, 'train', nn_list=nnl)
+    po, go, _, _ = om.call(b, 'train', nn_list=nnl, obs_weights=None if obs_weights is None else obs_weights.to(dtype))
     lo = om.compute_loss(po, go, keep_batch=True).sum() / n
     grads = [g.double() for g in torch.autograd.grad(lo, om.parameters())]
     return float(lo.detach()), grads

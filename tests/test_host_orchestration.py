@@ -92,6 +92,48 @@ def test_layerwise_call_and_override_and_flags(monkeypatch):
     assert rel_l2(pred_w, ref_w) < 1e-5
 
 
+def test_obs_weights_with_more_frames_than_observations_and_the_argument_check(monkeypatch):
+    """n = 3 frames, k = 2 observations, weights with a 0, negative values and values > 1 (O.synth_obs_weights): Model.call,
+    Model._call and RenderPlan.forward against the oracle; a strided view of a wider tensor and the reference's other shapes of
+    the same 6 numbers give the bits of the dense matrix; what `tf.reshape(w, (N, 1, 1, 1, -1))` would not take -- or the kernels
+    would misread -- raises ValueError before any adapter is called."""
+    fake_capi.install(monkeypatch)
+    from nlt_amd import capi as C
+    n, k = 3, 2
+    om, pm = make(256, 64, 32)
+    batch, nn = O.synth_batch(n, 64, 64, 16, 16, 32, 32, k=k, seed=5)
+    w = O.synth_obs_weights(n, k)
+    x, y_obs = torch.cat((batch[1], batch[2], batch[3]), 3), [r - b for b, r in nn]
+    with torch.no_grad():
+        ref_c, _, _, ref_vis = om.call(batch, 'vali', nn_list=nn, obs_weights=w)
+        plain = om.call(batch, 'vali', nn_list=nn)[3]['pred']
+        ref_y = om._call(x, y_obs, obs_weights=w)
+    assert rel_l2(plain, ref_vis['pred']) > 0.1                          # the weights matter
+    cb = cpu_batch(batch, nn)
+    got_c, _, _, vis = pm.call(cb, 'vali', obs_weights=w)
+    assert rel_l2(vis['pred'], ref_vis['pred']) < 1e-5 and rel_l2(got_c, ref_c) < 1e-5
+    assert rel_l2(pm._call(x, y_obs, obs_weights=w), ref_y) < 1e-5
+    wide = O.synth_obs_weights(n, 4)
+    for view in (wide[:, :k], w.reshape(n, 1, 1, 1, k), w.t().contiguous().t()):
+        assert torch.equal(pm.call(cb, 'vali', obs_weights=view)[3]['pred'], vis['pred'])
+        assert torch.equal(pm.plan.forward(cb[1], cb[2], cb[3], cb[9], cb[8], obs_weights=view)[0], pm.plan.forward(
+            cb[1], cb[2], cb[3], cb[9], cb[8], obs_weights=w)[0].clone())
+    called = []
+    for name in ('stem_forward', 'obs_mean_forward', 'conv_forward', 'warp_forward'):
+        monkeypatch.setattr(C, name, (lambda nm: lambda *a, **kw: called.append(nm))(name))
+    gen = pm.plan.generation
+    for bad in (w.double(), w.to(torch.int32), w[0], O.synth_obs_weights(n, k + 1), torch.zeros(n * k + 1), w.t(), w.tolist()):
+        with pytest.raises(ValueError, match='obs_weights'):
+            pm.call(cb, 'vali', obs_weights=bad)
+        with pytest.raises(ValueError, match='obs_weights'):
+            pm._call(x, y_obs, obs_weights=bad)
+        with pytest.raises(ValueError, match='obs_weights'):
+            pm.plan.forward(cb[1], cb[2], cb[3], cb[9], cb[8], obs_weights=bad)
+        with pytest.raises(ValueError, match='obs_weights'):
+            pm.plan.backward(torch.zeros_like(cb[1]), cb[1], cb[2], cb[3], cb[9], cb[8], obs_weights=bad)
+    assert not called and pm.plan.generation == gen
+
+
 def test_no_obs_no_skip(monkeypatch):
     fake_capi.install(monkeypatch)
     om, pm = make(256, 64, 64, use_obs=False, skip_connect_base=False)

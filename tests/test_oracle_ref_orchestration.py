@@ -5,7 +5,7 @@ test-side TensorFlow shim (tests/tf_shim/: each TF primitive delegates to oracle
 
 This is what makes `oracle/nlt_oracle.py:OracleModel` (call / _call / compute_loss; modes; obs_override; use_obs = False;
 skip_connect_base = False; depth 64 / 256 / 1024 incl. the bottleneck self-concat) and the feature aggregation
-"orchestration: pinned (reference code executed)".  The TF kernels behind the primitives stay unpinned.
+"orchestration: pinned (reference code executed)" -- `_call`'s `obs_weights` included (the third part of the fixture).  The TF kernels behind the primitives stay unpinned.
 The fixture travels; /root/reference is not read here."""
 import os
 
@@ -23,6 +23,10 @@ for _part in ('ref_orchestration.npz', 'ref_orchestration_2.npz'):
     with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', _part)) as _z:
         G.update((k, _z[k]) for k in _z.files)
 CASES = sorted({k.split('/')[0] for k in G if k.startswith('d')})
+# the third part: the reference's `Model._call(x, y_obs, obs_weights=w)` (its `call` has no such parameter)
+with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_orchestration_3.npz')) as _z:
+    GW = {k: _z[k] for k in _z.files}
+WEIGHTED = sorted({k.split('/')[0] for k in GW})
 
 
 def rel(a, b):
@@ -92,6 +96,35 @@ def test_oracle_model_equals_the_reference_s_own_model_code(name):
             sc = om.compute_loss(pred_c, gt_c, keep_batch=False)
         assert np.allclose(per.numpy(), G[name + '/loss_per_example'], rtol=1e-5)
         assert np.allclose(float(sc), float(G[name + '/loss_scalar']), rtol=1e-5)
+
+
+@pytest.mark.parametrize('name', WEIGHTED)
+def test_oracle_call_with_obs_weights_equals_the_reference_s_own_model_code(name):
+    """nlt/models/nlt.py:143-145,162-164 executed: the reshape to (N, 1, 1, 1, -1), the product with the [N, H, W, C, k] stack,
+    the mean over k, and the unweighted per-observation features handed to the next level.  n != k, weights with an exact 0,
+    negative values and values > 1; the stored output is >= 1000 x the bar away from the unweighted one and from the ones under
+    the weights flipped along either axis, so none of those mistakes passes.  use_obs = False: the weights change nothing."""
+    import obs_weights_util as U
+    depth, uv, im, n, k, wseed, bseed, use_obs = (int(x) for x in GW[name + '/meta'])
+    w = O.synth_obs_weights(n, k)
+    U.check_weights(w, n, k)
+    assert np.array_equal(w.numpy(), GW[name + '/obs_weights'])
+    om = O.OracleModel(depth=depth, uvh=uv, uvw=uv, imh=im, imw=im, seed=wseed, use_obs=bool(use_obs))
+    batch, nn = O.synth_batch(n, uv, uv, 16, 16, im, im, k=k, seed=bseed)
+    x, y_obs = torch.cat((batch[1], batch[2], batch[3]), 3), [r - b for b, r in nn]
+
+    def run(wv):
+        with torch.no_grad():
+            return {'call_out': om._call(x, y_obs, obs_weights=wv).numpy()}
+    ref = GW[name + '/call_out']
+    assert ref.shape == (n, uv, uv, 3)
+    assert rel(run(w)['call_out'], ref) <= 1e-6
+    assert rel(run(w.reshape(n, 1, 1, 1, k))['call_out'], ref) <= 1e-6 and rel(run(w.reshape(-1, k)[:, :, None])['call_out'], ref) <= 1e-6
+    if use_obs:
+        _, dist = U.assert_sensitive(run, w, {'call_out': 1e-6}, name)
+        assert min(dist.values()) >= 0.1, dist               # (far more than 1000 x 1e-6: the margin of the GPU cases' 1e-4 bar)
+    else:
+        assert np.array_equal(run(w)['call_out'], run(None)['call_out'])
 
 
 def test_bad_modes_raise_like_the_reference():
