@@ -155,6 +155,7 @@ class RenderPlan(OverrideMixin):
         self.n_up = len(is_c) - sum(is_c) - 1            # expanding Sequential blocks
         assert self.n_down == self.n_up
         self._bufs = {}
+        self.buffer_serial = 0          # bumped whenever `_buffers` replaces the resident buffer set (see `replay_stamp`)
 
     def __del__(self):
         try:
@@ -193,7 +194,16 @@ class RenderPlan(OverrideMixin):
         b['pred'] = E(n, h, w, 3)
         b['skip3'] = None               # allocated by the fused inference path on first use
         self._bufs = {key: b}           # keep one shape resident
+        self.buffer_serial += 1         # (captured graphs over the previous set must not be replayed: it goes back to the allocator)
         return b
+
+    def replay_stamp(self, reg=None):
+        """What a captured hipGraph over this plan bakes in besides its inputs, as three integers: the resident buffer set
+        (`buffer_serial`), the cached scratch of `_capi._workspace` (its allocation epoch, shared by every plan of the process) and
+        the set of packed fragment buffers (`reg.version`; -1 without a registry).  A graph captured under one stamp may be
+        replayed only while the stamp still reads the same: anything else has handed memory the graph writes back to the
+        allocator.  Pure host arithmetic -- no launch, no synchronisation."""
+        return (self.buffer_serial, C._alloc_epoch[0], reg.version if reg is not None else -1)
 
     def _level_channels(self):
         q = self.q
@@ -226,9 +236,15 @@ class RenderPlan(OverrideMixin):
         return {label for label, k in self._ran if k == kind}
 
     def set_choice(self, label, kind, hint):
-        """Stores a choice unless one stands in its way: the first winner keeps a label; lds / wino / c32 exclude each other."""
+        """Stores a choice unless one stands in its way: the first winner keeps a label; lds / wino / c32 exclude each other.
+        A kind that takes the launch AWAY from the register-tiled kernel (direct, lds, wino, c32) is not stored for a label that
+        holds a choice of any kind already: a later round of trials (another kind of pass over the same labels) would otherwise
+        re-route, on the noise of its clock, a launch of a pass that was tuned, recorded or captured before -- and a re-recorded
+        tape or re-captured graph would round differently from the one it replaces."""
         own = [getattr(self, a) for a in CHOICE_DICTS[kind]]
         rivals = [getattr(self, CHOICE_DICTS[k][0]) for k in EXCLUSIVE] if kind in EXCLUSIVE else []
+        if kind in EXCLUSIVE or kind == 'direct':
+            rivals = [getattr(self, a) for a in HINT_DICTS]
         if any(label in d for d in own + rivals):
             return
         values = (C.ALGO_DIRECT,) if kind == 'direct' else hint if kind == 'splitk' else (hint,)

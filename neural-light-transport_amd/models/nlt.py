@@ -118,7 +118,7 @@ class Model(BaseModel):
         # hipGraph replay of the inference forward (opt-in: NLT_GRAPH=1 or model.use_graphs = True).  The ~36 launches
         # of a step cost ~0.6 ms of host time; for small workloads (512^2, k = 1) that is the whole step.
         self.use_graphs = os.environ.get('NLT_GRAPH', '0') == '1'
-        self._graph = None              # {'key', 'hits', 'graph', 'out'}: the entry of `_graphs` used last
+        self._graph = None              # {'key', 'hits', 'graph', 'out', 'stamp'}: the entry of `_graphs` used last
         self._graphs = {}               # input addresses (+ weights version ...) -> entry; a few staging slots' worth
         # `deterministic = true` (not a reference key) / NLT_DETERMINISTIC=1 / model.deterministic = True before the first step:
         # every sum of a train step in an order fixed by shapes and launch geometry -- the atomic-free siblings of the resampler
@@ -471,20 +471,28 @@ class Model(BaseModel):
         key = (tuple(t.data_ptr() for t in (base, cvis, lvis, warp, nn_rgb, nn_base)), tuple(base.shape), tuple(warp.shape),
                nn_rgb.shape[1], want_indices, self._epoch[0], self.flat_params._version, self.plan.fuse_ends, self.conv_algo)
         g = self._graphs.get(key)
-        if g is None:
-            if len(self._graphs) >= 8:                           # ever-changing input addresses: forget the oldest
+        # A graph also bakes in the plan's buffer set, the cached scratch and the packed fragment buffers: what
+        # `RenderPlan.replay_stamp` counts.  Another call at another shape, or another model growing the shared scratch, hands
+        # those back to the allocator; the entry then starts over -- eagerly where the buffer set is new (it is allocated, and
+        # its plan-time trials run, outside any capture), by a fresh capture where only scratch or fragments moved.
+        stamp = self.plan.replay_stamp(getattr(self, 'pack_registry', None))
+        if g is None or g['stamp'] is None or g['stamp'][0] != stamp[0]:     # (no stamp: its first sight raised)
+            if g is None and len(self._graphs) >= 8:             # ever-changing input addresses: forget the oldest
                 self._graphs.pop(next(iter(self._graphs)))
-            self._graph = self._graphs[key] = {'key': key, 'hits': 0, 'graph': None, 'out': None}
+            self._graph = g = self._graphs[key] = {'key': key, 'hits': 0, 'graph': None, 'out': None, 'stamp': None}
             out = eager()                                        # first sight: eager (also runs the plan-time autotune)
+            g['stamp'] = self.plan.replay_stamp(getattr(self, 'pack_registry', None))
             return out[:5] + (out[0] if getattr(self, '_pred_fresh', False) else out[0].clone(),)
         self._graph = g
-        if g['graph'] is None:                                   # second sight: capture (the capture itself does not execute)
+        if g['graph'] is None or g['stamp'] != stamp:            # second sight: capture (the capture itself does not execute)
+            g['graph'] = g['out'] = None
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 o = self._render(*args)
                 g['out'] = o + (o[0].clone(),)
             g['graph'] = graph
+            g['stamp'] = self.plan.replay_stamp(getattr(self, 'pack_registry', None))    # (scratch the capture itself grew included)
         g['graph'].replay()
         g['hits'] += 1
         return g['out']

@@ -172,9 +172,16 @@ class GraphedTrainStep:
     step) stay eager, after the replay.
 
     The graph is tied to tensor ADDRESSES: the batch is copied into static buffers owned by this object (a no-op when
-    the caller already passes them back), shapes must not change, and the returned loss / to_vis tensors are the
-    graph's static outputs -- consume them before the next call.  The first `warmup` calls run eagerly (plan-time
-    autotune, workspace allocation); any failure to capture falls back to the eager step for good."""
+    the caller already passes them back), the shapes of the batches given to THIS object must not change, and the returned
+    loss / to_vis tensors are the graph's static outputs -- consume them before the next call.  The first `warmup` calls
+    run eagerly (plan-time autotune, workspace allocation); any failure to capture falls back to the eager step for good.
+
+    Between two calls anything else may run: other calls on the model at any shape (a validation step on a short batch, a
+    test render), other models in the process.  Such calls can hand memory the graph baked in back to the allocator -- the
+    plan keeps one shape's buffers resident, cached scratch is replaced when a larger one is needed, a census retires packed
+    fragments -- and `RenderPlan.replay_stamp` (three integers, compared before every replay) says so: after scratch or
+    fragments moved the step is captured again at once; after the buffer set was replaced one step runs eagerly (the new set
+    is allocated, and tuned, outside any capture) and the next one captures."""
 
     TENSORS = (1, 2, 3, 4, 5, 6, 8, 9, 10)       # tensor entries of the 11-tuple batch (nlt/models/nlt.py:91-92)
 
@@ -182,7 +189,7 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.global_bs, self.group = model, optimizer, global_bs, group
         self.warmup, self.seen = warmup, 0
         self.graph, self.static, self.out, self.failed = None, None, None, None
-        self._table = self._reg_version = None       # the registry's descriptor table the graph embeds, and the buffer-set version it was captured at
+        self._table = self._stamp = None             # the registry's descriptor table the graph embeds, and `plan.replay_stamp` at the capture
 
     def static_batch(self):
         """The graph's own input tensors (None before the capture): a loader that fills THESE and passes them back
@@ -208,10 +215,18 @@ class GraphedTrainStep:
             self.seen += 1
             return distributed_train_step(self.model, batch, self.optimizer, self.global_bs, self.group)
         reg = getattr(self.model, 'pack_registry', None)
-        if self.graph is not None and reg is not None and reg.version != self._reg_version:
-            # the SET of packed buffers changed after the capture (a census retired some, a plan re-tuned: advisor r05): the
-            # captured repack launch would walk a descriptor table the registry no longer maintains -- capture again
+        stamp = self.model.plan.replay_stamp(reg)
+        if self._stamp is not None and stamp != self._stamp:
+            # Something the graph baked in was let go after the capture (`RenderPlan.replay_stamp`).  The SET of packed buffers
+            # changed (a census retired some, a plan re-tuned: advisor r05): the captured repack launch would walk a descriptor
+            # table the registry no longer maintains.  Cached scratch grew (another model, a larger shape): the graph points
+            # into the old one.  Either way: capture again.  The plan's buffer set was replaced (a call on the model at another
+            # shape): the graph's activations are back with the allocator -- this step runs eagerly, so that the new set is
+            # allocated (and its plan-time trials run) outside any capture, and the next call captures.
             self.graph = self.out = None
+            new_set, self._stamp = stamp[0] != self._stamp[0], None
+            if new_set:
+                return distributed_train_step(self.model, batch, self.optimizer, self.global_bs, self.group)
         if self.graph is None:
             try:
                 self.static = list(batch)
@@ -229,8 +244,8 @@ class GraphedTrainStep:
                 with torch.cuda.graph(graph):
                     self.out = self._body(tuple(self.static))
                 self.graph = graph
-                if reg is not None:
-                    self._table, self._reg_version = reg.table, reg.version   # (keeps the captured table's tensors alive)
+                self._table = reg.table if reg is not None else None      # (keeps the captured table's tensors alive)
+                self._stamp = self.model.plan.replay_stamp(reg)           # (after the capture: scratch it grew itself included)
             except Exception as e:                       # capture is an optimisation, never a requirement
                 self.failed = repr(e)
                 self.graph = None
