@@ -494,6 +494,50 @@ int nlt_remap_bilinear_f32(const float* src, int h, int w, int c, const void* ma
                            int ldm, int oh, int ow, int force_kbg, float* out, void* stream);
 
 /*
+ * The capture writer: every value data_gen/render.py and postproc.py put on disk for one sample, in two launches, and
+ * the diffuse bases of all frames in one.  Bit-exact against the separate entry points above (same device helpers).
+ *
+ * Camera space, one thread per pixel.
+ *   replaces: data_gen/render.py:155-171 -- uv2cam[alpha < 1] = 0, write_arr(uv2cam, clip=True), save_float16_npy(uv2cam),
+ *             calc_light_cosines / calc_view_cosines + np.clip + denormalize_float.
+ * locs, normals [imh*imw,3] float64; valid, occluded (NULL = no cast shadows) [imh*imw] uint8; (cx,cy,cz) the camera,
+ * (lx,ly,lz) the light; alpha [imh,imw] uint8 (NULL = nothing masked; < 255 masks); uv2cam [imh,imw,2] float64.
+ * -> cvis_camspc (ignores `occluded`), lvis_camspc [imh,imw] uint8: cosine clipped to [0,1], TRUNCATED x255;
+ *    uv2cam_f16 [imh,imw,2] float16: the masked map, float64 -> float16 in one rounding to nearest even (4-byte aligned);
+ *    uv2cam_png [imh,imw,3] uint8: the masked map clipped, truncated x255, blue = 0.
+ */
+int nlt_capture_camspc(const double* locs, const double* normals, const unsigned char* valid,
+                       const unsigned char* occluded, double cx, double cy, double cz, double lx, double ly, double lz,
+                       const unsigned char* alpha, const double* uv2cam, int imh, int imw,
+                       unsigned char* cvis_camspc, unsigned char* lvis_camspc, void* uv2cam_f16,
+                       unsigned char* uv2cam_png, void* stream);
+
+/*
+ * UV space, one thread per texel: cam2uv is read once, the 1/32-pixel coordinate and the four taps are formed once.
+ *   replaces: data_gen/render.py:157,159 (cam2uv.png, cam2uv.npy; cam2uv is NOT masked) and :173-179
+ *             remap(cvis_camspc | lvis_camspc | rgb_camspc, cam2uv) with force_kbg.
+ * cam2uv [uvh,uvw,ldm] float64 (ldm >= 2: x, y first); cvis_camspc, lvis_camspc [imh,imw] uint8; rgb_camspc
+ * [imh,imw,ld_rgb] uint8, ld_rgb >= 3 (Blender writes RGBA; three channels are read), or NULL together with rgb
+ * (a test sample rendered without ground truth).
+ * -> cvis, lvis [uvh,uvw], rgb [uvh,uvw,3] uint8; cam2uv_f16 [uvh,uvw,2] float16; cam2uv_png [uvh,uvw,3] uint8.
+ */
+int nlt_capture_uvspc(const double* cam2uv, int ldm, int uvh, int uvw, const unsigned char* cvis_camspc,
+                      const unsigned char* lvis_camspc, const unsigned char* rgb_camspc, int ld_rgb, int imh, int imw,
+                      unsigned char* cvis, unsigned char* lvis, unsigned char* rgb, void* cam2uv_f16,
+                      unsigned char* cam2uv_png, void* stream);
+
+/*
+ * diffuse.png and diffuse_camspc.png of `frames` samples in one launch.
+ *   replaces: data_gen/postproc.py:66-82 -- diffuse = write_arr(albedo * lvis/255, clip=True) and
+ *             remap(diffuse, np.load(uv2cam.npy)) (float16 map: the product with the size is rounded to float16 first).
+ * albedo [h,w,3] float64; lvis [frames,h,w] uint8; uv2cam_f16 [frames,imh,imw,2] float16.
+ * -> diffuse [frames,h,w,3], diffuse_camspc [frames,imh,imw,3] uint8.  The camera-space taps recompute the diffuse
+ *    bytes from albedo and lvis, so neither output is read here.
+ */
+int nlt_diffuse_bases(const double* albedo, const unsigned char* lvis, const void* uv2cam_f16, int frames, int h,
+                      int w, int imh, int imw, unsigned char* diffuse, unsigned char* diffuse_camspc, void* stream);
+
+/*
  * UV-index map: paints `samples` scattered (u,v) -> value samples onto an h x w grid.  A texel is TRUSTED when
  * an occupied texel -- integer indices ri = int((1-v)(h-1)), ci = int(u(w-1)) of some sample -- lies within L1
  * distance max_l1; trusted texels take the value of the nearest sample (Euclidean in uv; ties -> lowest sample

@@ -169,6 +169,9 @@ SIGNATURES = {
     'nlt_diffuse_base': (_c_int, [_vp, _vp, _c_int, _c_long, _vp, _vp]),
     'nlt_remap_bilinear_u8': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_remap_bilinear_f32': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    'nlt_capture_camspc': (_c_int, [_vp] * 4 + [_c_double] * 6 + [_vp, _vp, _c_int, _c_int] + [_vp] * 5),
+    'nlt_capture_uvspc': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _c_int, _c_int, _c_int] + [_vp] * 6),
+    'nlt_diffuse_bases': (_c_int, [_vp, _vp, _vp] + [_c_int] * 5 + [_vp, _vp, _vp]),
     'nlt_uv_index_map_workspace_bytes': (_c_long, [_c_int, _c_int, _c_long]),
     'nlt_uv_index_map': (_c_int, [_vp, _vp, _c_long, _c_int, _c_int, _c_int, _c_int, _c_double, _vp, _vp, _vp, _vp]),
     'nlt_knn_indices': (_c_int, [_vp, _c_int, _vp, _c_int, _c_int, _vp, _vp]),
@@ -1533,6 +1536,64 @@ def remap_bilinear(src, mapping, force_kbg=True):
     _call(name, _tptr(src, src.dtype, 'src'), h, w, c, _tptr(mapping, mapping.dtype, 'mapping'), _MAP_DTYPES[mapping.dtype],
           ldm, oh, ow, 1 if force_kbg else 0, out.data_ptr())
     return out
+
+
+def capture_camspc(locs, normals, valid, occluded, cam_loc, light_loc, alpha, uv2cam):
+    """One launch over the camera pixels (data_gen/render.py:155-171).  locs/normals [imh*imw,3] float64, valid / occluded
+    (or None) [imh*imw] uint8, alpha [imh,imw] uint8 (or None: nothing masked), uv2cam [imh,imw,2] float64 ->
+    (cvis_camspc, lvis_camspc uint8 [imh,imw], masked uv2cam float16 [imh,imw,2], uv2cam.png uint8 [imh,imw,3])."""
+    if uv2cam.dim() != 3 or uv2cam.shape[2] != 2 or valid.numel() != uv2cam.shape[0] * uv2cam.shape[1]:
+        raise NLTError("capture_camspc: uv2cam %s does not cover the %d pixels of `valid`" % (tuple(uv2cam.shape), valid.numel()))
+    imh, imw = uv2cam.shape[:2]
+    if alpha is not None and tuple(alpha.shape) != (imh, imw):
+        raise NLTError("capture_camspc: alpha %s is not [%d,%d]" % (tuple(alpha.shape), imh, imw))
+    dev, u8 = valid.device, torch.uint8
+    cvis = torch.empty((imh, imw), device=dev, dtype=u8)
+    lvis = torch.empty((imh, imw), device=dev, dtype=u8)
+    f16 = torch.empty((imh, imw, 2), device=dev, dtype=torch.float16)
+    png = torch.empty((imh, imw, 3), device=dev, dtype=u8)
+    _call('nlt_capture_camspc', _tptr(locs, torch.float64, 'locs'), _tptr(normals, torch.float64, 'normals'),
+          _tptr(valid, u8, 'valid'), _tptr(occluded, u8, 'occluded'), *(float(x) for x in cam_loc), *(float(x) for x in light_loc),
+          _tptr(alpha, u8, 'alpha'), _tptr(uv2cam, torch.float64, 'uv2cam'), imh, imw, cvis.data_ptr(), lvis.data_ptr(),
+          f16.data_ptr(), png.data_ptr())
+    return cvis, lvis, f16, png
+
+
+def capture_uvspc(cam2uv, cvis_camspc, lvis_camspc, rgb_camspc=None):
+    """One launch over the UV texels (data_gen/render.py:157,159,173-179).  cam2uv [uvh,uvw,>=2] float64; cvis_camspc,
+    lvis_camspc [imh,imw] uint8; rgb_camspc [imh,imw,3|4] uint8 or None -> (cvis, lvis uint8 [uvh,uvw], rgb uint8 [uvh,uvw,3]
+    or None, cam2uv float16 [uvh,uvw,2], cam2uv.png uint8 [uvh,uvw,3])."""
+    if cam2uv.dim() != 3 or cvis_camspc.dim() != 2 or lvis_camspc.shape != cvis_camspc.shape:
+        raise NLTError("capture_uvspc: cam2uv %s, cvis_camspc %s, lvis_camspc %s" % tuple(tuple(t.shape) for t in (cam2uv, cvis_camspc, lvis_camspc)))
+    uvh, uvw, ldm = cam2uv.shape
+    imh, imw = cvis_camspc.shape
+    if rgb_camspc is not None and (rgb_camspc.dim() != 3 or tuple(rgb_camspc.shape[:2]) != (imh, imw)):
+        raise NLTError("capture_uvspc: rgb_camspc %s is not [%d,%d,3|4]" % (tuple(rgb_camspc.shape), imh, imw))
+    dev, u8 = cam2uv.device, torch.uint8
+    cvis = torch.empty((uvh, uvw), device=dev, dtype=u8)
+    lvis = torch.empty((uvh, uvw), device=dev, dtype=u8)
+    rgb = torch.empty((uvh, uvw, 3), device=dev, dtype=u8) if rgb_camspc is not None else None
+    f16 = torch.empty((uvh, uvw, 2), device=dev, dtype=torch.float16)
+    png = torch.empty((uvh, uvw, 3), device=dev, dtype=u8)
+    _call('nlt_capture_uvspc', _tptr(cam2uv, torch.float64, 'cam2uv'), ldm, uvh, uvw, _tptr(cvis_camspc, u8, 'cvis_camspc'),
+          _tptr(lvis_camspc, u8, 'lvis_camspc'), _tptr(rgb_camspc, u8, 'rgb_camspc'), 0 if rgb_camspc is None else rgb_camspc.shape[2],
+          imh, imw, cvis.data_ptr(), lvis.data_ptr(), _tptr(rgb, u8, 'rgb'), f16.data_ptr(), png.data_ptr())
+    return cvis, lvis, rgb, f16, png
+
+
+def diffuse_bases(albedo_, lvis, uv2cam):
+    """One launch for all frames (data_gen/postproc.py:66-82).  albedo [H,W,3] float64, lvis [F,H,W] uint8, uv2cam
+    [F,imh,imw,2] float16 (as stored) -> (diffuse uint8 [F,H,W,3], diffuse_camspc uint8 [F,imh,imw,3])."""
+    if lvis.dim() != 3 or uv2cam.dim() != 4 or uv2cam.shape[0] != lvis.shape[0] or uv2cam.shape[3] != 2 \
+            or tuple(albedo_.shape) != tuple(lvis.shape[1:]) + (3,):
+        raise NLTError("diffuse_bases: albedo %s, lvis %s, uv2cam %s" % tuple(tuple(t.shape) for t in (albedo_, lvis, uv2cam)))
+    f, h, w = lvis.shape
+    imh, imw = uv2cam.shape[1:3]
+    diffuse = torch.empty((f, h, w, 3), device=lvis.device, dtype=torch.uint8)
+    cam = torch.empty((f, imh, imw, 3), device=lvis.device, dtype=torch.uint8)
+    _call('nlt_diffuse_bases', _tptr(albedo_, torch.float64, 'albedo'), _tptr(lvis, torch.uint8, 'lvis'),
+          _tptr(uv2cam, torch.float16, 'uv2cam'), f, h, w, imh, imw, diffuse.data_ptr(), cam.data_ptr())
+    return diffuse, cam
 
 
 def uv_index_map(uvs, values, h, w, max_l1=4, fill=0.0, want_index=False):

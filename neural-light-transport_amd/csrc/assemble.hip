@@ -23,12 +23,10 @@ __device__ __forceinline__ double dot3(double ax, double ay, double az, double b
   return (ax * bx + ay * by) + az * bz;
 }
 
-__global__ __launch_bounds__(256) void cosine_kernel(const double* __restrict__ locs, const double* __restrict__ normals,
-                                                     const u8* __restrict__ valid, const u8* __restrict__ occluded,
-                                                     double sx, double sy, double sz, long pixels,
-                                                     double* __restrict__ cos_out, u8* __restrict__ u8_out) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= pixels) return;
+// cos at pixel i for a source at (sx, sy, sz): the operation order every cosine output of this file shares
+__device__ __forceinline__ double cosine_at(const double* __restrict__ locs, const double* __restrict__ normals,
+                                            const u8* __restrict__ valid, const u8* __restrict__ occluded,
+                                            double sx, double sy, double sz, long i) {
   double c = 0.0;
   const bool keep = valid[i] != 0 && !(occluded && occluded[i] != 0);
   if (keep) {
@@ -42,11 +40,24 @@ __global__ __launch_bounds__(256) void cosine_kernel(const double* __restrict__ 
     nx = nx / nl; ny = ny / nl; nz = nz / nl;
     c = dot3(dx, dy, dz, nx, ny, nz);
   }
+  return c;
+}
+
+// denormalize_float(np.clip(x, 0, 1)): clip, then TRUNCATE x * 255 (render.py:164,170; write_arr(clip=True))
+__device__ __forceinline__ u8 quantize_unit(double c) {
+  const double q = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
+  return (u8)(int)(q * 255.0);
+}
+
+__global__ __launch_bounds__(256) void cosine_kernel(const double* __restrict__ locs, const double* __restrict__ normals,
+                                                     const u8* __restrict__ valid, const u8* __restrict__ occluded,
+                                                     double sx, double sy, double sz, long pixels,
+                                                     double* __restrict__ cos_out, u8* __restrict__ u8_out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pixels) return;
+  const double c = cosine_at(locs, normals, valid, occluded, sx, sy, sz, i);
   if (cos_out) cos_out[i] = c;
-  if (u8_out) {
-    double q = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);   // np.clip(x, 0, 1)
-    u8_out[i] = (u8)(int)(q * 255.0);                 // denormalize_float: truncation
-  }
+  if (u8_out) u8_out[i] = quantize_unit(c);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -77,17 +88,27 @@ __global__ __launch_bounds__(256) void albedo_div_kernel(double* __restrict__ su
   sum[e] = sum[e] / m;
 }
 
+// one channel of diffuse.png: clip(albedo * lvis/255, 0, 1) * 255, truncated (postproc.py:72-76)
+__device__ __forceinline__ u8 diffuse_u8(double albedo, u8 lvis) {
+  const double lv = (double)lvis / 255.0;
+  double d = albedo * lv;
+  d = d < 0.0 ? 0.0 : (d > 1.0 ? 1.0 : d);
+  return (u8)(int)(d * 255.0);
+}
+
+// byte i of diffuse [frames, texels, 3]: consecutive threads read consecutive albedo entries and store consecutive bytes
+__device__ __forceinline__ u8 diffuse_byte(const double* __restrict__ albedo, const u8* __restrict__ lvis, long texels, long i) {
+  const long per_frame = texels * 3;
+  const long e = i % per_frame;
+  const long t = i / 3;                                          // frame*texels + texel
+  return diffuse_u8(albedo[e], lvis[t]);
+}
+
 __global__ __launch_bounds__(256) void diffuse_kernel(const double* __restrict__ albedo, const u8* __restrict__ lvis,
                                                       long texels, long total, u8* __restrict__ out) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;     // over frames*texels*3
   if (i >= total) return;
-  const long per_frame = texels * 3;
-  const long e = i % per_frame;
-  const long t = i / 3;                                          // frame*texels + texel
-  const double lv = (double)lvis[t] / 255.0;
-  double d = albedo[e] * lv;
-  d = d < 0.0 ? 0.0 : (d > 1.0 ? 1.0 : d);
-  out[i] = (u8)(int)(d * 255.0);
+  out[i] = diffuse_byte(albedo, lvis, texels, i);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -95,8 +116,9 @@ __global__ __launch_bounds__(256) void diffuse_kernel(const double* __restrict__
 // thread = output texel
 // ---------------------------------------------------------------------------------------
 template <int MAPT> __device__ __forceinline__ float map_coord(const void* m, long idx, int size);
+__device__ __forceinline__ float scale_coord(double v, int size) { return (float)(v * (double)size); }   // (mapping * size).astype(float32)
 template <> __device__ __forceinline__ float map_coord<0>(const void* m, long idx, int size) {      // float64 map
-  return (float)(static_cast<const double*>(m)[idx] * (double)size);
+  return scale_coord(static_cast<const double*>(m)[idx], size);
 }
 template <> __device__ __forceinline__ float map_coord<1>(const void* m, long idx, int size) {      // float32 map
   return static_cast<const float*>(m)[idx] * (float)size;
@@ -108,10 +130,7 @@ template <> __device__ __forceinline__ float map_coord<2>(const void* m, long id
 
 struct RemapCoord { int ix, iy, fx, fy; };
 
-template <int MAPT>
-__device__ __forceinline__ RemapCoord remap_coord(const void* mapping, long o, int ldm, int h, int w) {
-  const float mx = map_coord<MAPT>(mapping, o * ldm, w);
-  const float my = map_coord<MAPT>(mapping, o * ldm + 1, h);
+__device__ __forceinline__ RemapCoord remap_coord_px(float mx, float my) {
   const int sx = __float2int_rn(mx * 32.f);                    // cvRound(x * INTER_TAB_SIZE): half to even
   const int sy = __float2int_rn(my * 32.f);
   RemapCoord r;
@@ -122,26 +141,44 @@ __device__ __forceinline__ RemapCoord remap_coord(const void* mapping, long o, i
 }
 
 template <int MAPT>
+__device__ __forceinline__ RemapCoord remap_coord(const void* mapping, long o, int ldm, int h, int w) {
+  return remap_coord_px(map_coord<MAPT>(mapping, o * ldm, w), map_coord<MAPT>(mapping, o * ldm + 1, h));
+}
+
+// The four taps of an 8-bit remap: cv2's 15-bit weights from the 32 x 32 fraction table and the source PIXEL each tap reads
+// (-1: outside the image, or the top-left texel under force_kbg -> reads as 0).
+struct RemapTaps { int wt[4]; long px[4]; };
+
+__device__ __forceinline__ RemapTaps remap_taps(const RemapCoord& r, int h, int w, int force_kbg) {
+  RemapTaps t;
+  t.wt[0] = (32 - r.fy) * (32 - r.fx) * 32; t.wt[1] = (32 - r.fy) * r.fx * 32;
+  t.wt[2] = r.fy * (32 - r.fx) * 32;        t.wt[3] = r.fy * r.fx * 32;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = r.ix + (k & 1), y = r.iy + (k >> 1);
+    const bool ok = x >= 0 && x < w && y >= 0 && y < h && !(force_kbg && x == 0 && y == 0);
+    t.px[k] = ok ? (long)y * w + x : -1;
+  }
+  return t;
+}
+
+// (sum of tap * weight + 2^14) >> 15 of one channel; `at(pixel)` yields the source byte
+template <typename At>
+__device__ __forceinline__ u8 remap_blend(const RemapTaps& t, At at) {
+  int acc = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc += (t.px[k] >= 0 ? (int)at(t.px[k]) : 0) * t.wt[k];
+  return (u8)((acc + (1 << 14)) >> 15);
+}
+
+template <int MAPT>
 __global__ __launch_bounds__(256) void remap_u8_kernel(const u8* __restrict__ src, int h, int w, int c,
                                                        const void* __restrict__ mapping, int ldm, long out_px,
                                                        int force_kbg, u8* __restrict__ out) {
   const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= out_px) return;
-  const RemapCoord r = remap_coord<MAPT>(mapping, o, ldm, h, w);
-  const int wt[4] = {(32 - r.fy) * (32 - r.fx) * 32, (32 - r.fy) * r.fx * 32, r.fy * (32 - r.fx) * 32, r.fy * r.fx * 32};
-  long tap[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int x = r.ix + (t & 1), y = r.iy + (t >> 1);
-    const bool ok = x >= 0 && x < w && y >= 0 && y < h && !(force_kbg && x == 0 && y == 0);
-    tap[t] = ok ? ((long)y * w + x) * c : -1;
-  }
-  for (int ch = 0; ch < c; ++ch) {
-    int acc = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc += (tap[t] >= 0 ? (int)src[tap[t] + ch] : 0) * wt[t];
-    out[o * c + ch] = (u8)((acc + (1 << 14)) >> 15);
-  }
+  const RemapTaps t = remap_taps(remap_coord<MAPT>(mapping, o, ldm, h, w), h, w, force_kbg);
+  for (int ch = 0; ch < c; ++ch) out[o * c + ch] = remap_blend(t, [&](long p) { return src[p * c + ch]; });
 }
 
 template <int MAPT>
@@ -384,7 +421,135 @@ __global__ __launch_bounds__(256) void resize_cv_kernel(const void* __restrict__
   out[idx] = (float)(b0 * r0 + b1 * r1);
 }
 
+// ---------------------------------------------------------------------------------------
+// The capture writer (data_gen/render.py:150-179, postproc.py:66-82): every per-sample file of a capture in two launches,
+// the diffuse bases of all frames in one.  The arithmetic is the helpers' above; only the stores are new.
+// ---------------------------------------------------------------------------------------
+// np.float64 -> np.float16 (save_float16_npy): ONE rounding to nearest even.  Going through float32 would round twice; the
+// float is therefore rounded to odd (truncated, sticky bit kept), which leaves the final rounding to the half conversion.
+__device__ __forceinline__ __half half_of_double(double x) {
+  float f = (float)x;
+  unsigned b = __float_as_uint(f);
+  const double back = (double)f;
+  if (back != x && x == x) {                                     // inexact (and not NaN)
+    if (fabs(back) > fabs(x)) b -= 1u;                           // rounded away from zero: one step back = truncation
+    b |= 1u;
+  }
+  return __float2half_rn(__uint_as_float(b));
+}
+
+// A [0,1] map's (x, y) as the two files hold it: float16 pair, and the uint8 RGB texel of write_arr(clip=True), blue = 0
+__device__ __forceinline__ void store_map(double x, double y, long i, __half2* __restrict__ f16, u8* __restrict__ png) {
+  f16[i] = __halves2half2(half_of_double(x), half_of_double(y));
+  png[3 * i] = quantize_unit(x); png[3 * i + 1] = quantize_unit(y); png[3 * i + 2] = 0;
+}
+
+// thread = camera pixel   (render.py:155-171)
+__global__ __launch_bounds__(256) void capture_camspc_kernel(const double* __restrict__ locs, const double* __restrict__ normals,
+                                                             const u8* __restrict__ valid, const u8* __restrict__ occluded,
+                                                             double cx, double cy, double cz, double lx, double ly, double lz,
+                                                             const u8* __restrict__ alpha, const double* __restrict__ uv2cam,
+                                                             long pixels, u8* __restrict__ cvis, u8* __restrict__ lvis,
+                                                             __half2* __restrict__ map_f16, u8* __restrict__ map_png) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pixels) return;
+  cvis[i] = quantize_unit(cosine_at(locs, normals, valid, nullptr, cx, cy, cz, i));     // the view ignores cast shadows
+  lvis[i] = quantize_unit(cosine_at(locs, normals, valid, occluded, lx, ly, lz, i));
+  const bool outside = alpha && alpha[i] < 255;                  // uv2cam[alpha < 1] = 0
+  store_map(outside ? 0.0 : uv2cam[2 * i], outside ? 0.0 : uv2cam[2 * i + 1], i, map_f16, map_png);
+}
+
+// thread = UV texel   (render.py:157,159,173-179)
+__global__ __launch_bounds__(256) void capture_uvspc_kernel(const double* __restrict__ cam2uv, int ldm, long texels,
+                                                            const u8* __restrict__ cvis_c, const u8* __restrict__ lvis_c,
+                                                            const u8* __restrict__ rgb_c, int ld_rgb, int imh, int imw,
+                                                            u8* __restrict__ cvis, u8* __restrict__ lvis, u8* __restrict__ rgb,
+                                                            __half2* __restrict__ map_f16, u8* __restrict__ map_png) {
+  const long o = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= texels) return;
+  const double x = cam2uv[o * ldm], y = cam2uv[o * ldm + 1];
+  const RemapTaps t = remap_taps(remap_coord_px(scale_coord(x, imw), scale_coord(y, imh)), imh, imw, 1);
+  cvis[o] = remap_blend(t, [&](long p) { return cvis_c[p]; });
+  lvis[o] = remap_blend(t, [&](long p) { return lvis_c[p]; });
+  if (rgb)
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) rgb[3 * o + ch] = remap_blend(t, [&](long p) { return rgb_c[p * ld_rgb + ch]; });
+  store_map(x, y, o, map_f16, map_png);
+}
+
+// thread = one BYTE of diffuse (the first frames * texels * 3 threads, as diffuse_kernel: every load and store coalesced), then
+// one camera pixel of one frame.  The camera half forms its taps from albedo and lvis directly, so it does not wait for the UV
+// half's stores.   (postproc.py:66-82)
+__global__ __launch_bounds__(256) void diffuse_bases_kernel(const double* __restrict__ albedo, const u8* __restrict__ lvis,
+                                                            const __half* __restrict__ uv2cam, long uv_bytes, long texels,
+                                                            int h, int w, long cam_total, long pixels,
+                                                            u8* __restrict__ diffuse, u8* __restrict__ diffuse_cam) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < uv_bytes) {
+    diffuse[i] = diffuse_byte(albedo, lvis, texels, i);
+    return;
+  }
+  i -= uv_bytes;
+  if (i >= cam_total) return;
+  const u8* lv = lvis + (i / pixels) * texels;
+  const RemapTaps t = remap_taps(remap_coord<2>(uv2cam, i, 2, h, w), h, w, 1);
+  u8 px[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) px[ch] = remap_blend(t, [&](long p) { return diffuse_u8(albedo[3 * p + ch], lv[p]); });
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) diffuse_cam[3 * i + ch] = px[ch];
+}
+
 }  // namespace
+
+extern "C" int nlt_capture_camspc(const double* locs, const double* normals, const unsigned char* valid,
+                                  const unsigned char* occluded, double cx, double cy, double cz, double lx, double ly, double lz,
+                                  const unsigned char* alpha, const double* uv2cam, int imh, int imw,
+                                  unsigned char* cvis_camspc, unsigned char* lvis_camspc, void* uv2cam_f16,
+                                  unsigned char* uv2cam_png, void* stream) {
+  if (!locs || !normals || !valid || !uv2cam || imh <= 0 || imw <= 0) return NLT_ERR_BAD_ARG;
+  if (!cvis_camspc || !lvis_camspc || !uv2cam_f16 || !uv2cam_png) return NLT_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(uv2cam_f16) & 3u) return NLT_ERR_BAD_ARG;            // written as float16 pairs
+  if (imh > 32767 || imw > 32767) return NLT_ERR_UNSUPPORTED;
+  const long pixels = (long)imh * imw;
+  hipLaunchKernelGGL(capture_camspc_kernel, dim3(blocks_for(pixels)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     locs, normals, valid, occluded, cx, cy, cz, lx, ly, lz, alpha, uv2cam, pixels, cvis_camspc, lvis_camspc,
+                     static_cast<__half2*>(uv2cam_f16), uv2cam_png);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_capture_uvspc(const double* cam2uv, int ldm, int uvh, int uvw, const unsigned char* cvis_camspc,
+                                 const unsigned char* lvis_camspc, const unsigned char* rgb_camspc, int ld_rgb, int imh, int imw,
+                                 unsigned char* cvis, unsigned char* lvis, unsigned char* rgb, void* cam2uv_f16,
+                                 unsigned char* cam2uv_png, void* stream) {
+  if (!cam2uv || !cvis_camspc || !lvis_camspc || uvh <= 0 || uvw <= 0 || imh <= 0 || imw <= 0 || ldm < 2) return NLT_ERR_BAD_ARG;
+  if (!cvis || !lvis || !cam2uv_f16 || !cam2uv_png) return NLT_ERR_BAD_ARG;
+  if (reinterpret_cast<uintptr_t>(cam2uv_f16) & 3u) return NLT_ERR_BAD_ARG;
+  if ((rgb_camspc == nullptr) != (rgb == nullptr) || (rgb_camspc && ld_rgb < 3)) return NLT_ERR_BAD_ARG;
+  if (uvh > 32767 || uvw > 32767 || imh > 32767 || imw > 32767) return NLT_ERR_UNSUPPORTED;
+  const long texels = (long)uvh * uvw;
+  hipLaunchKernelGGL(capture_uvspc_kernel, dim3(blocks_for(texels)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     cam2uv, ldm, texels, cvis_camspc, lvis_camspc, rgb_camspc, ld_rgb, imh, imw, cvis, lvis, rgb,
+                     static_cast<__half2*>(cam2uv_f16), cam2uv_png);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_diffuse_bases(const double* albedo, const unsigned char* lvis, const void* uv2cam_f16, int frames, int h,
+                                 int w, int imh, int imw, unsigned char* diffuse, unsigned char* diffuse_camspc, void* stream) {
+  if (!albedo || !lvis || !uv2cam_f16 || !diffuse || !diffuse_camspc) return NLT_ERR_BAD_ARG;
+  if (frames <= 0 || h <= 0 || w <= 0 || imh <= 0 || imw <= 0) return NLT_ERR_BAD_ARG;
+  if (h > 32767 || w > 32767 || imh > 32767 || imw > 32767) return NLT_ERR_UNSUPPORTED;
+  const long texels = (long)h * w, pixels = (long)imh * imw;
+  const long uv_bytes = frames * texels * 3, cam_total = frames * pixels;
+  if ((uv_bytes + cam_total + 255) / 256 > 0x7fffffffL) return NLT_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(diffuse_bases_kernel, dim3(blocks_for(uv_bytes + cam_total)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     albedo, lvis, static_cast<const __half*>(uv2cam_f16), uv_bytes, texels, h, w, cam_total, pixels, diffuse,
+                     diffuse_camspc);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
 
 extern "C" int nlt_resize_cv_linear(const void* src, int src_kind, int n, int h, int w, int c, int oh, int ow, float* out,
                                     void* stream) {

@@ -6,10 +6,14 @@ mapping.  `intersect` is the dict render.py builds from xm.blender.camera.backpr
     'occluded' [P] uint8 (only for the light: the result of the reference's BVH shadow rays,
                           render.py:238-254, which stay in Blender)
 The reference's list-of-Vector form is converted with `dense_intersect`."""
+import os
+from os.path import join
+
 import numpy as np
 import torch
 
 from .. import _capi as C
+from .util import dump_json, encode_pool, load_json, name_from_json_path
 
 
 def dense_intersect(intersect, obj_name, device='cuda', occluded=None):
@@ -71,6 +75,101 @@ def grid_query_unstruct(uvs, values, grid_res, method=None):
     h, w = grid_res
     out = C.uv_index_map(uvs.contiguous(), values.contiguous(), h, w, int(max_l1), float(fill[0]))
     return out[:, :, 0] if out.shape[2] == 1 else out
+
+
+def _params(x):
+    """A camera / light as render.py's load_json gives it: the dict itself, or the path of its .json."""
+    return load_json(x) if isinstance(x, str) else x
+
+
+def _sample_hw(intersect, rgb_camspc, alpha):
+    for img in (alpha, rgb_camspc):
+        if img is not None:
+            return int(img.shape[0]), int(img.shape[1])
+    if 'hw' in intersect:
+        return tuple(int(x) for x in intersect['hw'])
+    if intersect['valid'].dim() == 2:
+        return tuple(intersect['valid'].shape)
+    raise ValueError("the camera resolution is unknown: give alpha or rgb_camspc, intersect['hw'] = (imh, imw), or a 2-D 'valid'")
+
+
+def render_sample(intersect, cached_unwrap, cam, light, uvs, rgb_camspc=None, alpha=None, max_l1_interp=4):
+    """render.py:main after Blender (lines 150-179): the bidirectional mapping, then every per-sample buffer in two launches
+    (nlt_capture_camspc over the camera pixels, nlt_capture_uvspc over the UV texels).
+
+    intersect: the dense form of `dense_intersect` (with 'face_i'; 'occluded' from the caller's shadow rays, absent = none).
+    cam, light: the dicts of cam.json / light.json (or their paths); only 'position' is read here.
+    rgb_camspc [imh,imw,3|4] uint8 and alpha [imh,imw] uint8 as Blender rendered them (tensors or arrays); rgb_camspc = None is
+    a test sample without ground truth (no rgb), alpha = None masks nothing.
+    Returns {file name: device tensor}, one entry per file `write_sample` writes, plus '_uv2cam' / '_cam2uv' / '_alpha' (the float64
+    maps and the mask: the debug re-projections and the tests read them)."""
+    cam, light = _params(cam), _params(light)
+    dev = intersect['valid'].device
+    as_dev = lambda a: None if a is None else (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev).contiguous()
+    rgb_camspc, alpha = as_dev(rgb_camspc), as_dev(alpha)
+    imh, imw = _sample_hw(intersect, rgb_camspc, alpha)
+    if alpha is not None and alpha.dim() != 2:
+        raise ValueError("alpha must be [imh,imw], got %s" % (tuple(alpha.shape),))
+    xs, ys = np.meshgrid(range(imw), range(imh))
+    xys = np.dstack((xs, ys)).reshape(-1, 2)                        # render.py:136-142
+    uv2cam, cam2uv = calc_bidir_mapping(cached_unwrap, None, xys, intersect, uvs, max_l1_interp)
+    cvis_c, lvis_c, uv2cam_f16, uv2cam_png = C.capture_camspc(
+        intersect['locs'].reshape(-1, 3), intersect['normals'].reshape(-1, 3), intersect['valid'].reshape(-1),
+        None if intersect.get('occluded') is None else intersect['occluded'].reshape(-1),
+        cam['position'], light['position'], alpha, uv2cam.contiguous())
+    cvis, lvis, rgb, cam2uv_f16, cam2uv_png = C.capture_uvspc(cam2uv.contiguous(), cvis_c, lvis_c, rgb_camspc)
+    sample = {'uv2cam.png': uv2cam_png, 'cam2uv.png': cam2uv_png, 'uv2cam.npy': uv2cam_f16, 'cam2uv.npy': cam2uv_f16,
+              'lvis_camspc.png': lvis_c, 'cvis_camspc.png': cvis_c, 'cvis.png': cvis, 'lvis.png': lvis,
+              '_uv2cam': uv2cam, '_cam2uv': cam2uv, '_alpha': alpha}
+    if rgb_camspc is not None:
+        sample['rgb_camspc.png'], sample['rgb.png'] = rgb_camspc, rgb
+    if alpha is not None:
+        sample['alpha.png'] = alpha
+    return sample
+
+
+def _neighbors(nn, cam, light):
+    """render.py:200-206: {'cam': cam_nn[cam_name], 'light': light_nn[light_name]}.  nn: that dict itself, or the pair
+    (cam_nn, light_nn) of neighbour tables (dicts or .json paths), looked up by the camera's / light's name."""
+    if isinstance(nn, dict):
+        return nn
+    name = lambda x: name_from_json_path(x) if isinstance(x, str) else x['name']
+    cam_nn, light_nn = (_params(t) for t in nn)
+    return {'cam': cam_nn[name(cam)], 'light': light_nn[name(light)]}
+
+
+def write_sample(outdir, sample, cam, light, nn, debug=False, workers=None):
+    """render.py:156-206: writes one sample directory -- the PNGs (through util/vis.py:write_img, PIL), the two float16 .npy
+    maps, cam.json / light.json (copied when a path is given, dumped when a dict) and nn.json.  debug: also the three
+    `*_camspc_repro.png` of render.py:180-194.  One device-to-host copy per buffer, then the encodes on a thread pool of
+    min(16, number of files) threads (`workers` overrides it; 1 = in order on one thread).  Returns the file names written."""
+    from shutil import copyfile
+    from ..util.vis import write_img
+    files = {k: v for k, v in sample.items() if not k.startswith('_')}
+    if debug:                                                       # render.py:186-188: back through uv2cam (masked, float64)
+        uv2cam = sample['_uv2cam']
+        if sample['_alpha'] is not None:
+            uv2cam = torch.where((sample['_alpha'] < 255).unsqueeze(-1), torch.zeros_like(uv2cam), uv2cam)
+        for k in ('cvis', 'lvis', 'rgb'):
+            if k + '.png' in files:
+                files[k + '_camspc_repro.png'] = C.remap_bilinear(files[k + '.png'], uv2cam.contiguous())
+    host = {k: v.cpu().numpy() for k, v in files.items()}
+    os.makedirs(outdir, exist_ok=True)
+
+    def put(name):
+        if name.endswith('.npy'):
+            np.save(join(outdir, name), host[name])
+        else:
+            write_img(host[name], join(outdir, name))
+    with encode_pool(len(host), workers) as pool:
+        list(pool.map(put, sorted(host)))
+    for name, x in (('cam.json', cam), ('light.json', light)):
+        if isinstance(x, str):
+            copyfile(x, join(outdir, name))
+        else:
+            dump_json(x, join(outdir, name))
+    dump_json(_neighbors(nn, cam, light), join(outdir, 'nn.json'))
+    return sorted(host) + ['cam.json', 'light.json', 'nn.json']
 
 
 def calc_bidir_mapping(cached_unwrap, obj_name, xys, intersect, uvs, max_l1_interp=4):
