@@ -67,6 +67,27 @@ class _Derived:
         self.conv = c
 
 
+def _state_tensors(st):
+    """Every device tensor an override state owns or reads: the given maps, the override maps, the derived convs' arrays and
+    their packed fragments."""
+    found = []
+
+    def walk(x):
+        if torch.is_tensor(x):
+            if x.is_cuda and x.numel():
+                found.append(x)
+        elif isinstance(x, dict):
+            for v in x.values():
+                walk(v)
+        elif isinstance(x, (list, tuple)):
+            for v in x:
+                walk(v)
+        elif hasattr(x, '_packed'):                         # a derived Conv2D: arrays + fragment cache {key: (version, buffer)}
+            walk((x.kernel, x.bias, x._packed, getattr(x, '_packed_bf', None)))
+    walk({k: v for k, v in st.items() if k not in ('stamp', 'serial', 'ready', 'streams')})
+    return found
+
+
 class OverrideMixin:
     """RenderPlan's fused `obs_override` forward (see the module docstring)."""
 
@@ -135,6 +156,20 @@ class OverrideMixin:
             st = getattr(self.q, '_ovr_state', None)
             if st is None or st['stamp'] != stamp:
                 st = self.q._ovr_state = self._build_override(obs_override, dev, stamp)
+            if st['ready'] is not None and C._stream() not in st['streams']:
+                # Another stream than the one the maps were made on (another lane, or the caller's own stream after a lane built
+                # them): it waits for the build ONCE -- whatever it is given afterwards, a tape recorded later included, is behind
+                # that wait -- and every tensor of the state is marked as read here, so that the allocator hands the memory of a
+                # REPLACED state out again only after this stream has passed what it had queued when the last plan let go of it.
+                cur = torch.cuda.current_stream(dev)
+                paused = C.tape_pause()
+                try:
+                    C.wait_event(cur, st['ready'])
+                finally:
+                    C.tape_resume(paused)
+                for t in _state_tensors(st):
+                    t.record_stream(cur)
+                st['streams'].add(cur.cuda_stream)
         if self._ovr is not st:
             self._ovr = st
             self._drop_tapes()
@@ -144,7 +179,9 @@ class OverrideMixin:
         q, D, U = self.q, self.n_down, self.n_up
         ovr = [t[0:1].contiguous() for t in obs_override]
         cl = [t.shape[3] for t in ovr]
-        st = {'stamp': stamp, 'serial': OverrideMixin._serial[0], 'ovr': ovr, 'enc': {}, 'dec': {}}
+        # 'ready': event on the building stream behind the last launch of the build; 'streams': the streams (handles) ordered
+        # behind it -- the building one, and every one `_prepare_override` has made wait for it (None / empty off the GPU)
+        st = {'stamp': stamp, 'serial': OverrideMixin._serial[0], 'ovr': ovr, 'enc': {}, 'dec': {}, 'ready': None, 'streams': set()}
         # precision = bf16: the maps of the bf16 region's consumers (first conv of levels >= 3 and of blocks j <= D - 3) are
         # evaluated on the region's OPERANDS -- given map and weight slice rounded to bf16, fp32 accumulation, fp32 result -- as
         # the full-K conv over concat(query, given) would see them: what is left against it is fp32 summation order
@@ -215,6 +252,26 @@ class OverrideMixin:
                 else:
                     st['dec'][j] = (dq, run_map(dm, ovr[D - j]))
                 cx = db.n_ch_out
+            if dev.type == 'cuda':
+                # The fp32 fragments `_forward_ovr`'s nlt_conv_forward_map launches read (V{l}.q.s2: the query rows alone; the
+                # plain expanding blocks: [x | query half], the bottleneck its one summed source) are packed HERE, not on
+                # first use by whichever lane gets there first: everything another stream will read is then complete at the
+                # event below, on the stream that made it.
+                def pack(d, c0, c1):
+                    if c0 % 4 == 0 and c1 % 4 == 0 and d.n_ch_out % 4 == 0:     # (what `_conv` asks of a bias-map launch)
+                        d.packed(c0, c1)
+                if not bf:
+                    for l in range(3, D + 1):
+                        pack(st['enc'][l][0], cl[l - 1], 0)
+                cx = 2 * cl[D]
+                for j in range(U - 1):
+                    if not (bf and j <= D - 3):
+                        pack(st['dec'][j][0], cl[D - j] if j == 0 else cx, 0 if j == 0 else cl[D - j])
+                    cx = q.layers[D + 1 + j].convs()[1][0].n_ch_out
+                cur = torch.cuda.current_stream(dev)
+                st['ready'] = C.new_event()
+                C.record_event(st['ready'], cur)
+                st['streams'].add(cur.cuda_stream)
         finally:
             C.tape_resume(paused)
         return st
