@@ -7,6 +7,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import ckpt
 from . import optim
 
 
@@ -83,6 +84,24 @@ def restore_checkpoint(path, model, optimizer=None, legacy_layout=False):
             raise ValueError("%s holds no optimizer state" % path)
         optimizer.load_state_dict(ck['optimizer'])
     return ck['step']
+
+
+def save_reference(manager, model, optimizer, step):
+    """`ckptmanager.save()` of the reference's loop (nlt/trainvali.py:194) in the REFERENCE's own format: a TensorFlow tensor
+    bundle `ckpt-N` under `manager` (a `ckpt.ReferenceCheckpointManager`), which the reference's `nlt_test.py --ckpt` and
+    `trainvali.py` are meant to pick up (ckpt.py's STATUS says how far that has been checked).  Returns the prefix written."""
+    return manager.save(model, optimizer, step)
+
+
+def resume_reference(manager, model, optimizer):
+    """`ioutil.restore(ckpt, ckptmanager)` (nlt/util/io.py:32-35): restores net + optimizer from the manager's latest
+    checkpoint -- one a reference run left there included -- and returns its step; an empty directory changes nothing and
+    returns 0 (`ckpt.step` keeps its initial value)."""
+    latest = manager.latest_checkpoint
+    if latest is None:
+        return 0
+    step = ckpt.restore_reference_checkpoint(model, latest, optimizer)
+    return 0 if step is None else step
 
 
 AUTOGRAD_STEP = os.environ.get('NLT_AUTOGRAD_STEP', '0') == '1'   # single-rank step through torch.autograd (the reference-shaped path)
