@@ -1149,6 +1149,55 @@ int nlt_conv_k3_backward_weights(int mode, const float* x, int n, int h, int w, 
                                  const float* dpre, int cout, float* dw_keras, float* dbias,
                                  float* workspace, long workspace_floats, void* stream);
 
+/* ======================= LPIPS v0.1, AlexNet / lin (csrc/lpips.hip) =======================
+ * The perceptual distance of Zhang et al. 2018 as the published v0.1 "alex" network with its linear layers defines it.  Per image
+ * in [0, 1] (NHWC, 3 channels): t = ((2 x - 1) - shift) / scale; five ReLU feature maps
+ *   f1 = conv 11x11 s4 p2 (3 -> 64) of t                      [h1 = (h + 4 - 11) / 4 + 1]
+ *   f2 = conv 5x5 s1 p2 (64 -> 192) of maxpool3x3s2(f1)       [h2 = (h1 - 3) / 2 + 1]
+ *   f3 = conv 3x3 s1 p1 (192 -> 384) of maxpool3x3s2(f2)      [h3 = (h2 - 3) / 2 + 1]
+ *   f4 = conv 3x3 s1 p1 (384 -> 256) of f3,  f5 = conv 3x3 s1 p1 (256 -> 256) of f4
+ * (zero padding in scaled space; pools unpadded, floor), then per level n = f / (sqrt(sum_c f^2) + 1e-10),
+ * d_l = mean over texels of sum_c lin_l[c] (n_pred - n_gt)^2, and the value is d_1 + ... + d_5.  Exact fp32 products; every sum
+ * in an order fixed by the shapes (per-workgroup partials added in index order): no float atomics, one form, capturable.
+ * Corner rules: a texel whose features are all zero at a level normalises to 0 (0 / (0 + eps): it adds nothing of its own, two
+ * such texels add 0) and its gradient there is 0; the max-pool gradient goes to the FIRST maximum in window order (row-major).
+ * Conv weights are Keras arrays (kh,kw,Cin,Cout); the 3x3 layers run on nlt_conv_k3_forward / nlt_conv_k3_backward_data.
+ *   replaces: LPIPS.__call__ (nlt/losses.py:121-169) running third_party/lpips/net-lin_alex_v0.1.pb, and xm.metric.LPIPS
+ *             (third_party/xiuminglib/xiuminglib/metric.py:187-258).
+ *
+ * Layer-level entry points (each callable alone):
+ * conv1: x [n,h,w,3] in [0,1], affine = shift[3] then scale[3]; y [n,h1,w1,64] = relu(b + conv(t)).  h, w >= 11.
+ * conv1 backward-data: dpre [n,h1,w1,64] (w.r.t. the pre-activation) -> dx [n,h,w,3] w.r.t. x (includes the 2 / scale factor). */
+int nlt_lpips_conv1_forward(const float* x, int n, int h, int w, const float* affine, const float* w_keras, const float* bias,
+                            float* y, void* stream);
+int nlt_lpips_conv1_backward_data(const float* dpre, int n, int h, int w, const float* affine, const float* w_keras, float* dx,
+                                  void* stream);
+/* conv2: x [n,h,w,64] -> y [n,h,w,192] = relu(b + conv5x5(x)); backward-data: dpre [n,h,w,192] -> dx [n,h,w,64] (the same
+ * kernel with mirrored taps and the channel axes swapped).  16-byte aligned arrays. */
+int nlt_lpips_conv2_forward(const float* x, int n, int h, int w, const float* w_keras, const float* bias, float* y, void* stream);
+int nlt_lpips_conv2_backward_data(const float* dpre, int n, int h, int w, const float* w_keras, float* dx, void* stream);
+/* Max-pool 3x3 stride 2, no padding, floor: x [n,h,w,c] -> y [n,(h-3)/2+1,(w-3)/2+1,c]; h, w >= 3.  Backward: dx [n,h,w,c] is
+ * overwritten; a gather over the at most 2 x 2 windows that cover a texel, each window's gradient to its first maximum. */
+int nlt_lpips_pool_forward(const float* x, int n, int h, int w, int c, float* y, void* stream);
+int nlt_lpips_pool_backward(const float* dy, const float* x, int n, int h, int w, int c, float* dx, void* stream);
+/* Head of one level on features fp, fg [n,texels,c] (c <= 512): d[f] = mean_texels sum_c lin[c] (n_p - n_g)^2.
+ * workspace: nlt_lpips_head_workspace_floats(n, texels) floats, 8-byte aligned (float64 partials).
+ * Adjoint: dpre [n,texels,c] = (dup + d d[f] / d fp) * (fp > 0) -- the features are ReLU outputs, so this is the gradient w.r.t.
+ * the conv's pre-activation; dup (may be NULL) is what the layers above send down to fp. */
+long nlt_lpips_head_workspace_floats(int n, long texels);
+int nlt_lpips_head_forward(const float* fp, const float* fg, int n, long texels, int c, const float* lin, float* workspace,
+                           long workspace_floats, float* d, void* stream);
+int nlt_lpips_head_backward(const float* fp, const float* fg, int n, long texels, int c, const float* lin, const float* dup,
+                            float* dpre, void* stream);
+/* The whole chain.  weights: nlt_lpips_weights_floats() floats, 16-byte aligned: shift[3], scale[3], 2 unused, then the Keras
+ * array and bias of conv1 .. conv5, then lin1 .. lin5.  workspace: nlt_lpips_workspace_floats(n,h,w,want_grad) floats, 16-byte
+ * aligned.  loss[f] = LPIPS(gt_f, pred_f); if dunit != NULL also d loss[f] / d pred [n,h,w,3] (multiply by the upstream
+ * per-example gradient with nlt_scale_rows).  h or w < 31 (a level without texels): NLT_ERR_UNSUPPORTED, the query answers -1. */
+long nlt_lpips_weights_floats(void);
+long nlt_lpips_workspace_floats(int n, int h, int w, int want_grad);
+int nlt_lpips_loss(const float* pred, const float* gt, int n, int h, int w, const float* weights, float* workspace,
+                   long workspace_floats, float* loss, float* dunit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

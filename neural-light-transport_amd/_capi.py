@@ -74,6 +74,18 @@ SIGNATURES = {
     'nlt_ssim_workspace_floats': (_c_long, [_c_int] * 5),
     'nlt_ssim_loss': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _c_long, _vp, _vp, _vp]),
     'nlt_ssim_values': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _c_long, _vp, _vp]),
+    'nlt_lpips_conv1_forward': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    'nlt_lpips_conv1_backward_data': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    'nlt_lpips_conv2_forward': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    'nlt_lpips_conv2_backward_data': (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    'nlt_lpips_pool_forward': (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    'nlt_lpips_pool_backward': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    'nlt_lpips_head_workspace_floats': (_c_long, [_c_int, _c_long]),
+    'nlt_lpips_head_forward': (_c_int, [_vp, _vp, _c_int, _c_long, _c_int, _vp, _vp, _c_long, _vp, _vp]),
+    'nlt_lpips_head_backward': (_c_int, [_vp, _vp, _c_int, _c_long, _c_int, _vp, _vp, _vp, _vp]),
+    'nlt_lpips_weights_floats': (_c_long, []),
+    'nlt_lpips_workspace_floats': (_c_long, [_c_int] * 4),
+    'nlt_lpips_loss': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_long, _vp, _vp, _vp]),
     'nlt_sub_forward': (_c_int, [_vp, _vp, _c_long, _vp, _vp]),
     'nlt_finish_pred': (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_act_forward': (_c_int, [_vp, _c_long, _c_int, _c_float, _vp, _vp]),
@@ -918,6 +930,97 @@ def ssim_values(im1, im2, max_val):
     _call('nlt_ssim_values', _ptr(_dense(im1, 'im1')), _ptr(_dense(im2, 'im2')), n, h, w, c, float(max_val), _ptr(ws), ws.numel(),
           out.data_ptr())
     return out
+
+
+# ---------------------------------------------------------------- LPIPS v0.1, alex / lin (csrc/lpips.hip)
+def _lpips_out(n, h, w, c, like):
+    return torch.empty((n, h, w, c), device=like.device, dtype=torch.float32)
+
+
+def lpips_conv1_forward(x, affine, w_keras, bias):
+    """x [n,h,w,3] in [0,1], affine = shift[3] + scale[3], w_keras (11,11,3,64) -> relu(conv1(((2x - 1) - shift) / scale)) [n,h1,w1,64]."""
+    n, h, w, _ = _dense(x, 'x').shape
+    y = _lpips_out(n, (h - 7) // 4 + 1, (w - 7) // 4 + 1, 64, x)
+    _call('nlt_lpips_conv1_forward', _ptr(x), n, h, w, _ptr(_dense(affine, 'affine')), _ptr(_dense(w_keras, 'w_keras')), _ptr(bias), _ptr(y))
+    return y
+
+
+def lpips_conv1_backward_data(dpre, h, w, affine, w_keras):
+    """dpre [n,h1,w1,64] (w.r.t. conv1's pre-activation) -> d / d x [n,h,w,3], the 2 / scale of the input affine included."""
+    n = _dense(dpre, 'dpre').shape[0]
+    dx = _lpips_out(n, h, w, 3, dpre)
+    _call('nlt_lpips_conv1_backward_data', _ptr(dpre), n, h, w, _ptr(_dense(affine, 'affine')), _ptr(_dense(w_keras, 'w_keras')), _ptr(dx))
+    return dx
+
+
+def lpips_conv2_forward(x, w_keras, bias):
+    """x [n,h,w,64], w_keras (5,5,64,192) -> relu(conv2(x)) [n,h,w,192]."""
+    n, h, w, _ = _dense(x, 'x').shape
+    y = _lpips_out(n, h, w, 192, x)
+    _call('nlt_lpips_conv2_forward', _ptr(x), n, h, w, _ptr(_dense(w_keras, 'w_keras')), _ptr(bias), _ptr(y))
+    return y
+
+
+def lpips_conv2_backward_data(dpre, w_keras):
+    """dpre [n,h,w,192] -> d / d (conv2's input) [n,h,w,64]."""
+    n, h, w, _ = _dense(dpre, 'dpre').shape
+    dx = _lpips_out(n, h, w, 64, dpre)
+    _call('nlt_lpips_conv2_backward_data', _ptr(dpre), n, h, w, _ptr(_dense(w_keras, 'w_keras')), _ptr(dx))
+    return dx
+
+
+def lpips_pool_forward(x):
+    """Max-pool 3x3 stride 2, no padding, floor."""
+    n, h, w, c = _dense(x, 'x').shape
+    y = _lpips_out(n, (h - 3) // 2 + 1, (w - 3) // 2 + 1, c, x)
+    _call('nlt_lpips_pool_forward', _ptr(x), n, h, w, c, _ptr(y))
+    return y
+
+
+def lpips_pool_backward(dy, x):
+    """d / d x of lpips_pool_forward(x) from dy: each window's gradient to its first maximum in window order."""
+    n, h, w, c = _dense(x, 'x').shape
+    dx = torch.empty_like(x)
+    _call('nlt_lpips_pool_backward', _ptr(_dense(dy, 'dy')), _ptr(x), n, h, w, c, _ptr(dx))
+    return dx
+
+
+def lpips_head_forward(fp, fg, lin):
+    """fp, fg [n,h,w,c] feature maps of one level -> d [n] = mean over texels of sum_c lin[c] (fp / |fp| - fg / |fg|)^2."""
+    _same_shape(fp, fg, 'lpips_head_forward')
+    n, h, w, c = _dense(fp, 'fp').shape
+    ws = torch.empty(_size('nlt_lpips_head_workspace_floats', n, h * w), device=fp.device, dtype=torch.float32)
+    d = torch.empty(n, device=fp.device, dtype=torch.float32)
+    _call('nlt_lpips_head_forward', _ptr(fp), _ptr(_dense(fg, 'fg')), n, h * w, c, _ptr(_dense(lin, 'lin')), _ptr(ws), ws.numel(), _ptr(d))
+    return d
+
+
+def lpips_head_backward(fp, fg, lin, dup=None):
+    """(dup + d d[f] / d fp) * (fp > 0): the gradient w.r.t. the pre-activation of the conv that made fp."""
+    _same_shape(fp, fg, 'lpips_head_backward')
+    n, h, w, c = _dense(fp, 'fp').shape
+    dpre = torch.empty_like(fp)
+    _call('nlt_lpips_head_backward', _ptr(fp), _ptr(_dense(fg, 'fg')), n, h * w, c, _ptr(_dense(lin, 'lin')),
+          _ptr(None if dup is None else _dense(dup, 'dup')), _ptr(dpre))
+    return dpre
+
+
+def lpips_loss(pred, gt, weights, want_grad):
+    """pred, gt [n,h,w,3] in [0,1] (h, w >= 31), weights: the blob of lpips_weights.blob() on the device -> (loss [n], d loss[f] /
+    d pred or None).  One form for both modes: its sums are ordered (csrc/lpips.hip), so `deterministic` has nothing to switch."""
+    _same_shape(pred, gt, 'lpips_loss')
+    if pred.dim() != 4 or pred.shape[3] != 3:
+        raise NLTError("lpips_loss: [n,h,w,3] expected, got %s" % (tuple(pred.shape),))
+    if weights.numel() != lib().nlt_lpips_weights_floats():
+        raise NLTError("lpips_loss: a weights blob of %d floats expected, got %d" % (lib().nlt_lpips_weights_floats(), weights.numel()))
+    n, h, w, _ = pred.shape
+    ws = torch.empty(_size('nlt_lpips_workspace_floats', n, h, w, 1 if want_grad else 0, what='h, w >= 31'),
+                     device=pred.device, dtype=torch.float32)
+    loss = torch.empty(n, device=pred.device, dtype=torch.float32)
+    dunit = torch.empty_like(pred) if want_grad else None
+    _call('nlt_lpips_loss', _ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(_dense(weights, 'weights')), _ptr(ws),
+          ws.numel(), _ptr(loss), _ptr(dunit))
+    return loss, dunit
 
 
 def scale_rows(x, scale):

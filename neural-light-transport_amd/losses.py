@@ -1,8 +1,11 @@
-"""Losses with the reference's call signatures (nlt/losses.py:39-53,75-87,90-118) on HIP kernels
-(csrc/train_ops.hip, csrc/barron.hip, csrc/ssim.hip); torch.autograd.Function is glue only."""
+"""Losses with the reference's call signatures (nlt/losses.py:39-53,75-87,90-118,121-169) on HIP kernels
+(csrc/train_ops.hip, csrc/barron.hip, csrc/ssim.hip, csrc/lpips.hip); torch.autograd.Function is glue only."""
+import os
+
 import torch
 
 from . import _capi as C
+from . import lpips_weights
 
 
 class _L2Fn(torch.autograd.Function):
@@ -34,6 +37,18 @@ class _SSIMFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pred, gt, max_val):
         loss, dunit = C.ssim_loss(pred.contiguous(), gt.contiguous(), max_val, bool(ctx.needs_input_grad[0]))
+        ctx.dunit = dunit
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        return C.scale_rows(ctx.dunit, gloss.contiguous()), None, None
+
+
+class _LPIPSFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, gt, blob):
+        loss, dunit = C.lpips_loss(pred.contiguous(), gt.contiguous(), blob, bool(ctx.needs_input_grad[0]))
         ctx.dunit = dunit
         return loss
 
@@ -125,4 +140,33 @@ class SSIM:
             alpha = torch.as_tensor(weights, dtype=torch.float32, device=pred.device).expand(pred.shape).contiguous()
             gt, pred = _MulFn.apply(gt, alpha), _MulFn.apply(pred, alpha)
         per = _SSIMFn.apply(pred, gt, self.dynamic_range)
+        return per if keep_batch else per.mean()
+
+
+class LPIPS:
+    """LPIPS v0.1 "alex / lin" between gt and pred in [0, 1], [N,H,W,3] (nlt/losses.py:121-169) on csrc/lpips.hip.  `weights`: a
+    path (`.npz` / `.pb`, lpips_weights.load) or the arrays themselves; parsed and validated here, on the host, and uploaded as
+    one packed blob per device on first use.  The `weights=` argument of the call alpha-blends gt and pred against zeros first.
+    per_ch=True (each channel tiled to three and averaged) is never asked for by the model and raises."""
+
+    def __init__(self, weights, per_ch=False):
+        if per_ch:
+            raise NotImplementedError("losses.LPIPS(per_ch=True): the model never passes it (nlt/models/nlt.py:74-75)")
+        self.per_ch = False
+        self.arrays = lpips_weights.load(weights) if isinstance(weights, (str, bytes, os.PathLike)) else lpips_weights.validate(weights)
+        self._blobs = {}
+
+    def blob(self, device):
+        """The packed weights on `device` (uploaded once)."""
+        key = str(torch.device(device))
+        if key not in self._blobs:
+            self._blobs[key] = torch.from_numpy(lpips_weights.blob(self.arrays)).to(device)
+        return self._blobs[key]
+
+    def __call__(self, gt, pred, keep_batch=False, weights=None):
+        assert gt.shape[3] == 3 and pred.shape[3] == 3, "Both ground truth and prediction must be of shape `(N, H, W, 3)`"
+        if weights is not None:
+            alpha = torch.as_tensor(weights, dtype=torch.float32, device=pred.device).expand(pred.shape).contiguous()
+            gt, pred = _MulFn.apply(gt, alpha), _MulFn.apply(pred, alpha)
+        per = _LPIPSFn.apply(pred, gt, self.blob(pred.device))
         return per if keep_batch else per.mean()

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import _capi as C
+from . import losses, lpips_weights
 
 
 DEVICE = 'cuda'
@@ -85,3 +86,25 @@ class SSIM(Base):
 
     def _values(self, im1, im2):
         return C.ssim_values(im1, im2, self.drange).tolist()
+
+
+class LPIPS(SSIM):
+    """xm.metric.LPIPS (metric.py:187-258): LPIPS v0.1 "alex / lin" (lower is better) of im1 / drange and im2 / drange -- the
+    minimum allowed is taken as 0, as there -- on csrc/lpips.hip; one-channel inputs are tripled.  `weight_pb`: the weights file
+    (`.pb` or `.npz`); None takes what NLT_LPIPS_WEIGHTS names (nothing is bundled: lpips_weights.py), else NotImplementedError.
+    Inputs and `.batch` are handled as for metric.SSIM.  Parity-unpinned: no TensorFlow and no real weights file to run against;
+    the semantics are restated in tests/lpips_ref.py."""
+
+    def __init__(self, dtype, weight_pb=None):
+        super().__init__(dtype)
+        path = weight_pb if weight_pb is not None else lpips_weights.configured_path()
+        if path is None:
+            raise NotImplementedError("metric.LPIPS: no weights are bundled; pass weight_pb or set %s" % lpips_weights.ENV)
+        self._loss = losses.LPIPS(path)
+
+    def _values(self, im1, im2):
+        if im1.shape[-1] == 1:
+            im1, im2 = im1.expand(-1, -1, -1, 3).contiguous(), im2.expand(-1, -1, -1, 3).contiguous()
+        if self.drange != 1.:
+            im1, im2 = im1 / self.drange, im2 / self.drange
+        return C.lpips_loss(im1, im2, self._loss.blob(im1.device), False)[0].tolist()

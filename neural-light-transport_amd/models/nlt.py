@@ -13,6 +13,7 @@ import torch
 
 from .. import _capi as C
 from .. import losses
+from .. import lpips_weights
 from .. import metric
 from ..datasets.nlt import ResidentTexels
 from ..engine import RenderPlan
@@ -151,10 +152,16 @@ class Model(BaseModel):
                 # the reference's SSIM.__call__ has no keep_batch and crashes its own train step;
                 # losses.SSIM here takes it (csrc/ssim.hip)
                 loss = losses.SSIM(1 - 0)                       # nlt/models/nlt.py:80-81
-            elif loss_name in ('lpips', 'l1'):
-                # lpips: the frozen AlexNet blob is not part of the reference tree
-                # (.MISSING_LARGE_BLOBS); l1 has no keep_batch and crashes the
-                # reference's own train step
+            elif loss_name == 'lpips':
+                # the network is csrc/lpips.hip; its weights (the frozen AlexNet graph is not part of the reference tree:
+                # .MISSING_LARGE_BLOBS) come from the file `lpips_weights` / NLT_LPIPS_WEIGHTS names, parsed here on the host
+                path = lpips_weights.configured_path(self.config)
+                if path is None:
+                    raise NotImplementedError("lpips: no weights are bundled; set the config key `%s` (or %s) to an .npz / .pb "
+                                              "file of the LPIPS v0.1 alex / lin weights" % (lpips_weights.KEY, lpips_weights.ENV))
+                loss = losses.LPIPS(path, per_ch=False)         # nlt/models/nlt.py:74-75
+            elif loss_name == 'l1':
+                # l1 has no keep_batch and crashes the reference's own train step
                 raise NotImplementedError(loss_name)
             else:
                 raise NotImplementedError(loss_name)
