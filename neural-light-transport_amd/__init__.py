@@ -6,7 +6,13 @@ libnlt_hip.so (include/nlt_hip.h), reached through `_capi`.
 """
 from . import _capi as capi          # noqa: F401
 from . import networks, models, losses, optim, trainvali, nlt_test, metric   # noqa: F401
+from . import nlt_test_main
 from .util import net as netutil     # noqa: F401
+
+# the driver half of the reference's nlt_test.py (nlt_test_main.py), under the names the reference has it: nlt_test.run(...)
+for _name in ('get_config_ini', 'make_datapipe', 'restore_model', 'run', 'parse_args', 'main'):
+    setattr(nlt_test, _name, getattr(nlt_test_main, _name))
+del _name
 
 
 def make_config(**overrides):

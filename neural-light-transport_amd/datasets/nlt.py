@@ -8,6 +8,7 @@ buffers out, bit-identical to `_load_data`'s uint8 -> float64/255 -> float32.
 per-sample PNGs, `uv2cam.npy` fp16 maps, `nn.json`) once into that store."""
 import json
 import re
+import warnings
 from itertools import product
 from os.path import exists, join
 
@@ -140,12 +141,60 @@ class ResidentTexels:
         return self._float
 
 
+def shuffle_order(n, buffer_size, rng):
+    """The order in which `tf.data.Dataset.shuffle(buffer_size)` can emit a stream of n elements, as indices into the stream
+    (nlt/datasets/base.py:109-110): a buffer takes the first `buffer_size` elements; then, until it is empty, one uniformly
+    chosen slot is emitted and refilled with the stream's next element (once the stream has run dry the last slot moves
+    into the hole).  So the element at stream position i never leaves before output position i - buffer_size + 1,
+    buffer_size = 1 is the identity and buffer_size >= n a uniform permutation.  `rng`: a numpy.random.Generator; TF's own
+    random stream is not reproduced, the algorithm's support is."""
+    n, size = int(n), max(1, int(buffer_size))
+    buf = list(range(min(size, n)))
+    nxt, out = len(buf), []
+    while buf:
+        j = int(rng.integers(len(buf)))
+        out.append(buf[j])
+        if nxt < n:
+            buf[j] = nxt
+            nxt += 1
+        else:
+            buf[j] = buf[-1]
+            buf.pop()
+    return out
+
+
+def shard_slice(n, world, rank):
+    """The contiguous slice of a global batch of n frames that `rank` of `world` takes: ceil(n / world) frames per rank, the
+    last ranks short (7 over 4: 2, 2, 2, 1)."""
+    per = -(-n // world)
+    return slice(per * rank, min(per * (rank + 1), n))
+
+
+class Pipeline:
+    """One epoch of batches, the iterable `Dataset.build_pipeline` returns (the `tf.data` pipeline of nlt/datasets/base.py:
+    89-117 scheduled on the host): `id_lists` is fixed when it is built, every iteration loads the batches anew with
+    `Dataset.load_batch`, and `take(n)` keeps the first n items (n < 0: all, as `tf.data.Dataset.take`)."""
+
+    def __init__(self, dataset, id_lists, resident=False):
+        self.dataset, self.id_lists, self.resident = dataset, [list(x) for x in id_lists], resident
+
+    def take(self, n):
+        return Pipeline(self.dataset, self.id_lists if n < 0 else self.id_lists[:n], self.resident)
+
+    def __len__(self):
+        return len(self.id_lists)
+
+    def __iter__(self):
+        for ids in self.id_lists:
+            yield self.dataset.load_batch(ids, resident=self.resident)
+
+
 class Dataset:
     """store: {'ids': [str], 'nn': {id: {'cam','light'}}, 'diffuse','rgb' [F,H,W,3] uint8 CUDA,
     'cvis','lvis' [F,H,W] uint8, 'uv2cam' [F,imh,imw,2] fp16, 'rgb_camspc' [F,imh,imw,3] uint8,
     'complete': [bool]}.  ids follow the reference's '{trainvali|test}_{i:09d}_{cam}_{light}'."""
 
-    def __init__(self, config, mode, store=None, k=1, device='cuda', ring=0):
+    def __init__(self, config, mode, store=None, k=1, device='cuda', ring=0, shuffle_buffer_size=64, nn_cache=True):
         if mode not in ('train', 'vali', 'test'):
             raise ValueError("Invalid mode: {provided}. Allowed modes: {allowed}".format(
                 provided=mode, allowed=('train', 'vali', 'test')))
@@ -164,6 +213,11 @@ class Dataset:
         self.bs = 1 if mode == 'test' else config.getint('DEFAULT', 'bs')     # datasets/base.py
         self.files = self._glob()
         assert self.files, "No files to process into a dataset"           # nlt/datasets/base.py:38
+        self.shuffle_buffer_size = int(shuffle_buffer_size)               # nlt/datasets/base.py:28,33
+        self.seed = int(np.random.SeedSequence().generate_state(1)[0])    # `build_pipeline(seed=None)`: one draw per Dataset
+        # `_nn_indices` per sample id, filled on first use (nn_cache=False: the regex scan over every id of the store for every
+        # sample of every batch, as `_get_nn_id` does it)
+        self._nn_cache = {} if nn_cache else None
 
     TEXEL_KEYS = ('diffuse', 'rgb', 'cvis', 'lvis')
 
@@ -233,6 +287,14 @@ class Dataset:
         raise ValueError("Found {n} matches:\n\t{matches}".format(n=len(matched), matches=matched))
 
     def _nn_indices(self, id_):
+        if self._nn_cache is None:
+            return self._scan_nn_indices(id_)
+        hit = self._nn_cache.get(id_)
+        if hit is None:                                              # (a ValueError of the scan leaves no entry: it is raised again)
+            hit = self._nn_cache[id_] = self._scan_nn_indices(id_)
+        return list(hit)
+
+    def _scan_nn_indices(self, id_):
         nns = self.store['nn'][id_]
         nns = nns if isinstance(nns, (list, tuple)) else [nns]
         out = []
@@ -240,6 +302,32 @@ class Dataset:
             nn_id = self._get_nn_id(nn)
             out.append(-1 if nn_id is None else self.index[nn_id])       # missing neighbour -> zeros (:152-157)
         return out + [-1] * (self.k - len(out))
+
+    def build_pipeline(self, seed=None, no_batch=False, epoch=0, ring=None, resident=False, rank=0, world=1):
+        """nlt/datasets/base.py:89-117 for ONE epoch, as an iterable of the model's 11-tuples (`Pipeline`): the sorted files,
+        in 'train' mode shuffled through tf.data's buffer algorithm (`shuffle_order`, buffer = `shuffle_buffer_size`), cut into
+        batches of `bs` with the short last batch kept (no_batch: batches of one sample, where the reference hands out bare
+        samples).  The order is a function of (seed, epoch) alone -- numpy.random.default_rng([seed, epoch]); seed = None: the
+        seed this Dataset drew when it was made -- so a resumed run replays the epochs it has not done.  There is no map /
+        cache / prefetch stage: `load_batch` gathers a batch out of the resident store when the iterator reaches it.
+        ring: sets the staging ring `load_batch` uses from now on (None: as constructed).  world > 1: every GLOBAL batch is
+        cut into contiguous slices, one per rank (`shard_slice`); a global batch too short to give every rank a frame is
+        dropped on every rank, with one warning (only a short last batch can be)."""
+        files = sorted(self.files)
+        if self.mode == 'train':
+            rng = np.random.default_rng([self.seed if seed is None else int(seed), int(epoch)])
+            files = [files[i] for i in shuffle_order(len(files), self.shuffle_buffer_size, rng)]
+        bs = 1 if no_batch else self.bs
+        id_lists = [files[i:i + bs] for i in range(0, len(files), bs)]
+        if world > 1:
+            kept = [ids for ids in id_lists if len(ids[shard_slice(len(ids), world, world - 1)]) > 0]
+            if len(kept) != len(id_lists):
+                warnings.warn("%d batch(es) too short to give each of %d ranks a frame were dropped on every rank"
+                              % (len(id_lists) - len(kept), world))
+            id_lists = [ids[shard_slice(len(ids), world, rank)] for ids in kept]
+        if ring is not None and int(ring) != self.ring:
+            self.ring, self._slots, self._turn = int(ring), {}, 0
+        return Pipeline(self, id_lists, resident=resident)
 
     def _slot(self, n):
         """The staging buffers the next batch of n samples goes into (None: allocate fresh ones)."""
