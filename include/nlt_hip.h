@@ -1198,6 +1198,34 @@ long nlt_lpips_workspace_floats(int n, int h, int w, int want_grad);
 int nlt_lpips_loss(const float* pred, const float* gt, int n, int h, int w, const float* weights, float* workspace,
                    long workspace_floats, float* loss, float* dunit, void* stream);
 
+/* ======================= Relighting under an environment map (csrc/relight.hip) =======================
+ * A view's one-light-at-a-time (OLAT) renders combined linearly with a lat-long probe's per-light solid-angle integrals.
+ *   replaces: nothing -- the reference has no call site for this step; it is the HDRI relighting of the paper (Zhang et al. 2021,
+ *             "Neural Light Transport for Relighting and View Synthesis", environment-map results), which the released code omits.
+ * Lat-long convention (ours; z-up as in the Blender scenes): pixel (i, j) of envmap [he, we, 3] (float32 linear radiance) looks
+ * along d = (sin t cos p, sin t sin p, cos t) with t = pi (i + 1/2) / he, p = 2 pi (j + 1/2) / we - pi, and covers
+ * dO = sin t * (pi / he) * (2 pi / we).
+ *
+ * out [n_rot, n_lights, 3]: out[r, l, c] = sum of envmap[p, c] * dO(p) over the pixels p whose nearest light under rot[r] is l:
+ * the light with the largest dot product dirs[l] . (rot[r] . d(p)) (float32), ties to the lowest l.  dirs [n_lights, 3] unit
+ * vectors, rot [n_rot, 3, 3] row-major.  Sums in float64 in an order the shapes fix (a row's pixels in order, then the rows in
+ * order), rounded once to float32: no float atomics, equal inputs give equal bits.  workspace:
+ * nlt_envmap_light_weights_workspace_floats() floats, 8-byte aligned, undefined on entry.  n_lights > 1024: NLT_ERR_UNSUPPORTED
+ * (the query answers -1). */
+long nlt_envmap_light_weights_workspace_floats(int he, int we, int n_lights, int n_rot);
+int nlt_envmap_light_weights(const float* envmap, int he, int we, const float* dirs, int n_lights, const float* rot, int n_rot,
+                             float* workspace, long workspace_floats, float* out, void* stream);
+/* acc [n_rot, texels, 3] += sum over the chunk's lights l = l0 .. l0 + n_chunk - 1 of weights[r, l, c] * lin(clip01(pred[l - l0])),
+ * pred [n_chunk, texels, 3], weights [n_rot, n_lights, 3]: per element one fmaf per light in increasing l, starting from the
+ * stored value -- so the result does not depend on how the lights are cut into chunks.  lin: the identity (is_linear) or the
+ * sRGB decode (v / 12.92 below 0.04045, else ((v + 0.055) / 1.055)^2.4).  l0 + n_chunk > n_lights: NLT_ERR_BAD_ARG; an array of
+ * 2^31 or more elements: NLT_ERR_UNSUPPORTED.  16-byte accesses when texels % 4 == 0 and pred, acc are 16-byte aligned. */
+int nlt_relight_accumulate(const float* pred, int n_chunk, long texels, const float* weights, int n_rot, int n_lights, int l0,
+                           int is_linear, float* acc, void* stream);
+/* out [n_rot, texels, 3] = enc(clip01(exposure * acc)); enc: the sRGB encode (12.92 v up to 0.0031308, else
+ * 1.055 v^(1/2.4) - 0.055) when to_srgb, else the identity.  out is a buffer of its own. */
+int nlt_relight_finish(const float* acc, int n_rot, long texels, float exposure, int to_srgb, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -213,6 +213,11 @@ SIGNATURES = {
     'nlt_conv_k3_backward_data': (_c_int, [_c_int, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp]),
     'nlt_conv_k3_wgrad_workspace_floats': (_c_long, [_c_int] * 6),
     'nlt_conv_k3_backward_weights': (_c_int, [_c_int, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _vp, _vp, _c_long, _vp]),
+    # relighting under an environment map (csrc/relight.hip)
+    'nlt_envmap_light_weights_workspace_floats': (_c_long, [_c_int] * 4),
+    'nlt_envmap_light_weights': (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _c_long, _vp, _vp]),
+    'nlt_relight_accumulate': (_c_int, [_vp, _c_int, _c_long, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    'nlt_relight_finish': (_c_int, [_vp, _c_int, _c_long, _c_float, _c_int, _vp, _vp]),
 }
 
 _real = None
@@ -1021,6 +1026,47 @@ def lpips_loss(pred, gt, weights, want_grad):
     _call('nlt_lpips_loss', _ptr(_dense(pred, 'pred')), _ptr(_dense(gt, 'gt')), n, h, w, _ptr(_dense(weights, 'weights')), _ptr(ws),
           ws.numel(), _ptr(loss), _ptr(dunit))
     return loss, dunit
+
+
+# ---------------------------------------------------------------- relighting under an environment map (csrc/relight.hip)
+def envmap_light_weights(envmap, dirs, rot):
+    """envmap [he,we,3] (linear radiance, lat-long, z-up: include/nlt_hip.h), dirs [L,3] unit vectors, rot [R,3,3] -> [R,L,3]:
+    per rotation and light the probe's solid-angle integral over the pixels nearest that light.  Ordered float64 sums."""
+    if envmap.dim() != 3 or envmap.shape[2] != 3 or dirs.dim() != 2 or dirs.shape[1] != 3 or rot.dim() != 3 or tuple(rot.shape[1:]) != (3, 3):
+        raise NLTError("envmap_light_weights: envmap [he,we,3], dirs [L,3], rot [R,3,3] expected, got %s, %s, %s"
+                       % (tuple(envmap.shape), tuple(dirs.shape), tuple(rot.shape)))
+    he, we, n_lights, n_rot = envmap.shape[0], envmap.shape[1], dirs.shape[0], rot.shape[0]
+    need = _size('nlt_envmap_light_weights_workspace_floats', he, we, n_lights, n_rot, what='at most 1024 lights')
+    ws = _workspace(_per_stream('envmap_weights'), envmap.device, need)
+    out = torch.empty((n_rot, n_lights, 3), device=envmap.device, dtype=torch.float32)
+    _call('nlt_envmap_light_weights', _ptr(_dense(envmap, 'envmap')), he, we, _ptr(_dense(dirs, 'dirs')), n_lights,
+          _ptr(_dense(rot, 'rot')), n_rot, _ptr(ws), ws.numel(), _ptr(out))
+    return out
+
+
+def relight_accumulate(pred, weights, l0, acc, is_linear):
+    """acc [R,texels,3] += sum_l weights[:, l0 + l] * lin(clip01(pred[l])) over the chunk pred [Lc,...,3] (any texel shape), one
+    fmaf per light in light order; weights [R,L,3].  In place; returns acc."""
+    if pred.dim() < 2 or pred.shape[-1] != 3 or weights.dim() != 3 or weights.shape[2] != 3 or acc.dim() < 2 or acc.shape[-1] != 3:
+        raise NLTError("relight_accumulate: pred [Lc,...,3], weights [R,L,3], acc [R,...,3] expected, got %s, %s, %s"
+                       % (tuple(pred.shape), tuple(weights.shape), tuple(acc.shape)))
+    n_chunk, n_rot, n_lights = pred.shape[0], weights.shape[0], weights.shape[1]
+    texels = pred[0].numel() // 3
+    if acc.shape[0] != n_rot or acc[0].numel() != texels * 3:
+        raise NLTError("relight_accumulate: acc %s does not match %d rotations of %d texels" % (tuple(acc.shape), n_rot, texels))
+    _call('nlt_relight_accumulate', _ptr(_dense(pred, 'pred')), n_chunk, texels, _ptr(_dense(weights, 'weights')), n_rot, n_lights,
+          int(l0), 1 if is_linear else 0, _ptr(_dense(acc, 'acc')))
+    return acc
+
+
+def relight_finish(acc, exposure, to_srgb):
+    """enc(clip01(exposure * acc)) as a new tensor of acc's shape [R,...,3]; enc: sRGB encode (to_srgb) or the identity."""
+    if acc.dim() < 2 or acc.shape[-1] != 3:
+        raise NLTError("relight_finish: acc [R,...,3] expected, got %s" % (tuple(acc.shape),))
+    out = torch.empty_like(acc)
+    _call('nlt_relight_finish', _ptr(_dense(acc, 'acc')), acc.shape[0], acc[0].numel() // 3, float(exposure), 1 if to_srgb else 0,
+          _ptr(out))
+    return out
 
 
 def scale_rows(x, scale):
