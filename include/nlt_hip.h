@@ -1226,6 +1226,57 @@ int nlt_relight_accumulate(const float* pred, int n_chunk, long texels, const fl
  * 1.055 v^(1/2.4) - 0.055) when to_srgb, else the identity.  out is a buffer of its own. */
 int nlt_relight_finish(const float* acc, int n_rot, long texels, float exposure, int to_srgb, float* out, void* stream);
 
+/* ======================= Mesh ray casting (csrc/raycast.hip) =======================
+ * First-hit rays against a triangle mesh, in float64, deterministic (no atomics): the geometry behind the dense `intersect` of
+ * data_gen/render.py for a camera and a light that are not in the capture.
+ *   replaces: xm.blender.camera.backproject_to_3d (third_party/xiuminglib/xiuminglib/blender/camera.py:512-654) and the shadow
+ *             rays of calc_light_cosines (data_gen/render.py:238-254), Python loops over a mathutils BVH inside Blender.
+ * The hit test (two-sided Moeller-Trumbore, no fused operations; tests/raycast_ref.py restates it operation by operation):
+ *   e1 = v1 - v0, e2 = v2 - v0, p = d x e2, det = e1 . p; miss unless det is finite and non-zero; inv = 1 / det, s = o - v0,
+ *   u = (s . p) * inv, miss if u < 0 or u > 1; q = s x e1, v = (d . q) * inv, miss if v < 0 or u + v > 1; t = (e2 . q) * inv, hit
+ *   iff t >= 0.  a . b = (ax bx + ay by) + az bz.  Closest hit = smallest t, equal t to the lower triangle index (the caller's
+ *   numbering).  loc = o + t d; normal = (e1 x e2) / |e1 x e2|, the geometric normal, not flipped towards the ray.  A triangle
+ *   whose e1 x e2 is the zero vector or not finite is degenerate and never hit.  Not watertight: a ray aimed exactly at a shared
+ *   edge may miss both triangles.  The box test of the traversal is conservative up to the conditioning stated in the source.
+ *
+ * The hierarchy, two float64 device buffers the caller allocates (8-byte aligned; every element is written by nlt_bvh_build):
+ *   tris  [Lp * 4][10], nlt_bvh_tris_doubles(n_tris) doubles: per slot v0, e1, e2 and the triangle's index as a double (-1: an
+ *         empty slot, the other nine are 0).  L = ceil(n_tris / 4) leaves of 4 slots, Lp = L rounded up to a power of two.
+ *   nodes [2 Lp - 1][6], nlt_bvh_nodes_doubles(n_tris) doubles: box lo, hi of a complete binary tree, children of node i at
+ *         2i + 1 and 2i + 2, leaf j at node Lp - 1 + j; lo = (1,1,1), hi = (-1,-1,-1) marks a node with nothing to hit.
+ * Limits: n_tris, n_rays, n_pixels <= 0: NLT_ERR_BAD_ARG; 2^31 or more (or 3 n_rays >= 2^31): NLT_ERR_UNSUPPORTED; the size
+ * queries answer -1 for both.  Any ray count works (the last workgroup is partial).  Nothing is launched after a refusal.
+ *
+ * Step 1: codes [n_tris] int32 = 30-bit Morton codes (10 bits per axis, x highest) of the centroids ((v0 + v1) + v2) / 3 of
+ * tri_verts [n_tris, 3, 3] in the box lo .. hi.  Step 2 is the caller's: order = the indices of a STABLE ascending sort of the
+ * codes, int32 [n_tris] (a permutation of 0 .. n_tris - 1; it is trusted).  Step 3: nlt_bvh_build fills both buffers (one
+ * launch for the leaves, one per level above them).  tris_doubles / nodes_doubles are the capacities: smaller than the queries
+ * answer is NLT_ERR_BAD_ARG. */
+long nlt_bvh_tris_doubles(long n_tris);
+long nlt_bvh_nodes_doubles(long n_tris);
+int nlt_bvh_morton(const double* tri_verts, long n_tris, double lox, double loy, double loz, double hix, double hiy, double hiz,
+                   int* codes, void* stream);
+int nlt_bvh_build(const double* tri_verts, const int* order, long n_tris, double* tris, long tris_doubles, double* nodes,
+                  long nodes_doubles, void* stream);
+/* origins, dirs [n_rays, 3] float64, directions used as given -> t [n_rays] float64 (+inf: a miss), tri [n_rays] int32 (the
+ * caller's triangle index, -1: a miss), face [n_rays] int32 = tri2face[tri] (tri2face int32 [n_tris] or NULL: face = tri; -1: a
+ * miss).  tris / nodes: a hierarchy nlt_bvh_build made for n_tris triangles; read-only here and below. */
+int nlt_raycast(const double* tris, const double* nodes, long n_tris, const int* tri2face, const double* origins, const double* dirs,
+                long n_rays, double* t, int* tri, int* face, void* stream);
+/* One ray per pixel (x, y) of an imh x imw image, row-major (pixel x + imw y), generated as backproject_to_3d does:
+ * ray_to = from_homo(Minv . (x, y, 1, 1)) (each row summed left to right, then divided by w), dir = (ray_to - cam) / |ray_to - cam|
+ * (a division per component), origin = cam.  cam_host: 19 doubles in HOST memory, read before the call returns: Minv row-major
+ * (the inverse of the 4 x 4 world -> pixel matrix), then the camera location.  Outputs, the dense intersect of
+ * data_gen/render.py: locs, normals [imh imw, 3] float64 (zeros where nothing is hit), valid [imh imw] uint8, face_i [imh imw]
+ * int32 (tri2face[tri], -1 where nothing is hit). */
+int nlt_raycast_camera(const double* tris, const double* nodes, long n_tris, const int* tri2face, const double* cam_host, int imh,
+                       int imw, double* locs, double* normals, unsigned char* valid, int* face_i, void* stream);
+/* Cast shadows (data_gen/render.py:238-254): for every pixel with valid != 0 the closest hit of the ray from the light (lx, ly, lz)
+ * towards locs[pixel], direction normalised as above, full = |loc - light|.  No hit: not occluded; else
+ * occluded = !(|t - full| <= 1e-8 + 1e-5 |full|) (np.isclose's defaults).  occluded [n_pixels] uint8; 0 where valid == 0. */
+int nlt_raycast_shadow(const double* tris, const double* nodes, long n_tris, const double* locs, const unsigned char* valid,
+                       long n_pixels, double lx, double ly, double lz, unsigned char* occluded, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

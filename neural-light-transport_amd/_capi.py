@@ -218,6 +218,14 @@ SIGNATURES = {
     'nlt_envmap_light_weights': (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _vp, _c_int, _vp, _c_long, _vp, _vp]),
     'nlt_relight_accumulate': (_c_int, [_vp, _c_int, _c_long, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     'nlt_relight_finish': (_c_int, [_vp, _c_int, _c_long, _c_float, _c_int, _vp, _vp]),
+    # mesh ray casting (csrc/raycast.hip)
+    'nlt_bvh_tris_doubles': (_c_long, [_c_long]),
+    'nlt_bvh_nodes_doubles': (_c_long, [_c_long]),
+    'nlt_bvh_morton': (_c_int, [_vp, _c_long] + [_c_double] * 6 + [_vp, _vp]),
+    'nlt_bvh_build': (_c_int, [_vp, _vp, _c_long, _vp, _c_long, _vp, _c_long, _vp]),
+    'nlt_raycast': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp]),
+    'nlt_raycast_camera': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
+    'nlt_raycast_shadow': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_long] + [_c_double] * 3 + [_vp, _vp]),
 }
 
 _real = None
@@ -1632,6 +1640,76 @@ def back_backward(x, fm1, u, v, dpred, n, h2, w2, w_s2, w_s1, w_head, alpha, dx,
     wts = [_ptr(_dense(t, 'weight')) for t in (w_s2, w_s1, w_head)]
     outs = [_ptr(_dense(t, 'grad')) for t in (dx, dfm1, dw_s2, db_s2, dw_s1, db_s1, dw_head, db_head)]
     _call('nlt_back_backward', *ins, n, h2, w2, *wts, float(alpha), *outs, _ptr(ws))
+
+
+# ---------------------------------------------------------------- mesh ray casting (csrc/raycast.hip)
+def bvh_build(tri_verts, lo, hi):
+    """tri_verts [T,3,3] float64, lo / hi the mesh's box (3 numbers each) -> (tris, nodes): the two float64 hierarchy buffers
+    of include/nlt_hip.h, exactly the queried sizes.  Morton codes on the device, a stable torch.sort, then the build."""
+    if tri_verts.dim() != 3 or tuple(tri_verts.shape[1:]) != (3, 3):
+        raise NLTError("bvh_build: tri_verts [T,3,3] expected, got %s" % (tuple(tri_verts.shape),))
+    n, dev = tri_verts.shape[0], tri_verts.device
+    n_tris_d = _size('nlt_bvh_tris_doubles', n, what='1 .. 2^31 - 1 triangles')
+    n_nodes_d = _size('nlt_bvh_nodes_doubles', n)
+    tv = _tptr(tri_verts, torch.float64, 'tri_verts')
+    codes = torch.empty(n, device=dev, dtype=torch.int32)
+    _call('nlt_bvh_morton', tv, n, *(float(x) for x in lo), *(float(x) for x in hi), codes.data_ptr())
+    order = torch.sort(codes, stable=True).indices.to(torch.int32)
+    tris = torch.empty(n_tris_d, device=dev, dtype=torch.float64)
+    nodes = torch.empty(n_nodes_d, device=dev, dtype=torch.float64)
+    _call('nlt_bvh_build', tv, _tptr(order, torch.int32, 'order'), n, tris.data_ptr(), tris.numel(), nodes.data_ptr(), nodes.numel())
+    return tris, nodes
+
+
+def _bvh_args(tris, nodes, n_tris, tri2face):
+    if tri2face is not None and tri2face.numel() != n_tris:
+        raise NLTError("tri2face has %d entries for %d triangles" % (tri2face.numel(), n_tris))
+    if tris.numel() != _size('nlt_bvh_tris_doubles', n_tris) or nodes.numel() != _size('nlt_bvh_nodes_doubles', n_tris):
+        raise NLTError("the hierarchy buffers were not built for %d triangles" % n_tris)
+    return _tptr(tris, torch.float64, 'tris'), _tptr(nodes, torch.float64, 'nodes'), n_tris
+
+
+def raycast(tris, nodes, n_tris, tri2face, origins, dirs):
+    """origins, dirs [R,3] float64 (directions as given) -> (t float64 [R], +inf = miss; tri int32 [R]; face int32 [R])."""
+    if origins.dim() != 2 or origins.shape[1] != 3 or origins.shape != dirs.shape:
+        raise NLTError("raycast: origins and dirs [R,3] expected, got %s, %s" % (tuple(origins.shape), tuple(dirs.shape)))
+    r, dev = origins.shape[0], origins.device
+    t = torch.empty(r, device=dev, dtype=torch.float64)
+    tri = torch.empty(r, device=dev, dtype=torch.int32)
+    face = torch.empty(r, device=dev, dtype=torch.int32)
+    _call('nlt_raycast', *_bvh_args(tris, nodes, n_tris, tri2face), _tptr(tri2face, torch.int32, 'tri2face'),
+          _tptr(origins, torch.float64, 'origins'), _tptr(dirs, torch.float64, 'dirs'), r, t.data_ptr(), tri.data_ptr(), face.data_ptr())
+    return t, tri, face
+
+
+def raycast_camera(tris, nodes, n_tris, tri2face, cam_mat_inv, cam_loc, imh, imw):
+    """cam_mat_inv: the 16 numbers of the inverse world -> pixel matrix, row-major; cam_loc: 3 numbers ->
+    (locs, normals float64 [imh*imw,3], valid uint8 [imh*imw], face_i int32 [imh*imw]), row-major pixels."""
+    vals = [float(x) for x in cam_mat_inv] + [float(x) for x in cam_loc]
+    if len(vals) != 19:
+        raise NLTError("raycast_camera: 16 matrix entries and 3 coordinates expected")
+    if getattr(_tls, 'tape', None) is not None:
+        raise NLTError("raycast_camera reads its camera from host memory during the call: it cannot be recorded on a launch tape")
+    host = (_c_double * 19)(*vals)
+    dev, p = tris.device, int(imh) * int(imw)
+    locs = torch.empty((p, 3), device=dev, dtype=torch.float64)
+    normals = torch.empty((p, 3), device=dev, dtype=torch.float64)
+    valid = torch.empty(p, device=dev, dtype=torch.uint8)
+    face_i = torch.empty(p, device=dev, dtype=torch.int32)
+    _call('nlt_raycast_camera', *_bvh_args(tris, nodes, n_tris, tri2face), _tptr(tri2face, torch.int32, 'tri2face'),
+          ctypes.addressof(host), int(imh), int(imw), locs.data_ptr(), normals.data_ptr(), valid.data_ptr(), face_i.data_ptr())
+    return locs, normals, valid, face_i
+
+
+def raycast_shadow(tris, nodes, n_tris, locs, valid, light_loc):
+    """locs [P,3] float64, valid [P] uint8, light_loc 3 numbers -> occluded uint8 [P] (data_gen/render.py:238-254)."""
+    p = valid.numel()
+    if locs.numel() != 3 * p:
+        raise NLTError("raycast_shadow: locs %s does not match %d pixels" % (tuple(locs.shape), p))
+    occluded = torch.empty(p, device=valid.device, dtype=torch.uint8)
+    _call('nlt_raycast_shadow', *_bvh_args(tris, nodes, n_tris, None), _tptr(locs, torch.float64, 'locs'),
+          _tptr(valid, torch.uint8, 'valid'), p, *(float(x) for x in light_loc), occluded.data_ptr())
+    return occluded
 
 
 # ---------------------------------------------------------------- texel-buffer assembly

@@ -1,0 +1,433 @@
+// Mesh ray casting: first-hit rays per camera pixel and shadow rays per hit pixel, the geometry step that feeds
+// data_gen/render.py's dense `intersect` without Blender.
+//   replaces: xm.blender.camera.backproject_to_3d (third_party/xiuminglib/xiuminglib/blender/camera.py:512-654) and the
+//             shadow-ray loop of calc_light_cosines (data_gen/render.py:238-254), both Python loops over a mathutils BVH.
+// Built with -ffp-contract=off (csrc/Makefile): results are compared bit for bit with NumPy (tests/raycast_ref.py).
+//
+// THE DEFINITION OF A HIT (one device function, `hit_triangle`; float64, two-sided Moeller-Trumbore, no fused operations):
+//   e1 = v1 - v0, e2 = v2 - v0, p = d x e2, det = e1 . p;        miss unless det is finite and non-zero
+//   inv = 1 / det, s = o - v0, u = (s . p) * inv;                miss if u < 0 or u > 1
+//   q = s x e1, v = (d . q) * inv;                               miss if v < 0 or u + v > 1
+//   t = (e2 . q) * inv;                                          hit iff t >= 0
+// a . b = (ax*bx + ay*by) + az*bz; (a x b) = (ay*bz - az*by, az*bx - ax*bz, ax*by - ay*bx).  The closest hit is the smallest t,
+// equal t goes to the lower ORIGINAL triangle index.  loc = o + t*d (a multiply, then an add); normal = (e1 x e2) / |e1 x e2|
+// (component-wise division by sqrt((nx*nx + ny*ny) + nz*nz)): the geometric normal, not flipped towards the ray.
+// A triangle whose e1 x e2 is the zero vector or not finite is DEGENERATE: it is never hit, it is left out of every box, and its
+// NaNs reach nothing.  The test is not watertight: a ray aimed exactly at a shared edge can miss both triangles.
+//
+// THE HIERARCHY (two float64 buffers, sizes from nlt_bvh_tris_doubles / nlt_bvh_nodes_doubles; T triangles):
+//   L  = ceil(T / 4) leaves of kLeaf = 4 slots, padded to Lp = the next power of two; depth D = log2(Lp).
+//   tris  [Lp * 4][10]: v0 (3), e1 (3), e2 (3), original triangle index as a double (-1: empty slot -- padding or a degenerate
+//         triangle; its nine other doubles are 0).  Slot s < T holds triangle order[s] (the caller's stable sort of the 30-bit
+//         Morton codes of nlt_bvh_morton).
+//   nodes [2 * Lp - 1][6]: box lo (3), hi (3) of a complete binary tree, children of node i at 2i + 1 and 2i + 2, leaf j at node
+//         Lp - 1 + j.  A node without a hittable triangle has lo = (1,1,1), hi = (-1,-1,-1) (lo.x > hi.x marks "empty").
+//   Boxes come level by level from the leaves up, one launch per level: no atomics, no spinning, equal inputs give equal bits.
+//
+// THE TRAVERSAL: one ray per lane, near child first, the far child on a per-lane stack in LDS ((D + 1) ints per lane, sized at
+// launch from D; entry k of lane l at [k * 64 + l], so a wave's pushes and pops hit 64 different banks).  A node is pruned only
+// when its entry distance is STRICTLY greater than the best t, so an equal-t, lower-index triangle is still reached.
+// The box test is conservative.  Per axis the slab [lo - m, hi + m] is used with m = kBoxUlps ulps of max(|lo|, |hi|, |o|) plus
+// the smallest normal double (so lo - m < o < hi + m strictly when o lies in a zero-thickness slab or on a box face, also at 0),
+// t1 = (lo - m - o) * (1/d), t2 = (hi + m - o) * (1/d).  A direction component that is +0, -0 or so small that 1/d overflows gives
+// t1, t2 = -inf / +inf in some order when o is strictly inside the widened slab (no constraint) and two infinities of one sign
+// when it is outside (a miss: such a ray never enters the slab); 0 * inf cannot occur strictly inside.  NaNs are dropped by
+// fmin / fmax, which is the accepting direction.  The interval ends are then moved outward by kSlabUlps ulps.
+// Why these numbers suffice: t1 and t2 carry three roundings each (the subtraction, the reciprocal, the product), a relative
+// error below 2 ulps, so 4 ulps outward make the interval contain every exact parameter of a point of the widened box.  The
+// widening m covers what the triangle test itself may accept outside the exact triangle: u, v and t come from about a dozen
+// rounded operations on coordinate differences, so for a triangle that is not a sliver seen edge-on (|e1||e2||d| / |det| up
+// to ~4) an accepted point lies within a few tens of ulps of the largest coordinate involved (a vertex or the origin); 256 is
+// that with margin.  For worse-conditioned slivers the bound grows with the condition number and is not claimed.
+// Every store is a plain vector store.
+#include <math.h>
+#include <stdint.h>
+
+#include "nlt_common.h"
+
+namespace {
+
+constexpr int kThreads = 64;                    // one wave per workgroup: no barriers, the LDS stack is per lane
+constexpr int kLeaf = 4;
+constexpr int kTriDoubles = 10;
+constexpr double kBoxUlps = 256.0 * 2.220446049250313e-16;
+constexpr double kSlabUlps = 4.0 * 2.220446049250313e-16;
+constexpr double kTiny = 2.2250738585072014e-308;
+
+struct V3 { double x, y, z; };
+
+__device__ __forceinline__ V3 sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ double dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 load3(const double* p) { return {p[0], p[1], p[2]}; }
+__device__ __forceinline__ void store3(double* p, V3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+__device__ __forceinline__ bool finite3(V3 a) { return isfinite(a.x) && isfinite(a.y) && isfinite(a.z); }
+
+// the definition of a hit (file header)
+__device__ __forceinline__ bool hit_triangle(V3 o, V3 d, V3 v0, V3 e1, V3 e2, double& t_out) {
+  const V3 p = cross(d, e2);
+  const double det = dot(e1, p);
+  if (!isfinite(det) || det == 0.0) return false;
+  const double inv = 1.0 / det;
+  const V3 s = sub(o, v0);
+  const double u = dot(s, p) * inv;
+  if (!(u >= 0.0 && u <= 1.0)) return false;
+  const V3 q = cross(s, e1);
+  const double v = dot(d, q) * inv;
+  if (!(v >= 0.0 && u + v <= 1.0)) return false;
+  const double t = dot(e2, q) * inv;
+  if (!(t >= 0.0)) return false;
+  t_out = t;
+  return true;
+}
+
+__device__ __forceinline__ bool degenerate(V3 e1, V3 e2) {
+  const V3 n = cross(e1, e2);
+  return !finite3(n) || (n.x == 0.0 && n.y == 0.0 && n.z == 0.0);
+}
+
+// dir = (to - from) / |to - from|, a division per component
+__device__ __forceinline__ V3 unit_towards(V3 from, V3 to, double& len) {
+  const V3 w = sub(to, from);
+  len = sqrt(dot(w, w));
+  return {w.x / len, w.y / len, w.z / len};
+}
+
+// ---------------------------------------------------------------- build
+__device__ __forceinline__ unsigned spread10(unsigned v) {
+  v = (v | (v << 16)) & 0x030000FFu;
+  v = (v | (v << 8)) & 0x0300F00Fu;
+  v = (v | (v << 4)) & 0x030C30C3u;
+  v = (v | (v << 2)) & 0x09249249u;
+  return v;
+}
+
+__device__ __forceinline__ unsigned quant10(double c, double lo, double hi) {
+  const double x = (c - lo) / (hi - lo) * 1024.0;
+  if (!(x > 0.0)) return 0u;                        // (NaN, a zero extent, below the box)
+  return x >= 1023.0 ? 1023u : (unsigned)x;
+}
+
+__global__ __launch_bounds__(256) void morton_kernel(const double* __restrict__ tv, int n, V3 lo, V3 hi, int* __restrict__ codes) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double* p = tv + (long)i * 9;
+  const double cx = ((p[0] + p[3]) + p[6]) / 3.0, cy = ((p[1] + p[4]) + p[7]) / 3.0, cz = ((p[2] + p[5]) + p[8]) / 3.0;
+  codes[i] = (int)((spread10(quant10(cx, lo.x, hi.x)) << 2) | (spread10(quant10(cy, lo.y, hi.y)) << 1) |
+                   spread10(quant10(cz, lo.z, hi.z)));
+}
+
+// one thread per leaf: its four slots of `tris`, then its box
+__global__ __launch_bounds__(256) void leaves_kernel(const double* __restrict__ tv, const int* __restrict__ order, int n, int lp,
+                                                     double* __restrict__ tris, double* __restrict__ nodes) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= lp) return;
+  V3 lo = {1.0, 1.0, 1.0}, hi = {-1.0, -1.0, -1.0};
+  bool any = false;
+  for (int k = 0; k < kLeaf; ++k) {
+    const long s = (long)j * kLeaf + k;
+    double* out = tris + s * kTriDoubles;
+    bool keep = false;
+    if (s < n) {
+      const int i = order[s];
+      const double* p = tv + (long)i * 9;
+      const V3 v0 = load3(p), v1 = load3(p + 3), v2 = load3(p + 6);
+      const V3 e1 = sub(v1, v0), e2 = sub(v2, v0);
+      if (finite3(v0) && !degenerate(e1, e2)) {
+        keep = true;
+        store3(out, v0); store3(out + 3, e1); store3(out + 6, e2);
+        out[9] = (double)i;
+        const V3 tlo = {fmin(v0.x, fmin(v1.x, v2.x)), fmin(v0.y, fmin(v1.y, v2.y)), fmin(v0.z, fmin(v1.z, v2.z))};
+        const V3 thi = {fmax(v0.x, fmax(v1.x, v2.x)), fmax(v0.y, fmax(v1.y, v2.y)), fmax(v0.z, fmax(v1.z, v2.z))};
+        lo = any ? V3{fmin(lo.x, tlo.x), fmin(lo.y, tlo.y), fmin(lo.z, tlo.z)} : tlo;
+        hi = any ? V3{fmax(hi.x, thi.x), fmax(hi.y, thi.y), fmax(hi.z, thi.z)} : thi;
+        any = true;
+      }
+    }
+    if (!keep) {
+      for (int c = 0; c < 9; ++c) out[c] = 0.0;
+      out[9] = -1.0;
+    }
+  }
+  double* b = nodes + ((long)lp - 1 + j) * 6;
+  store3(b, lo); store3(b + 3, hi);
+}
+
+// one thread per node of the level that starts at node `first` and has `count` nodes
+__global__ __launch_bounds__(256) void level_kernel(double* __restrict__ nodes, int first, int count) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k >= count) return;
+  const long i = (long)first + k;
+  const double* a = nodes + (2 * i + 1) * 6;
+  const double* b = a + 6;
+  const V3 alo = load3(a), ahi = load3(a + 3), blo = load3(b), bhi = load3(b + 3);
+  const bool ea = alo.x > ahi.x, eb = blo.x > bhi.x;
+  V3 lo, hi;
+  if (ea) { lo = blo; hi = bhi; }
+  else if (eb) { lo = alo; hi = ahi; }
+  else {
+    lo = {fmin(alo.x, blo.x), fmin(alo.y, blo.y), fmin(alo.z, blo.z)};
+    hi = {fmax(ahi.x, bhi.x), fmax(ahi.y, bhi.y), fmax(ahi.z, bhi.z)};
+  }
+  store3(nodes + i * 6, lo); store3(nodes + i * 6 + 3, hi);
+}
+
+// ---------------------------------------------------------------- traversal
+struct Ray {
+  V3 o, d, inv;
+};
+
+__device__ __forceinline__ void slab(double lo, double hi, double o, double inv, double& tn, double& tf) {
+  const double m = fmax(fmax(fabs(lo), fabs(hi)), fabs(o)) * kBoxUlps + kTiny;
+  const double t1 = ((lo - m) - o) * inv, t2 = ((hi + m) - o) * inv;
+  tn = fmax(tn, fmin(t1, t2));
+  tf = fmin(tf, fmax(t1, t2));
+}
+
+// Entry distance of the ray into the widened box, moved outward; false when the ray misses it.  (box: lo[3], hi[3])
+__device__ __forceinline__ bool hit_box(const Ray& r, const double* __restrict__ box, double& enter) {
+  const double lox = box[0], hix = box[3];
+  if (lox > hix) return false;                      // an empty node
+  double tn = -INFINITY, tf = INFINITY;
+  slab(lox, hix, r.o.x, r.inv.x, tn, tf);
+  slab(box[1], box[4], r.o.y, r.inv.y, tn, tf);
+  slab(box[2], box[5], r.o.z, r.inv.z, tn, tf);
+  tn -= fabs(tn) * kSlabUlps;
+  tf += fabs(tf) * kSlabUlps;
+  enter = tn;
+  return !(tn > tf) && !(tf < 0.0);
+}
+
+struct Hit {
+  double t;
+  int tri;        // original index, -1: none
+  long slot;      // where its (v0, e1, e2) lies in `tris`
+};
+
+__device__ __forceinline__ Hit closest_hit(V3 o, V3 d, const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
+                                           int* __restrict__ stack /* this lane's entry 0; entries kThreads ints apart */) {
+  Ray r;
+  r.o = o; r.d = d;
+  r.inv = {1.0 / d.x, 1.0 / d.y, 1.0 / d.z};
+  Hit best = {INFINITY, -1, 0};
+  double enter;
+  if (!hit_box(r, nodes, enter)) return best;
+  int sp = 0;
+  int node = 0;
+  const int first_leaf = lp - 1;
+  while (true) {
+    if (node >= first_leaf) {
+      const long s0 = (long)(node - first_leaf) * kLeaf;
+      for (int k = 0; k < kLeaf; ++k) {
+        const double* p = tris + (s0 + k) * kTriDoubles;
+        const int idx = (int)p[9];
+        if (idx < 0) continue;
+        double t;
+        if (hit_triangle(o, d, load3(p), load3(p + 3), load3(p + 6), t) && (t < best.t || (t == best.t && idx < best.tri))) {
+          best.t = t; best.tri = idx; best.slot = s0 + k;
+        }
+      }
+      node = -1;
+    } else {
+      const int c0 = 2 * node + 1;
+      double ea, eb;
+      const bool ha = hit_box(r, nodes + (long)c0 * 6, ea) && !(ea > best.t);
+      const bool hb = hit_box(r, nodes + (long)c0 * 6 + 6, eb) && !(eb > best.t);
+      if (ha && hb) {
+        const bool a_first = !(eb < ea);
+        stack[sp * kThreads] = a_first ? c0 + 1 : c0;
+        ++sp;
+        node = a_first ? c0 : c0 + 1;
+      } else if (ha) node = c0;
+      else if (hb) node = c0 + 1;
+      else node = -1;
+    }
+    while (node < 0) {
+      if (sp == 0) return best;
+      --sp;
+      const int cand = stack[sp * kThreads];
+      // its entry distance again (cheaper than a second LDS word per entry): prune only when strictly beyond the best t
+      double e;
+      if (hit_box(r, nodes + (long)cand * 6, e) && !(e > best.t)) node = cand;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void raycast_kernel(const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
+                                                           const int* __restrict__ tri2face, const double* __restrict__ origins,
+                                                           const double* __restrict__ dirs, int n, double* __restrict__ t_out,
+                                                           int* __restrict__ tri_out, int* __restrict__ face_out) {
+  extern __shared__ int s_stack[];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const Hit h = closest_hit(load3(origins + (long)i * 3), load3(dirs + (long)i * 3), tris, nodes, lp, s_stack + threadIdx.x);
+  t_out[i] = h.t;
+  tri_out[i] = h.tri;
+  face_out[i] = h.tri < 0 ? -1 : (tri2face ? tri2face[h.tri] : h.tri);
+}
+
+struct Camera {
+  double m[16];   // inverse of the 4 x 4 pixel <- world matrix, row-major
+  V3 loc;
+};
+
+__global__ __launch_bounds__(kThreads) void camera_kernel(const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
+                                                          const int* __restrict__ tri2face, Camera cam, int imw, int n,
+                                                          double* __restrict__ locs, double* __restrict__ normals,
+                                                          unsigned char* __restrict__ valid, int* __restrict__ face_i) {
+  extern __shared__ int s_stack[];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const double x = (double)(i % imw), y = (double)(i / imw);
+  const double* m = cam.m;
+  // M^-1 . (x, y, 1, 1), each row summed left to right; then from_homo
+  const double hx = ((m[0] * x + m[1] * y) + m[2]) + m[3], hy = ((m[4] * x + m[5] * y) + m[6]) + m[7];
+  const double hz = ((m[8] * x + m[9] * y) + m[10]) + m[11], hw = ((m[12] * x + m[13] * y) + m[14]) + m[15];
+  const V3 to = {hx / hw, hy / hw, hz / hw};
+  double len;
+  const V3 d = unit_towards(cam.loc, to, len);
+  const Hit h = closest_hit(cam.loc, d, tris, nodes, lp, s_stack + threadIdx.x);
+  V3 loc = {0.0, 0.0, 0.0}, nrm = {0.0, 0.0, 0.0};
+  if (h.tri >= 0) {
+    loc = {cam.loc.x + h.t * d.x, cam.loc.y + h.t * d.y, cam.loc.z + h.t * d.z};
+    const double* p = tris + h.slot * kTriDoubles;
+    const V3 c = cross(load3(p + 3), load3(p + 6));
+    const double l = sqrt(dot(c, c));
+    nrm = {c.x / l, c.y / l, c.z / l};
+  }
+  store3(locs + (long)i * 3, loc);
+  store3(normals + (long)i * 3, nrm);
+  valid[i] = h.tri >= 0 ? 1 : 0;
+  face_i[i] = h.tri < 0 ? -1 : (tri2face ? tri2face[h.tri] : h.tri);
+}
+
+__global__ __launch_bounds__(kThreads) void shadow_kernel(const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
+                                                          const double* __restrict__ locs, const unsigned char* __restrict__ valid,
+                                                          V3 light, int n, unsigned char* __restrict__ occluded) {
+  extern __shared__ int s_stack[];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  unsigned char occ = 0;
+  if (valid[i]) {
+    double full;
+    const V3 d = unit_towards(light, load3(locs + (long)i * 3), full);
+    const Hit h = closest_hit(light, d, tris, nodes, lp, s_stack + threadIdx.x);
+    // data_gen/render.py:248-253: no hit is "not blocked"; else np.isclose(t, full) with its defaults
+    if (h.tri >= 0) occ = fabs(h.t - full) <= 1e-8 + 1e-5 * fabs(full) ? 0 : 1;
+  }
+  occluded[i] = occ;
+}
+
+// ---------------------------------------------------------------- host
+int leaves_padded(long n_tris) {
+  const long l = (n_tris + kLeaf - 1) / kLeaf;
+  long lp = 1;
+  while (lp < l) lp <<= 1;
+  return (int)lp;
+}
+
+int depth_of(int lp) {
+  int d = 0;
+  while ((1 << d) < lp) ++d;
+  return d;
+}
+
+int tris_status(long n_tris) {
+  if (n_tris <= 0) return NLT_ERR_BAD_ARG;
+  if (n_tris >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  return NLT_OK;
+}
+
+int rays_status(long n) {
+  if (n <= 0) return NLT_ERR_BAD_ARG;
+  if (n >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  return NLT_OK;
+}
+
+size_t stack_bytes(int lp) { return (size_t)(depth_of(lp) + 1) * kThreads * sizeof(int); }
+
+unsigned blocks(long n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+}  // namespace
+
+extern "C" long nlt_bvh_tris_doubles(long n_tris) {
+  if (tris_status(n_tris) != NLT_OK) return -1;
+  return (long)leaves_padded(n_tris) * kLeaf * kTriDoubles;
+}
+
+extern "C" long nlt_bvh_nodes_doubles(long n_tris) {
+  if (tris_status(n_tris) != NLT_OK) return -1;
+  return (2l * leaves_padded(n_tris) - 1) * 6;
+}
+
+extern "C" int nlt_bvh_morton(const double* tri_verts, long n_tris, double lox, double loy, double loz, double hix, double hiy,
+                              double hiz, int* codes, void* stream) {
+  if (!tri_verts || !codes) return NLT_ERR_BAD_ARG;
+  const int st = tris_status(n_tris);
+  if (st != NLT_OK) return st;
+  hipLaunchKernelGGL(morton_kernel, dim3(blocks(n_tris, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), tri_verts, (int)n_tris,
+                     V3{lox, loy, loz}, V3{hix, hiy, hiz}, codes);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_bvh_build(const double* tri_verts, const int* order, long n_tris, double* tris, long tris_doubles, double* nodes,
+                             long nodes_doubles, void* stream) {
+  if (!tri_verts || !order || !tris || !nodes) return NLT_ERR_BAD_ARG;
+  const int st = tris_status(n_tris);
+  if (st != NLT_OK) return st;
+  if (tris_doubles < nlt_bvh_tris_doubles(n_tris) || nodes_doubles < nlt_bvh_nodes_doubles(n_tris)) return NLT_ERR_BAD_ARG;
+  const int lp = leaves_padded(n_tris);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(leaves_kernel, dim3(blocks(lp, 256)), dim3(256), 0, s, tri_verts, order, (int)n_tris, lp, tris, nodes);
+  for (int count = lp >> 1; count >= 1; count >>= 1)              // the level of `count` nodes starts at node count - 1
+    hipLaunchKernelGGL(level_kernel, dim3(blocks(count, 256)), dim3(256), 0, s, nodes, count - 1, count);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_raycast(const double* tris, const double* nodes, long n_tris, const int* tri2face, const double* origins,
+                           const double* dirs, long n_rays, double* t, int* tri, int* face, void* stream) {
+  if (!tris || !nodes || !origins || !dirs || !t || !tri || !face) return NLT_ERR_BAD_ARG;
+  int st = tris_status(n_tris);
+  if (st == NLT_OK) st = rays_status(n_rays);
+  if (st == NLT_OK && n_rays * 3 >= (1l << 31)) st = NLT_ERR_UNSUPPORTED;
+  if (st != NLT_OK) return st;
+  const int lp = leaves_padded(n_tris);
+  hipLaunchKernelGGL(raycast_kernel, dim3(blocks(n_rays, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream),
+                     tris, nodes, lp, tri2face, origins, dirs, (int)n_rays, t, tri, face);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_raycast_camera(const double* tris, const double* nodes, long n_tris, const int* tri2face, const double* cam_host,
+                                  int imh, int imw, double* locs, double* normals, unsigned char* valid, int* face_i, void* stream) {
+  if (!tris || !nodes || !cam_host || !locs || !normals || !valid || !face_i) return NLT_ERR_BAD_ARG;
+  if (imh <= 0 || imw <= 0) return NLT_ERR_BAD_ARG;
+  const int st = tris_status(n_tris);
+  if (st != NLT_OK) return st;
+  const long n = (long)imh * imw;
+  if (n * 3 >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  Camera cam;
+  for (int k = 0; k < 16; ++k) cam.m[k] = cam_host[k];
+  cam.loc = {cam_host[16], cam_host[17], cam_host[18]};
+  const int lp = leaves_padded(n_tris);
+  hipLaunchKernelGGL(camera_kernel, dim3(blocks(n, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream), tris,
+                     nodes, lp, tri2face, cam, imw, (int)n, locs, normals, valid, face_i);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_raycast_shadow(const double* tris, const double* nodes, long n_tris, const double* locs, const unsigned char* valid,
+                                  long n_pixels, double lx, double ly, double lz, unsigned char* occluded, void* stream) {
+  if (!tris || !nodes || !locs || !valid || !occluded) return NLT_ERR_BAD_ARG;
+  int st = tris_status(n_tris);
+  if (st == NLT_OK) st = rays_status(n_pixels);
+  if (st == NLT_OK && n_pixels * 3 >= (1l << 31)) st = NLT_ERR_UNSUPPORTED;
+  if (st != NLT_OK) return st;
+  const int lp = leaves_padded(n_tris);
+  hipLaunchKernelGGL(shadow_kernel, dim3(blocks(n_pixels, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream),
+                     tris, nodes, lp, locs, valid, V3{lx, ly, lz}, (int)n_pixels, occluded);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}

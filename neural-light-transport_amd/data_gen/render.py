@@ -4,8 +4,9 @@ mapping.  `intersect` is the dict render.py builds from xm.blender.camera.backpr
     'locs', 'normals'  [P,3] float64 CUDA        'valid' [P] uint8 (loc is not None and the hit
     'face_i' [P] int64 (only for the mapping)     object is the subject, render.py:219,267,302)
     'occluded' [P] uint8 (only for the light: the result of the reference's BVH shadow rays,
-                          render.py:238-254, which stay in Blender)
-The reference's list-of-Vector form is converted with `dense_intersect`."""
+                          render.py:238-254)
+The reference's list-of-Vector form is converted with `dense_intersect`; data_gen/mesh.py casts the rays itself
+(`backproject`, `shadow`) for a camera and a light that are not in a capture."""
 import os
 from os.path import join
 
@@ -174,8 +175,9 @@ def write_sample(outdir, sample, cam, light, nn, debug=False, workers=None):
 
 def calc_bidir_mapping(cached_unwrap, obj_name, xys, intersect, uvs, max_l1_interp=4):
     """render.py:279-351.  cached_unwrap: the {face: [[loop, vert, u, v], ...]} table of
-    data_gen/uv_unwrap.py:53-74 (dict, or a path to its pickle).  Returns (uv2cam [imh,imw,2],
-    cam2uv [uvs,uvs,2]) float64 in [0,1]."""
+    data_gen/uv_unwrap.py:53-74 (dict, or a path to its pickle), or its dense form {'uv': float64 [F,Vmax,2], 'counts': [F]}
+    (data_gen/mesh.py:dense_unwrap), which builds the same sample list with array indexing instead of a Python loop over the
+    hit pixels.  Returns (uv2cam [imh,imw,2], cam2uv [uvs,uvs,2]) float64 in [0,1]."""
     if isinstance(cached_unwrap, str):
         import pickle
         with open(cached_unwrap, 'rb') as h:
@@ -184,13 +186,22 @@ def calc_bidir_mapping(cached_unwrap, obj_name, xys, intersect, uvs, max_l1_inte
     xys = np.asarray(xys)
     face_i = np.asarray(intersect['face_i'])
     hit = np.nonzero(face_i >= 0)[0]
-    cam_locs, uv_list = [], []
-    for p in hit:                                           # pixel-major, then the face's vertices: the
-        uv = np.asarray(cached_unwrap[int(face_i[p])])[:, 2:]      # reference's sample order (render.py:299-317)
-        uv_list.append(uv)
-        cam_locs.append(np.repeat(xys[p:p + 1].astype(np.float64), uv.shape[0], 0))
-    uv = np.vstack(uv_list)
-    xy = np.vstack(cam_locs)
+    if isinstance(cached_unwrap, dict) and 'uv' in cached_unwrap and 'counts' in cached_unwrap:
+        table, counts = np.asarray(cached_unwrap['uv'], np.float64), np.asarray(cached_unwrap['counts'])
+        faces = face_i[hit]
+        n = counts[faces]
+        if faces.size and (faces.max() >= len(counts) or n.min() <= 0):
+            raise KeyError("a hit face has no entry in the dense unwrap table")
+        uv = table[faces][np.arange(table.shape[1])[None, :] < n[:, None]]      # row-major: pixel-major, then the face's vertices
+        xy = np.repeat(xys[hit].astype(np.float64), n, 0)
+    else:
+        cam_locs, uv_list = [], []
+        for p in hit:                                           # pixel-major, then the face's vertices: the
+            uv = np.asarray(cached_unwrap[int(face_i[p])])[:, 2:]      # reference's sample order (render.py:299-317)
+            uv_list.append(uv)
+            cam_locs.append(np.repeat(xys[p:p + 1].astype(np.float64), uv.shape[0], 0))
+        uv = np.vstack(uv_list)
+        xy = np.vstack(cam_locs)
     dev = intersect['valid'].device
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)
     method = {'func': 'griddata', 'func_underlying': 'nearest', 'fill_value': (0,), 'max_l1_interp': max_l1_interp}
