@@ -1276,6 +1276,32 @@ int nlt_raycast_camera(const double* tris, const double* nodes, long n_tris, con
  * occluded = !(|t - full| <= 1e-8 + 1e-5 |full|) (np.isclose's defaults).  occluded [n_pixels] uint8; 0 where valid == 0. */
 int nlt_raycast_shadow(const double* tris, const double* nodes, long n_tris, const double* locs, const unsigned char* valid,
                        long n_pixels, double lx, double ly, double lz, unsigned char* occluded, void* stream);
+/* Direct lighting of the mesh by one point light, seen by a camera: Lambert + GGX, hard cast shadows, spp_side x spp_side
+ * box-filtered samples per pixel for colour and coverage.  Not Cycles: no global illumination, no subsurface scattering, no
+ * light size; parity with a Blender render is not claimed.  Float64, only + - * / sqrt, no fused operations, every operation in
+ * this order (tests/shade_ref.py restates it); no atomics, equal inputs give equal bits.  With S = spp_side, per pixel (x, y),
+ * samples j = 0 .. S-1 (outer loop) and i = 0 .. S-1 (inner loop):
+ *   px = x + ((2i + 1) / (2S) - 0.5), py = y + ((2j + 1) / (2S) - 0.5)   (S = 1: exactly (x, y), the ray of nlt_raycast_camera)
+ *   the ray through (px, py), its closest hit, loc = cam + t d and the geometric normal ng as in nlt_raycast_camera; a miss
+ *   adds nothing.  The hit's barycentrics with the hit test's own operations: p = d x e2, inv = 1 / (e1 . p), s = cam - v0,
+ *   u = (s . p) * inv, q = s x e1, v = (d . q) * inv; w = (1 - u) - v; blend(a0, a1, a2) = (w a0 + u a1) + v a2 per component.
+ *   n = ng, or, with tri_normals [n_tris, 3, 3] (per corner, indexed by the caller's triangle index): m = blend(n0, n1, n2),
+ *   lm = sqrt(m . m), n = m / lm when lm is finite and > 0, else ng.  wo = (cam - loc) / |cam - loc|, co = n . wo; when co < 0:
+ *   n = -n, co = -co (two-sided).  kd = (kd_r, kd_g, kd_b), or, with tri_rgb [n_tris, 3, 3]: blend(c0, c1, c2).
+ *   wl = light - loc, r2 = wl . wl, wi = wl / sqrt(r2), ci = n . wi; unless ci > 0 the sample adds nothing.
+ *   Shadow, the rule of nlt_raycast_shadow: closest hit of the ray from the light towards loc, full = |loc - light|; a hit with
+ *   !(|t - full| <= 1e-8 + 1e-5 |full|) occludes and the sample adds nothing.
+ *   spec = 0 unless co > 0; else with a2 = alpha * alpha: hv = wi + wo, h = hv / sqrt(hv . hv), nh = n . h, vh = wo . h,
+ *   dd = (nh nh) * (a2 - 1) + 1, D = a2 / (pi * (dd dd)); G1(c) = (2 c) / (c + sqrt(a2 + (1 - a2) * (c c)));
+ *   m1 = 1 - vh, m2 = m1 m1, m5 = (m2 m2) * m1, F = ks + (1 - ks) * m5; spec = (((D * G1(ci)) * G1(co)) * F) / ((4 ci) * co).
+ *   radiance[c] = ((intensity / r2) * ci) * (kd[c] / pi + spec), pi = 3.141592653589793.
+ * rgb_linear [imh imw, 3] float32 = the sum of radiance in (j, i) order / (double)(S S), rounded once; coverage [imh imw]
+ * float32 = hits / (S S).  Every element of both is written, nothing else is.  cam_host: the 19 host doubles of
+ * nlt_raycast_camera.  tri_normals, tri_rgb: float64 device arrays or NULL.  spp_side outside 1 .. 8, imh or imw <= 0:
+ * NLT_ERR_BAD_ARG; the size limits of nlt_raycast_camera.  Nothing is launched after a refusal. */
+int nlt_render_direct(const double* tris, const double* nodes, long n_tris, const double* tri_normals, const double* tri_rgb,
+                      const double* cam_host, int imh, int imw, int spp_side, double lx, double ly, double lz, double intensity,
+                      double kd_r, double kd_g, double kd_b, double ks, double alpha, float* rgb_linear, float* coverage, void* stream);
 
 #ifdef __cplusplus
 }

@@ -226,6 +226,7 @@ SIGNATURES = {
     'nlt_raycast': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _vp, _vp, _vp, _vp]),
     'nlt_raycast_camera': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     'nlt_raycast_shadow': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_long] + [_c_double] * 3 + [_vp, _vp]),
+    'nlt_render_direct': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_int, _c_int, _c_int] + [_c_double] * 9 + [_vp, _vp, _vp]),
 }
 
 _real = None
@@ -1710,6 +1711,30 @@ def raycast_shadow(tris, nodes, n_tris, locs, valid, light_loc):
     _call('nlt_raycast_shadow', *_bvh_args(tris, nodes, n_tris, None), _tptr(locs, torch.float64, 'locs'),
           _tptr(valid, torch.uint8, 'valid'), p, *(float(x) for x in light_loc), occluded.data_ptr())
     return occluded
+
+
+def render_direct(tris, nodes, n_tris, tri_normals, tri_rgb, cam_mat_inv, cam_loc, imh, imw, spp_side, light_loc, intensity, kd, ks,
+                  alpha):
+    """One point light's direct lighting of the mesh (include/nlt_hip.h: nlt_render_direct).  tri_normals, tri_rgb: float64
+    [n_tris,3,3] or None; camera as `raycast_camera`; light_loc, kd: 3 numbers -> (rgb_linear float32 [imh*imw,3], coverage
+    float32 [imh*imw]), row-major pixels."""
+    vals = [float(x) for x in cam_mat_inv] + [float(x) for x in cam_loc]
+    if len(vals) != 19:
+        raise NLTError("render_direct: 16 matrix entries and 3 coordinates expected")
+    if getattr(_tls, 'tape', None) is not None:
+        raise NLTError("render_direct reads its camera from host memory during the call: it cannot be recorded on a launch tape")
+    for name, t in (('tri_normals', tri_normals), ('tri_rgb', tri_rgb)):
+        if t is not None and t.numel() != 9 * n_tris:
+            raise NLTError("render_direct: %s %s does not match %d triangles" % (name, tuple(t.shape), n_tris))
+    host = (_c_double * 19)(*vals)
+    dev, p = tris.device, int(imh) * int(imw)
+    rgb = torch.empty((max(p, 0), 3), device=dev, dtype=torch.float32)
+    coverage = torch.empty(max(p, 0), device=dev, dtype=torch.float32)
+    _call('nlt_render_direct', *_bvh_args(tris, nodes, n_tris, None), _tptr(tri_normals, torch.float64, 'tri_normals'),
+          _tptr(tri_rgb, torch.float64, 'tri_rgb'), ctypes.addressof(host), int(imh), int(imw), int(spp_side),
+          *(float(x) for x in light_loc), float(intensity), *(float(x) for x in kd), float(ks), float(alpha), rgb.data_ptr(),
+          coverage.data_ptr())
+    return rgb, coverage
 
 
 # ---------------------------------------------------------------- texel-buffer assembly

@@ -40,6 +40,30 @@
 // to ~4) an accepted point lies within a few tens of ulps of the largest coordinate involved (a vertex or the origin); 256 is
 // that with margin.  For worse-conditioned slivers the bound grows with the condition number and is not claimed.
 // Every store is a plain vector store.
+//
+// DIRECT LIGHTING (`render_kernel`, nlt_render_direct): one point light, Lambert + GGX, hard cast shadows, S x S box-filtered
+// samples per pixel.  Not Cycles: no global illumination, no subsurface scattering, no light size.  Float64 throughout, only
+// + - * / sqrt, every operation in the order written here (tests/shade_ref.py restates it); one lane per pixel, the primary ray
+// and the shadow ray share the lane's LDS stack in turn.  Per pixel (x, y), samples j = 0 .. S-1 (outer), i = 0 .. S-1 (inner):
+//   px = x + ((2i + 1) / (2S) - 0.5), py = y + ((2j + 1) / (2S) - 0.5)        (S = 1: exactly (x, y), the ray of camera_kernel)
+//   ray, closest hit, loc = cam + t*d and the geometric normal ng exactly as in camera_kernel, with (px, py) for (x, y)
+//   a miss adds nothing.  (u, v) = the barycentrics of `hit_triangle` recomputed at the hit's slot with its operations:
+//     p = d x e2, inv = 1 / (e1 . p), s = cam - v0, u = (s . p) * inv, q = s x e1, v = (d . q) * inv;  w = (1 - u) - v
+//   blend(a0, a1, a2) = (w*a0 + u*a1) + v*a2 per component, corners of the caller's triangle index
+//   n  = ng, or with tri_normals: m = blend(n0, n1, n2), lm = sqrt(m . m), n = m / lm when lm is finite and > 0, else ng
+//   wo = (cam - loc) / |cam - loc|, co = n . wo;  co < 0: n = -n, co = -co                       (two-sided)
+//   kd = the constant, or with tri_rgb: blend(c0, c1, c2)
+//   wl = light - loc, r2 = wl . wl, wi = wl / sqrt(r2), ci = n . wi;  unless ci > 0 the sample adds nothing
+//   shadow: the rule of shadow_kernel -- ds = (loc - light) / full, full = |loc - light|, closest hit from the light; a hit with
+//     !(|t - full| <= 1e-8 + 1e-5 * |full|) is occluded and the sample adds nothing
+//   spec = 0 unless co > 0; else with a2 = alpha * alpha:
+//     hv = wi + wo, h = hv / sqrt(hv . hv), nh = n . h, vh = wo . h
+//     dd = (nh*nh) * (a2 - 1) + 1, D = a2 / (pi * (dd*dd))
+//     G1(c) = (2*c) / (c + sqrt(a2 + (1 - a2) * (c*c)))
+//     m1 = 1 - vh, m2 = m1*m1, m5 = (m2*m2) * m1, F = ks + (1 - ks) * m5
+//     spec = (((D * G1(ci)) * G1(co)) * F) / ((4*ci) * co)
+//   radiance[c] = ((intensity / r2) * ci) * (kd[c] / pi + spec),   pi = 3.141592653589793
+// rgb[c] = (float)(sum of radiance[c] in (j, i) order / (double)(S*S)); coverage = (float)((double)hits / (double)(S*S)).
 #include <math.h>
 #include <stdint.h>
 
@@ -318,6 +342,104 @@ __global__ __launch_bounds__(kThreads) void shadow_kernel(const double* __restri
   occluded[i] = occ;
 }
 
+// direct lighting (file header): every operation in the order stated there
+struct Shade {
+  V3 light, kd;
+  double intensity, ks, alpha;
+};
+
+constexpr double kPi = 3.141592653589793;
+
+__device__ __forceinline__ V3 blend3(const double* __restrict__ a, double w, double u, double v) {
+  return {(w * a[0] + u * a[3]) + v * a[6], (w * a[1] + u * a[4]) + v * a[7], (w * a[2] + u * a[5]) + v * a[8]};
+}
+
+__device__ __forceinline__ double smith_g1(double c, double a2) { return (2.0 * c) / (c + sqrt(a2 + (1.0 - a2) * (c * c))); }
+
+__global__ __launch_bounds__(kThreads) void render_kernel(const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
+                                                          const double* __restrict__ tri_normals, const double* __restrict__ tri_rgb,
+                                                          Camera cam, Shade sh, int imw, int n, int spp_side,
+                                                          float* __restrict__ rgb, float* __restrict__ coverage) {
+  extern __shared__ int s_stack[];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  int* stack = s_stack + threadIdx.x;
+  const double x = (double)(i % imw), y = (double)(i / imw);
+  const double* m = cam.m;
+  const double two_s = (double)(2 * spp_side), count = (double)(spp_side * spp_side);
+  const double a2 = sh.alpha * sh.alpha;
+  double sr = 0.0, sg = 0.0, sb = 0.0;
+  int hits = 0;
+  for (int sj = 0; sj < spp_side; ++sj) {
+    const double py = y + ((double)(2 * sj + 1) / two_s - 0.5);
+    for (int si = 0; si < spp_side; ++si) {
+      const double px = x + ((double)(2 * si + 1) / two_s - 0.5);
+      const double hx = ((m[0] * px + m[1] * py) + m[2]) + m[3], hy = ((m[4] * px + m[5] * py) + m[6]) + m[7];
+      const double hz = ((m[8] * px + m[9] * py) + m[10]) + m[11], hw = ((m[12] * px + m[13] * py) + m[14]) + m[15];
+      const V3 to = {hx / hw, hy / hw, hz / hw};
+      double len;
+      const V3 d = unit_towards(cam.loc, to, len);
+      const Hit h = closest_hit(cam.loc, d, tris, nodes, lp, stack);
+      if (h.tri < 0) continue;
+      ++hits;
+      const V3 loc = {cam.loc.x + h.t * d.x, cam.loc.y + h.t * d.y, cam.loc.z + h.t * d.z};
+      const double* p = tris + h.slot * kTriDoubles;
+      const V3 v0 = load3(p), e1 = load3(p + 3), e2 = load3(p + 6);
+      const V3 c = cross(e1, e2);
+      const double l = sqrt(dot(c, c));
+      V3 nrm = {c.x / l, c.y / l, c.z / l};
+      // the barycentrics of hit_triangle, its operations again
+      const V3 pv = cross(d, e2);
+      const double inv = 1.0 / dot(e1, pv);
+      const V3 s = sub(cam.loc, v0);
+      const double u = dot(s, pv) * inv;
+      const V3 q = cross(s, e1);
+      const double v = dot(d, q) * inv;
+      const double w = (1.0 - u) - v;
+      if (tri_normals) {
+        const V3 mn = blend3(tri_normals + (long)h.tri * 9, w, u, v);
+        const double lm = sqrt(dot(mn, mn));
+        if (isfinite(lm) && lm > 0.0) nrm = {mn.x / lm, mn.y / lm, mn.z / lm};
+      }
+      double lo_;
+      const V3 wo = unit_towards(loc, cam.loc, lo_);
+      double co = dot(nrm, wo);
+      if (co < 0.0) { nrm = {-nrm.x, -nrm.y, -nrm.z}; co = -co; }
+      const V3 kd = tri_rgb ? blend3(tri_rgb + (long)h.tri * 9, w, u, v) : sh.kd;
+      const V3 wl = sub(sh.light, loc);
+      const double r2 = dot(wl, wl);
+      const double lr = sqrt(r2);
+      const V3 wi = {wl.x / lr, wl.y / lr, wl.z / lr};
+      const double ci = dot(nrm, wi);
+      if (!(ci > 0.0)) continue;
+      double full;
+      const V3 ds = unit_towards(sh.light, loc, full);
+      const Hit hs = closest_hit(sh.light, ds, tris, nodes, lp, stack);
+      if (hs.tri >= 0 && !(fabs(hs.t - full) <= 1e-8 + 1e-5 * fabs(full))) continue;
+      double spec = 0.0;
+      if (co > 0.0) {
+        const V3 hv = {wi.x + wo.x, wi.y + wo.y, wi.z + wo.z};
+        const double lh = sqrt(dot(hv, hv));
+        const V3 hh = {hv.x / lh, hv.y / lh, hv.z / lh};
+        const double nh = dot(nrm, hh), vh = dot(wo, hh);
+        const double dd = (nh * nh) * (a2 - 1.0) + 1.0;
+        const double D = a2 / (kPi * (dd * dd));
+        const double m1 = 1.0 - vh, m2 = m1 * m1, m5 = (m2 * m2) * m1;
+        const double F = sh.ks + (1.0 - sh.ks) * m5;
+        spec = (((D * smith_g1(ci, a2)) * smith_g1(co, a2)) * F) / ((4.0 * ci) * co);
+      }
+      const double e = (sh.intensity / r2) * ci;
+      sr += e * (kd.x / kPi + spec);
+      sg += e * (kd.y / kPi + spec);
+      sb += e * (kd.z / kPi + spec);
+    }
+  }
+  rgb[(long)i * 3] = (float)(sr / count);
+  rgb[(long)i * 3 + 1] = (float)(sg / count);
+  rgb[(long)i * 3 + 2] = (float)(sb / count);
+  coverage[i] = (float)((double)hits / count);
+}
+
 // ---------------------------------------------------------------- host
 int leaves_padded(long n_tris) {
   const long l = (n_tris + kLeaf - 1) / kLeaf;
@@ -428,6 +550,27 @@ extern "C" int nlt_raycast_shadow(const double* tris, const double* nodes, long 
   const int lp = leaves_padded(n_tris);
   hipLaunchKernelGGL(shadow_kernel, dim3(blocks(n_pixels, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream),
                      tris, nodes, lp, locs, valid, V3{lx, ly, lz}, (int)n_pixels, occluded);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_render_direct(const double* tris, const double* nodes, long n_tris, const double* tri_normals, const double* tri_rgb,
+                                 const double* cam_host, int imh, int imw, int spp_side, double lx, double ly, double lz,
+                                 double intensity, double kd_r, double kd_g, double kd_b, double ks, double alpha, float* rgb_linear,
+                                 float* coverage, void* stream) {
+  if (!tris || !nodes || !cam_host || !rgb_linear || !coverage) return NLT_ERR_BAD_ARG;
+  if (imh <= 0 || imw <= 0 || spp_side < 1 || spp_side > 8) return NLT_ERR_BAD_ARG;
+  const int st = tris_status(n_tris);
+  if (st != NLT_OK) return st;
+  const long n = (long)imh * imw;
+  if (n * 3 >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  Camera cam;
+  for (int k = 0; k < 16; ++k) cam.m[k] = cam_host[k];
+  cam.loc = {cam_host[16], cam_host[17], cam_host[18]};
+  const Shade sh = {V3{lx, ly, lz}, V3{kd_r, kd_g, kd_b}, intensity, ks, alpha};
+  const int lp = leaves_padded(n_tris);
+  hipLaunchKernelGGL(render_kernel, dim3(blocks(n, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream), tris,
+                     nodes, lp, tri_normals, tri_rgb, cam, sh, imw, (int)n, spp_side, rgb_linear, coverage);
   NLT_CHECK_LAUNCH();
   return NLT_OK;
 }

@@ -183,6 +183,23 @@ class Mesh:
         return C.raycast(*self.bvh, self.n_tris, self._tri2face, dev(origins), dev(dirs))
 
 
+def corner_normals(mesh):
+    """Area-weighted vertex normals of `mesh`, gathered per triangle corner through `mesh.tris` -> float64 [T,3,3] on the host.
+    A vertex's normal is the sum of e1 x e2 (twice the area times the unit normal) over the triangles that use it, divided by its
+    length; degenerate triangles add nothing, and a vertex whose sum is zero keeps a zero normal (the kernel then falls back to
+    the geometric normal where the blend vanishes)."""
+    tv = mesh.tri_verts
+    with np.errstate(all='ignore'):
+        c = np.cross(tv[:, 1] - tv[:, 0], tv[:, 2] - tv[:, 0])
+    c[~np.isfinite(c).all(1)] = 0.0
+    n = np.zeros_like(mesh.vertices)
+    for k in range(3):
+        np.add.at(n, mesh.tris[:, k], c)
+    length = np.sqrt((n * n).sum(1, keepdims=True))
+    n = np.divide(n, length, out=np.zeros_like(n), where=length > 0)
+    return np.ascontiguousarray(n[mesh.tris])
+
+
 def unwrap_from_obj(mesh):
     """The {face: [[loop, vert, u, v], ...]} table of data_gen/uv_unwrap.py:59-63 from the UVs the mesh file itself carries
     (`Mesh.load` / `load_mesh` of an .obj with `vt`).  No unwrapping is done here: a mesh without UVs raises."""
@@ -259,11 +276,12 @@ def shadow(mesh, light, intersect):
     return intersect
 
 
-def render_geometry(mesh, cached_unwrap, cam, light, imh, uvs, rgb_camspc=None):
+def render_geometry(mesh, cached_unwrap, cam, light, imh, uvs, rgb_camspc=None, alpha=None):
     """Every buffer of a sample for a camera and a light the capture does not hold: both ray casts, then `render_sample` with
-    alpha = 255 * valid (the binary hit mask; Cycles' anti-aliased alpha is out of scope).  rgb_camspc = None: a complete test
-    sample for `write_sample`."""
+    alpha = 255 * valid (the binary hit mask; Cycles' anti-aliased alpha is out of scope) unless an `alpha` [imh,imw] uint8 is
+    given (data_gen/shade.py passes the supersampled coverage).  rgb_camspc = None: a complete test sample for `write_sample`."""
     cam, light = _params(cam), _params(light)
     intersect = shadow(mesh, light, backproject(mesh, cam, imh))
-    alpha = (intersect['valid'] * 255).view(intersect['hw'])
+    if alpha is None:
+        alpha = (intersect['valid'] * 255).view(intersect['hw'])
     return render_sample(intersect, cached_unwrap, cam, light, uvs, rgb_camspc=rgb_camspc, alpha=alpha)
