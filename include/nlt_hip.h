@@ -1278,7 +1278,7 @@ int nlt_raycast_shadow(const double* tris, const double* nodes, long n_tris, con
                        long n_pixels, double lx, double ly, double lz, unsigned char* occluded, void* stream);
 /* Direct lighting of the mesh by one point light, seen by a camera: Lambert + GGX, hard cast shadows, spp_side x spp_side
  * box-filtered samples per pixel for colour and coverage.  Not Cycles: no global illumination, no subsurface scattering, no
- * light size; parity with a Blender render is not claimed.  Float64, only + - * / sqrt, no fused operations, every operation in
+ * light size (nlt_render_global below adds one diffuse bounce and a sized light); parity with a Blender render is not claimed.  Float64, only + - * / sqrt, no fused operations, every operation in
  * this order (tests/shade_ref.py restates it); no atomics, equal inputs give equal bits.  With S = spp_side, per pixel (x, y),
  * samples j = 0 .. S-1 (outer loop) and i = 0 .. S-1 (inner loop):
  *   px = x + ((2i + 1) / (2S) - 0.5), py = y + ((2j + 1) / (2S) - 0.5)   (S = 1: exactly (x, y), the ray of nlt_raycast_camera)
@@ -1302,6 +1302,47 @@ int nlt_raycast_shadow(const double* tris, const double* nodes, long n_tris, con
 int nlt_render_direct(const double* tris, const double* nodes, long n_tris, const double* tri_normals, const double* tri_rgb,
                       const double* cam_host, int imh, int imw, int spp_side, double lx, double ly, double lz, double intensity,
                       double kd_r, double kd_g, double kd_b, double ks, double alpha, float* rgb_linear, float* coverage, void* stream);
+/* nlt_render_direct plus a light of a size and one diffuse bounce: the light is a sphere of radius light_radius sampled at n_l
+ * points per sample (penumbrae), and every sample gathers, over n_b cosine-weighted directions, the light its surroundings
+ * reflect diffusely (colour bleeding, light in cast shadows).  Still not Cycles: one bounce, no glossy indirect light, no
+ * subsurface scattering, one object; parity with a Blender render is not claimed.  Same form as nlt_render_direct: float64, only
+ * + - * / sqrt, no fused operations, every operation in this order (tests/shade_global_ref.py restates it), no atomics, equal
+ * inputs give equal bits.  Both sample tables come from the caller; no sine or cosine is evaluated here.
+ *   light_pts  [n_lsets, n_l, 3] float64, device: unit vectors.  1 <= n_l <= 64, n_lsets >= 1.
+ *   bounce_pts [n_bsets, n_b, 2] float64, device: points (dx, dy) of the closed unit disc.  0 <= n_b <= 64, n_bsets >= 1; may be
+ *              NULL when n_b = 0 (it is not read then).
+ * Per pixel, samples (j, i) as in nlt_render_direct; sample s = j S + i uses light set s mod n_lsets and bounce set s mod n_bsets.
+ *   The primary ray, its hit (original triangle index T0), loc, ng, the barycentrics, n, the two-sided flip, wo, co and kd are
+ *   exactly those of nlt_render_direct.  A miss adds nothing.
+ *   DIRECT term of the sample: a = 0; for k = 0 .. n_l - 1: Lk = light + light_radius * light_pts[set][k] (per component a
+ *   multiply, then an add); with Lk for the light and Ik = intensity / (double)n_l for the intensity, the steps of
+ *   nlt_render_direct from "wl = light - loc" on: ci > 0 or nothing, the shadow ray from Lk with its isclose rule, spec,
+ *   radiance[c] = ((Ik / r2) * ci) * (kd[c] / pi + spec); a[c] += radiance[c].  The light sphere is not geometry: it occludes
+ *   nothing.  D[c] += a[c].
+ *   INDIRECT term of the sample (n_b > 0; else it is 0 and nothing of the following is done):
+ *   ngf = ng, negated when ng . wo < 0.  Tangent frame of n (Duff et al. 2017): sg = n.z >= 0 ? 1 : -1, fa = -1 / (sg + n.z),
+ *   fb = (n.x n.y) * fa, t1 = (1 + (sg * (n.x n.x)) * fa, sg * fb, -sg * n.x), t2 = (fb, sg + (n.y n.y) * fa, -n.y).
+ *   b = 0; for k = 0 .. n_b - 1: (dx, dy) = bounce_pts[set][k], qz = (1 - dx dx) - dy dy, dz = sqrt(qz > 0 ? qz : 0),
+ *   wv[c] = (dx * t1[c] + dy * t2[c]) + dz * n[c], wb = wv / sqrt(wv . wv); skipped unless ngf . wb > 0.  The closest hit of the ray
+ *   (loc, wb) over every triangle but the one of original index T0 (same hit test, same tie rule); a miss adds nothing.
+ *   loc2 = loc + t wb; ng2, the barycentrics (with loc for the origin, wb for the direction), the blended n2 and kd2 by the
+ *   primary's rules at the hit triangle; n2 = -n2 when n2 . wb > 0.  Lit by the light's CENTRE at the full intensity, Lambert only:
+ *   wl = light - loc2, r2 = wl . wl, wi = wl / sqrt(r2), ci = n2 . wi; ci > 0 or nothing; the shadow ray from the light towards
+ *   loc2 with the isclose rule; b[c] += ((intensity / r2) * ci) * (kd2[c] / pi).
+ *   I[c] += (kd[c] * b[c]) / (double)n_b.  (The bounce is cosine-weighted, so kd is the whole weight; the primary's specular
+ *   lobe receives no indirect light.)
+ * rgb_linear [imh imw, 3] float32 = (float)((D + I) / (double)(S S)); rgb_indirect [imh imw, 3] float32 = (float)(I / (double)(S S)),
+ * or NULL: not written; coverage as nlt_render_direct.  Every element of the outputs given is written, nothing else is; the tables
+ * and attribute arrays are read inside the stated elements only.  With n_b = 0, n_l = 1 and light_radius = 0 the outputs are
+ * nlt_render_direct's, bit for bit (for a light whose coordinates are not -0).
+ * NLT_ERR_BAD_ARG: a NULL required pointer (light_pts included), NULL bounce_pts with n_b > 0, n_l outside 1 .. 64, n_b outside
+ * 0 .. 64, n_lsets or n_bsets < 1, light_radius negative or not finite, and what nlt_render_direct refuses; its size limits give
+ * NLT_ERR_UNSUPPORTED.  Nothing is launched after a refusal. */
+int nlt_render_global(const double* tris, const double* nodes, long n_tris, const double* tri_normals, const double* tri_rgb,
+                      const double* cam_host, int imh, int imw, int spp_side, double lx, double ly, double lz, double intensity,
+                      double kd_r, double kd_g, double kd_b, double ks, double alpha, double light_radius, const double* light_pts,
+                      int n_l, int n_lsets, const double* bounce_pts, int n_b, int n_bsets, float* rgb_linear, float* coverage,
+                      float* rgb_indirect, void* stream);
 
 #ifdef __cplusplus
 }

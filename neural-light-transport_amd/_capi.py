@@ -227,6 +227,8 @@ SIGNATURES = {
     'nlt_raycast_camera': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp, _vp]),
     'nlt_raycast_shadow': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_long] + [_c_double] * 3 + [_vp, _vp]),
     'nlt_render_direct': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_int, _c_int, _c_int] + [_c_double] * 9 + [_vp, _vp, _vp]),
+    'nlt_render_global': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_int, _c_int, _c_int] + [_c_double] * 10 +
+                          [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
 }
 
 _real = None
@@ -1735,6 +1737,38 @@ def render_direct(tris, nodes, n_tris, tri_normals, tri_rgb, cam_mat_inv, cam_lo
           *(float(x) for x in light_loc), float(intensity), *(float(x) for x in kd), float(ks), float(alpha), rgb.data_ptr(),
           coverage.data_ptr())
     return rgb, coverage
+
+
+def render_global(tris, nodes, n_tris, tri_normals, tri_rgb, cam_mat_inv, cam_loc, imh, imw, spp_side, light_loc, intensity, kd, ks,
+                  alpha, light_radius, light_pts, bounce_pts=None, want_indirect=True):
+    """`render_direct` with a spherical light and one diffuse bounce (include/nlt_hip.h: nlt_render_global).  light_pts: float64
+    [n_lsets, n_l, 3] unit vectors; bounce_pts: float64 [n_bsets, n_b, 2] points of the unit disc, or None (no bounce: n_b = 0 and
+    a NULL table) -> (rgb_linear float32 [imh*imw,3], coverage float32 [imh*imw], rgb_indirect float32 [imh*imw,3] or None)."""
+    vals = [float(x) for x in cam_mat_inv] + [float(x) for x in cam_loc]
+    if len(vals) != 19:
+        raise NLTError("render_global: 16 matrix entries and 3 coordinates expected")
+    if getattr(_tls, 'tape', None) is not None:
+        raise NLTError("render_global reads its camera from host memory during the call: it cannot be recorded on a launch tape")
+    for name, t in (('tri_normals', tri_normals), ('tri_rgb', tri_rgb)):
+        if t is not None and t.numel() != 9 * n_tris:
+            raise NLTError("render_global: %s %s does not match %d triangles" % (name, tuple(t.shape), n_tris))
+    if light_pts.dim() != 3 or light_pts.shape[2] != 3:
+        raise NLTError("render_global: light_pts [n_lsets, n_l, 3] expected, got %s" % (tuple(light_pts.shape),))
+    if bounce_pts is not None and (bounce_pts.dim() != 3 or bounce_pts.shape[2] != 2):
+        raise NLTError("render_global: bounce_pts [n_bsets, n_b, 2] expected, got %s" % (tuple(bounce_pts.shape),))
+    n_lsets, n_l = int(light_pts.shape[0]), int(light_pts.shape[1])
+    n_bsets, n_b = (1, 0) if bounce_pts is None else (int(bounce_pts.shape[0]), int(bounce_pts.shape[1]))
+    host = (_c_double * 19)(*vals)
+    dev, p = tris.device, int(imh) * int(imw)
+    rgb = torch.empty((max(p, 0), 3), device=dev, dtype=torch.float32)
+    coverage = torch.empty(max(p, 0), device=dev, dtype=torch.float32)
+    indirect = torch.empty((max(p, 0), 3), device=dev, dtype=torch.float32) if want_indirect else None
+    _call('nlt_render_global', *_bvh_args(tris, nodes, n_tris, None), _tptr(tri_normals, torch.float64, 'tri_normals'),
+          _tptr(tri_rgb, torch.float64, 'tri_rgb'), ctypes.addressof(host), int(imh), int(imw), int(spp_side),
+          *(float(x) for x in light_loc), float(intensity), *(float(x) for x in kd), float(ks), float(alpha), float(light_radius),
+          _tptr(light_pts, torch.float64, 'light_pts'), n_l, n_lsets, _tptr(bounce_pts if n_b > 0 else None, torch.float64, 'bounce_pts'),
+          n_b, n_bsets, rgb.data_ptr(), coverage.data_ptr(), None if indirect is None else indirect.data_ptr())
+    return rgb, coverage, indirect
 
 
 # ---------------------------------------------------------------- texel-buffer assembly

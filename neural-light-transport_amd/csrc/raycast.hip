@@ -42,7 +42,8 @@
 // Every store is a plain vector store.
 //
 // DIRECT LIGHTING (`render_kernel`, nlt_render_direct): one point light, Lambert + GGX, hard cast shadows, S x S box-filtered
-// samples per pixel.  Not Cycles: no global illumination, no subsurface scattering, no light size.  Float64 throughout, only
+// samples per pixel.  Not Cycles: no global illumination, no subsurface scattering, no light size (GLOBAL RENDERS below add one
+// diffuse bounce and a sized light in a kernel of their own; this one stays as it is).  Float64 throughout, only
 // + - * / sqrt, every operation in the order written here (tests/shade_ref.py restates it); one lane per pixel, the primary ray
 // and the shadow ray share the lane's LDS stack in turn.  Per pixel (x, y), samples j = 0 .. S-1 (outer), i = 0 .. S-1 (inner):
 //   px = x + ((2i + 1) / (2S) - 0.5), py = y + ((2j + 1) / (2S) - 0.5)        (S = 1: exactly (x, y), the ray of camera_kernel)
@@ -64,6 +65,30 @@
 //     spec = (((D * G1(ci)) * G1(co)) * F) / ((4*ci) * co)
 //   radiance[c] = ((intensity / r2) * ci) * (kd[c] / pi + spec),   pi = 3.141592653589793
 // rgb[c] = (float)(sum of radiance[c] in (j, i) order / (double)(S*S)); coverage = (float)((double)hits / (double)(S*S)).
+//
+// GLOBAL RENDERS (`render_global_kernel`, nlt_render_global): the above with a spherical light of radius light_radius sampled at
+// n_l points (penumbrae) and one cosine-weighted diffuse bounce over n_b directions (colour bleeding, light in cast shadows).
+// Still not Cycles: one bounce, no glossy indirect light, no subsurface scattering, one object.  Same form: float64, + - * / sqrt
+// only, one lane per pixel, every traversal of a lane (primary, n_l shadow rays, n_b bounce rays and their shadow rays) uses the
+// lane's LDS stack in turn.  The tables come from the host (data_gen/shade.py): light_pts [n_lsets][n_l][3] unit vectors,
+// bounce_pts [n_bsets][n_b][2] points of the unit disc; no sine or cosine is evaluated here (tests/shade_global_ref.py restates
+// every step in NumPy).  Per sample s = j*S + i, with light set s mod n_lsets and bounce set s mod n_bsets:
+//   primary ray, hit (original index T0), loc, ng, (u, v, w), n, wo, co, the two-sided flip and kd exactly as above
+//   DIRECT  a = 0; for k = 0 .. n_l-1:  Lk[c] = light[c] + light_radius * light_pts[set][k][c],  Ik = intensity / (double)n_l
+//     the steps above from "wl = light - loc" on with Lk, Ik for light, intensity (ci > 0, shadow ray from Lk, spec);
+//     a[c] += ((Ik / r2) * ci) * (kd[c] / pi + spec).   D[c] += a[c].   The light sphere is not geometry: it occludes nothing.
+//   INDIRECT (n_b > 0, else 0)  ngf = ng, negated when ng . wo < 0
+//     frame (Duff et al. 2017): sg = n.z >= 0 ? 1 : -1, fa = -1 / (sg + n.z), fb = (n.x*n.y) * fa
+//       t1 = (1 + (sg * (n.x*n.x)) * fa, sg * fb, -sg * n.x),  t2 = (fb, sg + (n.y*n.y) * fa, -n.y)
+//     b = 0; for k = 0 .. n_b-1:  (dx, dy) = bounce_pts[set][k], qz = (1 - dx*dx) - dy*dy, dz = sqrt(qz > 0 ? qz : 0)
+//       wv[c] = (dx*t1[c] + dy*t2[c]) + dz*n[c], wb = wv / sqrt(wv . wv);  skipped unless ngf . wb > 0
+//       closest hit of (loc, wb) over all triangles but original index T0 (`closest_hit<true>`); a miss adds nothing
+//       loc2 = loc + t*wb; ng2, barycentrics (origin loc, direction wb), n2, kd2 by the primary's rules; n2 = -n2 when n2 . wb > 0
+//       the light's CENTRE, full intensity, Lambert only: wl = light - loc2, r2, wi, ci = n2 . wi; ci > 0 or nothing; shadow ray
+//       from the light towards loc2 (isclose rule);  b[c] += ((intensity / r2) * ci) * (kd2[c] / pi)
+//     I[c] += (kd[c] * b[c]) / (double)n_b
+// rgb[c] = (float)((D[c] + I[c]) / (double)(S*S)), rgb_indirect[c] = (float)(I[c] / (double)(S*S)), coverage as above.
+// D and I are kept apart so that n_b = 0, n_l = 1, light_radius = 0 gives render_kernel's bits (x + 0 = x).
 #include <math.h>
 #include <stdint.h>
 
@@ -228,8 +253,12 @@ struct Hit {
   long slot;      // where its (v0, e1, e2) lies in `tris`
 };
 
+// kSkip: the triangle whose ORIGINAL index is `skip` is passed over (the bounce rays of render_global_kernel leave from it);
+// without it the code is what it was.
+template <bool kSkip = false>
 __device__ __forceinline__ Hit closest_hit(V3 o, V3 d, const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
-                                           int* __restrict__ stack /* this lane's entry 0; entries kThreads ints apart */) {
+                                           int* __restrict__ stack /* this lane's entry 0; entries kThreads ints apart */,
+                                           int skip = -1) {
   Ray r;
   r.o = o; r.d = d;
   r.inv = {1.0 / d.x, 1.0 / d.y, 1.0 / d.z};
@@ -246,6 +275,7 @@ __device__ __forceinline__ Hit closest_hit(V3 o, V3 d, const double* __restrict_
         const double* p = tris + (s0 + k) * kTriDoubles;
         const int idx = (int)p[9];
         if (idx < 0) continue;
+        if (kSkip && idx == skip) continue;
         double t;
         if (hit_triangle(o, d, load3(p), load3(p + 3), load3(p + 6), t) && (t < best.t || (t == best.t && idx < best.tri))) {
           best.t = t; best.tri = idx; best.slot = s0 + k;
@@ -440,6 +470,167 @@ __global__ __launch_bounds__(kThreads) void render_kernel(const double* __restri
   coverage[i] = (float)((double)hits / count);
 }
 
+// global renders (file header): a kernel of its own beside render_kernel, which stays as it is
+struct Tables {
+  const double* light_pts;    // [n_lsets][n_l][3]
+  const double* bounce_pts;   // [n_bsets][n_b][2]; not read when n_b == 0
+  double light_radius;
+  int n_l, n_lsets, n_b, n_bsets;
+};
+
+// ng, the shading normal n (blended corner normals where given and usable, else ng; not flipped) and kd of the hit at `slot`
+// (original triangle `tri`) of the ray (o, d): the barycentrics are those of hit_triangle, its operations again.
+__device__ __forceinline__ void surface_at(const double* __restrict__ tris, long slot, int tri, V3 o, V3 d,
+                                           const double* __restrict__ tri_normals, const double* __restrict__ tri_rgb, V3 kd_const,
+                                           V3& ng, V3& n, V3& kd) {
+  const double* p = tris + slot * kTriDoubles;
+  const V3 v0 = load3(p), e1 = load3(p + 3), e2 = load3(p + 6);
+  const V3 c = cross(e1, e2);
+  const double l = sqrt(dot(c, c));
+  ng = {c.x / l, c.y / l, c.z / l};
+  n = ng;
+  const V3 pv = cross(d, e2);
+  const double inv = 1.0 / dot(e1, pv);
+  const V3 s = sub(o, v0);
+  const double u = dot(s, pv) * inv;
+  const V3 q = cross(s, e1);
+  const double v = dot(d, q) * inv;
+  const double w = (1.0 - u) - v;
+  if (tri_normals) {
+    const V3 mn = blend3(tri_normals + (long)tri * 9, w, u, v);
+    const double lm = sqrt(dot(mn, mn));
+    if (isfinite(lm) && lm > 0.0) n = {mn.x / lm, mn.y / lm, mn.z / lm};
+  }
+  kd = tri_rgb ? blend3(tri_rgb + (long)tri * 9, w, u, v) : kd_const;
+}
+
+// The light point L as seen from loc with normal n: r2, wi, ci; false unless ci > 0 and the shadow ray from L reaches loc.
+__device__ __forceinline__ bool lit_from(V3 L, V3 loc, V3 n, const double* __restrict__ tris, const double* __restrict__ nodes, int lp,
+                                         int* __restrict__ stack, double& r2, V3& wi, double& ci) {
+  const V3 wl = sub(L, loc);
+  r2 = dot(wl, wl);
+  const double lr = sqrt(r2);
+  wi = {wl.x / lr, wl.y / lr, wl.z / lr};
+  ci = dot(n, wi);
+  if (!(ci > 0.0)) return false;
+  double full;
+  const V3 ds = unit_towards(L, loc, full);
+  const Hit hs = closest_hit(L, ds, tris, nodes, lp, stack);
+  return !(hs.tri >= 0 && !(fabs(hs.t - full) <= 1e-8 + 1e-5 * fabs(full)));
+}
+
+__global__ __launch_bounds__(kThreads) void render_global_kernel(const double* __restrict__ tris, const double* __restrict__ nodes,
+                                                                 int lp, const double* __restrict__ tri_normals,
+                                                                 const double* __restrict__ tri_rgb, Camera cam, Shade sh, Tables tb,
+                                                                 int imw, int n, int spp_side, float* __restrict__ rgb,
+                                                                 float* __restrict__ coverage, float* __restrict__ rgb_indirect) {
+  extern __shared__ int s_stack[];
+  const int i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  int* stack = s_stack + threadIdx.x;
+  const double x = (double)(i % imw), y = (double)(i / imw);
+  const double* m = cam.m;
+  const double two_s = (double)(2 * spp_side), count = (double)(spp_side * spp_side);
+  const double a2 = sh.alpha * sh.alpha;
+  const double il = sh.intensity / (double)tb.n_l, nb = (double)tb.n_b;
+  double dr = 0.0, dg = 0.0, db = 0.0, ir = 0.0, ig = 0.0, ib = 0.0;
+  int hits = 0;
+  for (int sj = 0; sj < spp_side; ++sj) {
+    const double py = y + ((double)(2 * sj + 1) / two_s - 0.5);
+    for (int si = 0; si < spp_side; ++si) {
+      const double px = x + ((double)(2 * si + 1) / two_s - 0.5);
+      const double hx = ((m[0] * px + m[1] * py) + m[2]) + m[3], hy = ((m[4] * px + m[5] * py) + m[6]) + m[7];
+      const double hz = ((m[8] * px + m[9] * py) + m[10]) + m[11], hw = ((m[12] * px + m[13] * py) + m[14]) + m[15];
+      const V3 to = {hx / hw, hy / hw, hz / hw};
+      double len;
+      const V3 d = unit_towards(cam.loc, to, len);
+      const Hit h = closest_hit(cam.loc, d, tris, nodes, lp, stack);
+      if (h.tri < 0) continue;
+      ++hits;
+      const V3 loc = {cam.loc.x + h.t * d.x, cam.loc.y + h.t * d.y, cam.loc.z + h.t * d.z};
+      V3 ng, nrm, kd;
+      surface_at(tris, h.slot, h.tri, cam.loc, d, tri_normals, tri_rgb, sh.kd, ng, nrm, kd);
+      double lo_;
+      const V3 wo = unit_towards(loc, cam.loc, lo_);
+      double co = dot(nrm, wo);
+      if (co < 0.0) { nrm = {-nrm.x, -nrm.y, -nrm.z}; co = -co; }
+      const int s = sj * spp_side + si;
+      // the direct term: the light points of this sample's set, in k order
+      const double* lpts = tb.light_pts + (long)(s % tb.n_lsets) * tb.n_l * 3;
+      double ar = 0.0, ag = 0.0, ab = 0.0;
+      for (int k = 0; k < tb.n_l; ++k) {
+        const V3 L = {sh.light.x + tb.light_radius * lpts[3 * k], sh.light.y + tb.light_radius * lpts[3 * k + 1],
+                      sh.light.z + tb.light_radius * lpts[3 * k + 2]};
+        double r2, ci;
+        V3 wi;
+        if (!lit_from(L, loc, nrm, tris, nodes, lp, stack, r2, wi, ci)) continue;
+        double spec = 0.0;
+        if (co > 0.0) {
+          const V3 hv = {wi.x + wo.x, wi.y + wo.y, wi.z + wo.z};
+          const double lh = sqrt(dot(hv, hv));
+          const V3 hh = {hv.x / lh, hv.y / lh, hv.z / lh};
+          const double nh = dot(nrm, hh), vh = dot(wo, hh);
+          const double dd = (nh * nh) * (a2 - 1.0) + 1.0;
+          const double D = a2 / (kPi * (dd * dd));
+          const double m1 = 1.0 - vh, m2 = m1 * m1, m5 = (m2 * m2) * m1;
+          const double F = sh.ks + (1.0 - sh.ks) * m5;
+          spec = (((D * smith_g1(ci, a2)) * smith_g1(co, a2)) * F) / ((4.0 * ci) * co);
+        }
+        const double e = (il / r2) * ci;
+        ar += e * (kd.x / kPi + spec);
+        ag += e * (kd.y / kPi + spec);
+        ab += e * (kd.z / kPi + spec);
+      }
+      dr += ar; dg += ag; db += ab;
+      if (tb.n_b <= 0) continue;
+      // the indirect term: one cosine-weighted bounce per point of this sample's set, in k order
+      const double cg = dot(ng, wo);
+      const V3 ngf = cg < 0.0 ? V3{-ng.x, -ng.y, -ng.z} : ng;
+      const double sg = nrm.z >= 0.0 ? 1.0 : -1.0;
+      const double fa = -1.0 / (sg + nrm.z);
+      const double fb = (nrm.x * nrm.y) * fa;
+      const V3 t1 = {1.0 + (sg * (nrm.x * nrm.x)) * fa, sg * fb, -sg * nrm.x};
+      const V3 t2 = {fb, sg + (nrm.y * nrm.y) * fa, -nrm.y};
+      const double* bpts = tb.bounce_pts + (long)(s % tb.n_bsets) * tb.n_b * 2;
+      double br = 0.0, bg = 0.0, bb = 0.0;
+      for (int k = 0; k < tb.n_b; ++k) {
+        const double dx = bpts[2 * k], dy = bpts[2 * k + 1];
+        const double qz = (1.0 - dx * dx) - dy * dy;
+        const double dz = sqrt(qz > 0.0 ? qz : 0.0);
+        const V3 wv = {(dx * t1.x + dy * t2.x) + dz * nrm.x, (dx * t1.y + dy * t2.y) + dz * nrm.y, (dx * t1.z + dy * t2.z) + dz * nrm.z};
+        const double lw = sqrt(dot(wv, wv));
+        const V3 wb = {wv.x / lw, wv.y / lw, wv.z / lw};
+        if (!(dot(ngf, wb) > 0.0)) continue;
+        const Hit h2 = closest_hit<true>(loc, wb, tris, nodes, lp, stack, h.tri);
+        if (h2.tri < 0) continue;
+        const V3 loc2 = {loc.x + h2.t * wb.x, loc.y + h2.t * wb.y, loc.z + h2.t * wb.z};
+        V3 ng2, n2, kd2;
+        surface_at(tris, h2.slot, h2.tri, loc, wb, tri_normals, tri_rgb, sh.kd, ng2, n2, kd2);
+        if (dot(n2, wb) > 0.0) n2 = {-n2.x, -n2.y, -n2.z};
+        double r2, ci;
+        V3 wi;
+        if (!lit_from(sh.light, loc2, n2, tris, nodes, lp, stack, r2, wi, ci)) continue;
+        const double e = (sh.intensity / r2) * ci;
+        br += e * (kd2.x / kPi);
+        bg += e * (kd2.y / kPi);
+        bb += e * (kd2.z / kPi);
+      }
+      ir += (kd.x * br) / nb;
+      ig += (kd.y * bg) / nb;
+      ib += (kd.z * bb) / nb;
+    }
+  }
+  rgb[(long)i * 3] = (float)((dr + ir) / count);
+  rgb[(long)i * 3 + 1] = (float)((dg + ig) / count);
+  rgb[(long)i * 3 + 2] = (float)((db + ib) / count);
+  coverage[i] = (float)((double)hits / count);
+  if (rgb_indirect) {
+    rgb_indirect[(long)i * 3] = (float)(ir / count);
+    rgb_indirect[(long)i * 3 + 1] = (float)(ig / count);
+    rgb_indirect[(long)i * 3 + 2] = (float)(ib / count);
+  }
+}
+
 // ---------------------------------------------------------------- host
 int leaves_padded(long n_tris) {
   const long l = (n_tris + kLeaf - 1) / kLeaf;
@@ -571,6 +762,33 @@ extern "C" int nlt_render_direct(const double* tris, const double* nodes, long n
   const int lp = leaves_padded(n_tris);
   hipLaunchKernelGGL(render_kernel, dim3(blocks(n, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream), tris,
                      nodes, lp, tri_normals, tri_rgb, cam, sh, imw, (int)n, spp_side, rgb_linear, coverage);
+  NLT_CHECK_LAUNCH();
+  return NLT_OK;
+}
+
+extern "C" int nlt_render_global(const double* tris, const double* nodes, long n_tris, const double* tri_normals, const double* tri_rgb,
+                                 const double* cam_host, int imh, int imw, int spp_side, double lx, double ly, double lz,
+                                 double intensity, double kd_r, double kd_g, double kd_b, double ks, double alpha, double light_radius,
+                                 const double* light_pts, int n_l, int n_lsets, const double* bounce_pts, int n_b, int n_bsets,
+                                 float* rgb_linear, float* coverage, float* rgb_indirect, void* stream) {
+  if (!tris || !nodes || !cam_host || !light_pts || !rgb_linear || !coverage) return NLT_ERR_BAD_ARG;
+  if (imh <= 0 || imw <= 0 || spp_side < 1 || spp_side > 8) return NLT_ERR_BAD_ARG;
+  if (n_l < 1 || n_l > 64 || n_b < 0 || n_b > 64 || n_lsets < 1 || n_bsets < 1) return NLT_ERR_BAD_ARG;
+  if (n_b > 0 && !bounce_pts) return NLT_ERR_BAD_ARG;
+  if (!(light_radius >= 0.0) || !isfinite(light_radius)) return NLT_ERR_BAD_ARG;
+  const int st = tris_status(n_tris);
+  if (st != NLT_OK) return st;
+  const long n = (long)imh * imw;
+  if (n * 3 >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  if ((long)n_lsets * n_l * 3 >= (1l << 31) || (long)n_bsets * (n_b > 0 ? n_b : 1) * 2 >= (1l << 31)) return NLT_ERR_UNSUPPORTED;
+  Camera cam;
+  for (int k = 0; k < 16; ++k) cam.m[k] = cam_host[k];
+  cam.loc = {cam_host[16], cam_host[17], cam_host[18]};
+  const Shade sh = {V3{lx, ly, lz}, V3{kd_r, kd_g, kd_b}, intensity, ks, alpha};
+  const Tables tb = {light_pts, bounce_pts, light_radius, n_l, n_lsets, n_b, n_bsets};
+  const int lp = leaves_padded(n_tris);
+  hipLaunchKernelGGL(render_global_kernel, dim3(blocks(n, kThreads)), dim3(kThreads), stack_bytes(lp), static_cast<hipStream_t>(stream),
+                     tris, nodes, lp, tri_normals, tri_rgb, cam, sh, tb, imw, (int)n, spp_side, rgb_linear, coverage, rgb_indirect);
   NLT_CHECK_LAUNCH();
   return NLT_OK;
 }

@@ -1,9 +1,10 @@
 """python -m nlt_amd.data_gen.capture_main: a mesh in, a whole capture out -- every `trainvali_*` sample of cameras x lights with
-its direct-lighting render (data_gen/shade.py), a few `test_*` samples at held-out rig positions (these carry rgb_camspc too: the
+its render (data_gen/shade.py: direct lighting by a point light, or with --bounces / --light_samples / --light_size one diffuse
+bounce and a spherical light), a few `test_*` samples at held-out rig positions (these carry rgb_camspc too: the
 truth can be rendered), the neighbour tables, the diffuse bases and the index `datasets.nlt.load_store` reads.  No Blender.
 
     python -m nlt_amd.data_gen.capture_main --mesh bunny.ply --uv_unwrap unwrap.pickle --outroot out/bunny --n_cams 8 --n_lights 12 \\
-        --n_test 2 --imh 512 --uvs 1024 --spp 16
+        --n_test 2 --imh 512 --uvs 1024 --spp 16 [--bounces 8 --light_samples 4 --light_size 0.1]
 """
 import math
 from argparse import ArgumentParser
@@ -42,11 +43,19 @@ def parse_args(argv=None):
     p.add_argument('--flat', action='store_true', help="shade on the geometric normal, not on vertex normals")
     p.add_argument('--intensity', type=float, default=1.0)
     p.add_argument('--exposure', type=float, default=None, help="default: `default_exposure`")
+    p.add_argument('--bounces', type=int, default=0, help="bounce rays per sample (one diffuse bounce each), 0 to 64; 0: direct light only")
+    p.add_argument('--light_samples', type=int, default=1, help="points of the light's sphere per sample, 1 to 64")
+    p.add_argument('--light_size', type=float, default=None, help="radius of the lights' sphere, written to the light JSONs as `size` "
+                   "(default: the JSONs' own size, used only with --bounces or --light_samples)")
     p.add_argument('--device', default='cuda')
     args = p.parse_args(argv)
     args.kd = tuple(float(x) for x in args.kd.split(','))
     if len(args.kd) != 3:
         p.error("--kd takes r,g,b")
+    if not 0 <= args.bounces <= 64 or not 1 <= args.light_samples <= 64:
+        p.error("--bounces takes 0 to 64, --light_samples 1 to 64")
+    if args.light_size is not None and not (args.light_size >= 0.0 and math.isfinite(args.light_size)):
+        p.error("--light_size takes a finite radius >= 0")
     try:
         spp_side(args.spp)
     except ValueError as e:
@@ -56,7 +65,8 @@ def parse_args(argv=None):
 
 def default_exposure(light_distance, intensity=1.0):
     """One number for a whole capture: a white Lambert surface (kd = 1) facing a light `light_distance` away has linear radiance
-    intensity / (pi * distance^2); the exposure maps it to 0.8."""
+    intensity / (pi * distance^2); the exposure maps it to 0.8.  A rule of the direct light alone: the bounce light and the
+    light's size of a global render (--bounces, --light_samples, --light_size) do not enter it."""
     return 0.8 * math.pi * float(light_distance) ** 2 / float(intensity)
 
 
@@ -75,11 +85,12 @@ def neighbor_tables(cams, lights, test_cams, test_lights, device='cuda'):
 
 
 def write_capture(mesh, unwrap, outroot, cams, lights, test_pairs=(), imh=512, uvs=1024, spp=16, material=None, exposure=None,
-                  intensity=1.0, rig=None, workers=None):
+                  intensity=1.0, rig=None, workers=None, bounces=0, light_samples=1, light_size=None):
     """Writes `trainvali_%09d_{cam}_{light}` for the full product cams x lights and `test_%09d_{cam}_{light}` for every
     (cam, light) of test_pairs, then `postproc.postprocess` and `<outroot>.capture.json` (exposure, intensity, material, rig)
     beside the index.  unwrap: the {face: rows} table or its dense form.  exposure = None: `default_exposure` at the mean distance
-    of the lights from the mesh box's centre.  Returns (the index `postprocess` wrote, the capture.json dict)."""
+    of the lights from the mesh box's centre.  bounces, light_samples, light_size: `shade.render_view`'s (the defaults are its
+    direct-lighting render) and recorded in capture.json.  Returns (the index `postprocess` wrote, the capture.json dict)."""
     material = material or Material()
     if isinstance(unwrap, dict) and 'uv' not in unwrap:
         unwrap = dense_unwrap(unwrap)
@@ -93,16 +104,17 @@ def write_capture(mesh, unwrap, outroot, cams, lights, test_pairs=(), imh=512, u
     n = 0
     for cam in cams:
         for light in lights:
-            sample = render_view(mesh, unwrap, cam, light, imh, uvs, spp, material, exposure, intensity)
+            sample = render_view(mesh, unwrap, cam, light, imh, uvs, spp, material, exposure, intensity, bounces, light_samples, light_size)
             write_sample(join(outroot, 'trainvali_%09d_%s_%s' % (n, cam['name'], light['name'])), sample, cam, light, nn, workers=workers)
             n += 1
     for t, (cam, light) in enumerate(test_pairs):
-        sample = render_view(mesh, unwrap, cam, light, imh, uvs, spp, material, exposure, intensity)
+        sample = render_view(mesh, unwrap, cam, light, imh, uvs, spp, material, exposure, intensity, bounces, light_samples, light_size)
         write_sample(join(outroot, 'test_%09d_%s_%s' % (t, cam['name'], light['name'])), sample, cam, light, nn, workers=workers)
     index = postproc.postprocess(outroot, device=mesh.device, workers=workers)
     info = dict(exposure=float(exposure), intensity=float(intensity), spp=int(spp), imh=int(imh), uvs=int(uvs), material=material.to_json(),
                 rig=rig, cams=[c['name'] for c in cams], lights=[l['name'] for l in lights],
-                test=[[c['name'], l['name']] for c, l in test_pairs])
+                test=[[c['name'], l['name']] for c, l in test_pairs], bounces=int(bounces), light_samples=int(light_samples),
+                light_size=None if light_size is None else float(light_size))
     dump_json(info, outroot.rstrip('/') + '.capture.json')
     return index, info
 
@@ -125,6 +137,9 @@ def build_rig(args, centre, half_diagonal):
         lights, rig['lights_dir'] = _load_dir(args.lights_dir), args.lights_dir
     test_cams, test_lights = light_stage(args.n_test, args.n_test, radius, centre, hemisphere=args.hemisphere, cam_prefix='VC',
                                          light_prefix='VL', phase=1.0) if args.n_test > 0 else ([], [])
+    if args.light_size is not None:                      # the sphere's radius, where Blender keeps it: in every light's JSON
+        lights = [dict(l, size=float(args.light_size)) for l in lights]
+        test_lights = [dict(l, size=float(args.light_size)) for l in test_lights]
     return cams, lights, list(zip(test_cams, test_lights)), rig
 
 
@@ -140,7 +155,7 @@ def main(argv=None):
     cams, lights, test_pairs, rig = build_rig(args, *mesh_box(mesh))
     material = Material(kd=args.kd, ks=args.ks, roughness=args.roughness, smooth=not args.flat)
     return write_capture(mesh, unwrap, args.outroot, cams, lights, test_pairs, args.imh, args.uvs, args.spp, material, args.exposure,
-                         args.intensity, rig)
+                         args.intensity, rig, bounces=args.bounces, light_samples=args.light_samples, light_size=args.light_size)
 
 
 if __name__ == '__main__':

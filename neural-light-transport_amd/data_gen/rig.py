@@ -38,8 +38,8 @@ def light_stage(n_cams, n_lights, radius, target, focal_length=50.0, sensor=(32.
     sensor_height, clip_start, clip_end / name, position, size -- `n_cams` cameras at `radius` from `target` looking at it, and
     `n_lights` lights at `light_radius` (default: `radius`), both on Fibonacci spheres (the lights' azimuths turned by half a
     golden angle so that a light never sits in a camera).  hemisphere: the upper (z > target.z) half only.  phase turns the whole
-    rig about z: another phase gives held-out positions.  Names are prefix + a zero-padded index.  `light_size` is recorded only:
-    the renderer's lights are points."""
+    rig about z: another phase gives held-out positions.  Names are prefix + a zero-padded index.  `light_size` is the radius Blender gives a point lamp: nlt_render_direct's
+    lights are points and ignore it, `shade.render_global` samples a sphere of that radius."""
     target = np.asarray(target, np.float64).reshape(3)
     light_radius = radius if light_radius is None else light_radius
     cams, lights = [], []
