@@ -1344,6 +1344,86 @@ int nlt_render_global(const double* tris, const double* nodes, long n_tris, cons
                       int n_l, int n_lsets, const double* bounce_pts, int n_b, int n_bsets, float* rgb_linear, float* coverage,
                       float* rgb_indirect, void* stream);
 
+/* ======================= UV unwrap (csrc/unwrap.hip) =======================
+ * Smart-projection unwrapping of one mesh: projection groups by a greedy rule over the face normals, islands of faces that
+ * share an edge and a group, one planar projection per group, exact island boxes, and the loop UVs once the host has packed
+ * the boxes (data_gen/unwrap.py: pack_islands).
+ *   replaces: xm.blender.object.smart_uv_unwrap (third_party/xiuminglib/xiuminglib/blender/object.py:835-893), that is
+ *             bpy.ops.uv.smart_project inside Blender, as data_gen/uv_unwrap.py calls it.  Blender's greedy rule is restated
+ *             from its published script; parity with Blender is not claimed.
+ * Arithmetic (tests/unwrap_ref.py restates every stage operation by operation, and every output is held to it bit for bit):
+ *   float64 throughout, only + - * / sqrt and comparisons, no fused operation; a . b = (ax bx + ay by) + az bz;
+ *   a x b = (ay bz - az by, az bx - ax bz, ax by - ay bx); no sine or cosine is evaluated (the two cosines of the angle limit
+ *   come from the caller); no float atomics -- the only atomics are integer min / max, whose result no arrival order changes,
+ *   and the one float sum is a fixed tree; equal inputs give equal bits; every output buffer is exactly the stated size and
+ *   every element of it is written.
+ * The mesh: verts [n_verts, 3] float64; loop_verts [n_loops] int32, the faces' vertex indices laid end to end; face_off
+ * [n_faces + 1] int32 with face_off[0] = 0, non-decreasing, face_off[n_faces] = n_loops (trusted: the caller checks it).  A
+ * polygon is the fan (0, i, i + 1).  Per-face vectors are stored by component: n and unit are [3, n_faces].
+ * Limits: a count <= 0 is NLT_ERR_BAD_ARG, 2^31 or more NLT_ERR_UNSUPPORTED (the size query answers -1 for both); a NULL
+ * pointer or a scratch capacity below the query's answer is NLT_ERR_BAD_ARG.  Nothing is launched after a refusal.
+ *
+ * Scratch of nlt_unwrap_seed / _gather / _farthest: the tree's block sums (3 doubles per block of 256 faces, and per block of
+ * 256 of those, down to one) and one (value, index) candidate per block of 256 faces; 8-byte aligned, no state between calls. */
+long nlt_unwrap_workspace_bytes(long n_faces);
+/* a. Face frames.  n = the sum over the fan, in order and starting from +0, of (v_i - v_0) x (v_{i+1} - v_0);
+ * len = sqrt((nx nx + ny ny) + nz nz); area = 0.5 len; unit = n / len per component.  A face with fewer than three loops, a
+ * vertex index outside 0 .. n_verts - 1 or a len that is zero or not finite is DEGENERATE: ok = 0, unit = 0, area = 0 (n: as
+ * summed; 0 for a bad index or a short face).  n, unit [3, n_faces] float64, area [n_faces] float64, ok [n_faces] uint8. */
+int nlt_unwrap_frames(const double* verts, long n_verts, const int* loop_verts, long n_loops, const int* face_off, long n_faces,
+                      double* n, double* unit, double* area, unsigned char* ok, void* stream);
+/* b. Projection vectors, one round per vector; the caller reads `pair` (2 x int64 on the device: a face index or -1, and the
+ * bits of a float64) once per round.
+ * nlt_unwrap_seed: remaining [n_faces] uint8 = ok; pair = the ok face of largest area (ties to the lowest index) and its area.
+ * nlt_unwrap_gather: every face with remaining != 0 that is `seed` itself or has unit . unit_seed > cos_half leaves `remaining`
+ *   (its byte is cleared) and contributes unit * ((area * aw) + omw) per component; every other face and the padding
+ *   contribute +0.0.  The sum is a FIXED TREE: faces in index order in blocks of 256; inside a block x[i] += x[i + s] for
+ *   s = 128, 64 .. 1; the block results are reduced by the same rule, level after level, until one value is left.
+ *   vec [3] (device) = sum / sqrt(sum . sum) per component.  seed outside 0 .. n_faces - 1: NLT_ERR_BAD_ARG.
+ * nlt_unwrap_farthest: with d = unit . vec, best [n_faces] = d when first != 0, else (d > best ? d : best), for every ok face
+ *   (0 for a degenerate one); pair = the face with remaining != 0 of smallest best (ties to the lowest index) and that value.
+ *   The caller stops when the index is -1 or the value is >= cos(angle limit); else that face seeds the next round. */
+int nlt_unwrap_seed(const double* area, const unsigned char* ok, long n_faces, unsigned char* remaining, void* ws, long ws_bytes,
+                    long* pair, void* stream);
+int nlt_unwrap_gather(const double* unit, const double* area, unsigned char* remaining, long n_faces, long seed, double cos_half,
+                      double aw, double omw, void* ws, long ws_bytes, double* vec, void* stream);
+int nlt_unwrap_farthest(const double* unit, const unsigned char* ok, const unsigned char* remaining, double* best, long n_faces,
+                        const double* vec, int first, void* ws, long ws_bytes, long* pair, void* stream);
+/* c. group [n_faces] int32 = the k of largest unit . vectors[k] (vectors [n_vectors, 3] float64, device), ties to the lowest k;
+ * -1 for a degenerate face. */
+int nlt_unwrap_assign(const double* unit, const unsigned char* ok, long n_faces, const double* vectors, int n_vectors, int* group,
+                      void* stream);
+/* d. Islands: the connected components of non-degenerate faces that share an edge (an unordered pair of vertex INDICES; nothing
+ * is welded) and a group.  Step 1, nlt_unwrap_edge_keys: per loop, keys [n_loops] int64 = min(a, b) * n_verts + max(a, b) for
+ * the edge from the loop's vertex a to the vertex b of the face's next loop (the last loop's next is the first), and loop_face
+ * [n_loops] int32, the loop's face.  Step 2 is the caller's: a STABLE ascending sort of the keys -> keys_sorted and order
+ * (int64 [n_loops], a permutation; it is trusted).  Step 3, nlt_unwrap_islands_init: label [n_faces] int32 = the face's own
+ * index, -1 for a face whose group is < 0.  Step 4, nlt_unwrap_islands_round, repeated until it reports no change: neighbouring
+ * equal keys link their two faces when both groups are equal and >= 0 (a run of three or more keys links consecutive entries);
+ * of two linked faces' roots the larger is hooked under the smaller (integer atomicMin), then every face is pointed at its root.
+ * changed [1] int32 (device) is cleared first and set when anything was hooked; the caller reads it once per round.  On
+ * convergence label[f] is the smallest face index of f's component, under any schedule. */
+int nlt_unwrap_edge_keys(const int* loop_verts, long n_loops, const int* face_off, long n_faces, long n_verts, long* keys,
+                         int* loop_face, void* stream);
+int nlt_unwrap_islands_init(const int* group, long n_faces, int* label, void* stream);
+int nlt_unwrap_islands_round(const long* keys_sorted, const long* order, const int* loop_face, long n_loops, const int* group,
+                             long n_faces, int* label, int* changed, void* stream);
+/* e. Island boxes.  island [n_faces] int32: the face's island number 0 .. n_islands - 1 (the caller numbers the distinct labels
+ * in ascending order), -1 for a degenerate face.  frames [n_vectors, 2, 3] float64: per group the caller's orthonormal U, V with
+ * U x V = the group's vector.  Per loop of a face with an island: pu = (p . U) + 0.0, pv = (p . V) + 0.0 (-0.0 becomes +0.0);
+ * every other loop gets (0, 0).  puv [n_loops, 2]; boxes [n_islands, 4] = the exact (min pu, min pv, max pu, max pv) over the
+ * island's loops, through order-preserving 64-bit integer keys and integer atomic min / max in the box buffer itself.  An island
+ * number outside the range or a group outside 0 .. n_vectors - 1 is treated as -1. */
+int nlt_unwrap_boxes(const double* verts, const int* loop_verts, const int* loop_face, long n_loops, const int* group,
+                     const int* island, long n_faces, const double* frames, int n_vectors, double* puv, double* boxes, long n_islands,
+                     void* stream);
+/* g. UVs into the dense table uv [n_faces, vmax, 2] float64 of data_gen/render.py's calc_bidir_mapping.  rot [n_islands] uint8,
+ * offsets [n_islands, 2] float64 and scale are pack_islands' answer.  Slot (f, j) with j < the face's loop count and an island:
+ * local = (pu - umin, pv - vmin), or for rot != 0 the proper quarter turn (pv - vmin, umax - pu); uv = local * scale + offset (a
+ * multiply, then an add).  Every other slot: (0, 0).  vmax <= 0: NLT_ERR_BAD_ARG. */
+int nlt_unwrap_uv(const double* puv, long n_loops, const int* face_off, const int* island, long n_faces, const double* boxes,
+                  const unsigned char* rot, const double* offsets, long n_islands, double scale, int vmax, double* uv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ C ABI.  There is NO CPU or torch fallback: if the library is missing or a call r
 non-zero status this raises.
 """
 import ctypes
+import struct as _struct
 import threading
 import os
 
@@ -229,6 +230,18 @@ SIGNATURES = {
     'nlt_render_direct': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_int, _c_int, _c_int] + [_c_double] * 9 + [_vp, _vp, _vp]),
     'nlt_render_global': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _vp, _c_int, _c_int, _c_int] + [_c_double] * 10 +
                           [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _vp, _vp, _vp]),
+    # UV unwrap (csrc/unwrap.hip)
+    'nlt_unwrap_workspace_bytes': (_c_long, [_c_long]),
+    'nlt_unwrap_frames': (_c_int, [_vp, _c_long, _vp, _c_long, _vp, _c_long, _vp, _vp, _vp, _vp, _vp]),
+    'nlt_unwrap_seed': (_c_int, [_vp, _vp, _c_long, _vp, _vp, _c_long, _vp, _vp]),
+    'nlt_unwrap_gather': (_c_int, [_vp, _vp, _vp, _c_long, _c_long] + [_c_double] * 3 + [_vp, _c_long, _vp, _vp]),
+    'nlt_unwrap_farthest': (_c_int, [_vp, _vp, _vp, _vp, _c_long, _vp, _c_int, _vp, _c_long, _vp, _vp]),
+    'nlt_unwrap_assign': (_c_int, [_vp, _vp, _c_long, _vp, _c_int, _vp, _vp]),
+    'nlt_unwrap_edge_keys': (_c_int, [_vp, _c_long, _vp, _c_long, _c_long, _vp, _vp, _vp]),
+    'nlt_unwrap_islands_init': (_c_int, [_vp, _c_long, _vp, _vp]),
+    'nlt_unwrap_islands_round': (_c_int, [_vp, _vp, _vp, _c_long, _vp, _c_long, _vp, _vp, _vp]),
+    'nlt_unwrap_boxes': (_c_int, [_vp, _vp, _vp, _c_long, _vp, _vp, _c_long, _vp, _c_int, _vp, _vp, _c_long, _vp]),
+    'nlt_unwrap_uv': (_c_int, [_vp, _c_long, _vp, _vp, _c_long, _vp, _vp, _vp, _c_long, _c_double, _c_int, _vp, _vp]),
 }
 
 _real = None
@@ -1769,6 +1782,132 @@ def render_global(tris, nodes, n_tris, tri_normals, tri_rgb, cam_mat_inv, cam_lo
           _tptr(light_pts, torch.float64, 'light_pts'), n_l, n_lsets, _tptr(bounce_pts if n_b > 0 else None, torch.float64, 'bounce_pts'),
           n_b, n_bsets, rgb.data_ptr(), coverage.data_ptr(), None if indirect is None else indirect.data_ptr())
     return rgb, coverage, indirect
+
+
+# ---------------------------------------------------------------- UV unwrap (csrc/unwrap.hip)
+UNWRAP_MAX_ISLAND_ROUNDS = 256
+
+
+def _unwrap_mesh_args(loop_verts, face_off):
+    return _tptr(loop_verts, torch.int32, 'loop_verts'), loop_verts.numel(), _tptr(face_off, torch.int32, 'face_off'), face_off.numel() - 1
+
+
+def _no_tape(what):
+    if getattr(_tls, 'tape', None) is not None:
+        raise NLTError("%s reads a device value between its launches: it cannot be recorded on a launch tape" % what)
+
+
+def unwrap_frames(verts, loop_verts, face_off):
+    """verts [V,3] float64, loop_verts [L] int32, face_off [F+1] int32 (include/nlt_hip.h: nlt_unwrap_frames) ->
+    (n, unit float64 [3,F], by component; area float64 [F]; ok uint8 [F])."""
+    if verts.dim() != 2 or verts.shape[1] != 3 or loop_verts.dim() != 1 or face_off.dim() != 1:
+        raise NLTError("unwrap_frames: verts [V,3], loop_verts [L], face_off [F+1] expected")
+    lv, n_loops, fo, f = _unwrap_mesh_args(loop_verts, face_off)
+    dev = verts.device
+    n = torch.empty((3, max(f, 0)), device=dev, dtype=torch.float64)
+    unit = torch.empty((3, max(f, 0)), device=dev, dtype=torch.float64)
+    area = torch.empty(max(f, 0), device=dev, dtype=torch.float64)
+    ok = torch.empty(max(f, 0), device=dev, dtype=torch.uint8)
+    _call('nlt_unwrap_frames', _tptr(verts, torch.float64, 'verts'), verts.shape[0], lv, n_loops, fo, f, n.data_ptr(), unit.data_ptr(),
+          area.data_ptr(), ok.data_ptr())
+    return n, unit, area, ok
+
+
+def _unwrap_pair(pair):
+    idx, bits = (int(x) for x in pair.cpu())                        # (one read per round: the host decides whether to go on)
+    return idx, _struct.unpack('<d', _struct.pack('<q', bits))[0]
+
+
+def unwrap_vectors(unit, area, ok, cos_half, cos_full, aw, omw, max_groups=256):
+    """The greedy projection vectors of include/nlt_hip.h (nlt_unwrap_seed, then nlt_unwrap_gather + nlt_unwrap_farthest per
+    round) -> (vectors float64 [K,3], a view of a [max_groups,3] buffer; the seeds, K face indices).  ValueError: no face has
+    an area, or more than max_groups vectors would be needed."""
+    _no_tape('unwrap_vectors')
+    f, dev = area.numel(), area.device
+    need = _size('nlt_unwrap_workspace_bytes', f, what='1 .. 2^31 - 1 faces')
+    ws = _workspace(_per_stream('unwrap'), dev, (need + 3) // 4)
+    ws_bytes = ws.numel() * 4
+    remaining = torch.empty(f, device=dev, dtype=torch.uint8)
+    best = torch.empty(f, device=dev, dtype=torch.float64)
+    vectors = torch.empty((int(max_groups), 3), device=dev, dtype=torch.float64)
+    pair = torch.empty(2, device=dev, dtype=torch.int64)
+    up, ap, okp = _tptr(unit, torch.float64, 'unit'), _tptr(area, torch.float64, 'area'), _tptr(ok, torch.uint8, 'ok')
+    if unit.numel() != 3 * f or ok.numel() != f:
+        raise NLTError("unwrap_vectors: unit %s, ok %s do not match %d faces" % (tuple(unit.shape), tuple(ok.shape), f))
+    _call('nlt_unwrap_seed', ap, okp, f, remaining.data_ptr(), ws.data_ptr(), ws_bytes, pair.data_ptr())
+    seed, _ = _unwrap_pair(pair)
+    if seed < 0:
+        raise ValueError("the mesh has no face with a finite, non-zero area: nothing to unwrap")
+    seeds = []
+    while True:
+        k = len(seeds)
+        if k >= max_groups:
+            raise ValueError("more than max_groups = %d projection vectors are needed at this angle limit" % max_groups)
+        vec = vectors.data_ptr() + 24 * k
+        _call('nlt_unwrap_gather', up, ap, remaining.data_ptr(), f, seed, float(cos_half), float(aw), float(omw), ws.data_ptr(), ws_bytes, vec)
+        _call('nlt_unwrap_farthest', up, okp, remaining.data_ptr(), best.data_ptr(), f, vec, 1 if k == 0 else 0, ws.data_ptr(), ws_bytes,
+              pair.data_ptr())
+        seeds.append(seed)
+        seed, value = _unwrap_pair(pair)
+        if seed < 0 or value >= cos_full:
+            return vectors[:len(seeds)], seeds
+
+
+def unwrap_assign(unit, ok, vectors):
+    """unit [3,F], ok [F], vectors [K,3] -> group int32 [F] (nlt_unwrap_assign)."""
+    f = ok.numel()
+    group = torch.empty(f, device=ok.device, dtype=torch.int32)
+    _call('nlt_unwrap_assign', _tptr(unit, torch.float64, 'unit'), _tptr(ok, torch.uint8, 'ok'), f,
+          _tptr(vectors, torch.float64, 'vectors'), vectors.shape[0], group.data_ptr())
+    return group
+
+
+def unwrap_islands(loop_verts, face_off, n_verts, group, max_rounds=UNWRAP_MAX_ISLAND_ROUNDS):
+    """Edge keys, a stable torch.sort (plumbing, as in `bvh_build`), then hooking rounds until the device flag reports no change
+    -> (label int32 [F]: the smallest face index of the face's island, -1 degenerate; loop_face int32 [L]; the rounds run).
+    More than max_rounds rounds raise NLTError."""
+    _no_tape('unwrap_islands')
+    lv, n_loops, fo, f = _unwrap_mesh_args(loop_verts, face_off)
+    dev = loop_verts.device
+    keys = torch.empty(max(n_loops, 0), device=dev, dtype=torch.int64)
+    loop_face = torch.empty(max(n_loops, 0), device=dev, dtype=torch.int32)
+    label = torch.empty(max(f, 0), device=dev, dtype=torch.int32)
+    changed = torch.empty(1, device=dev, dtype=torch.int32)
+    gp = _tptr(group, torch.int32, 'group')
+    _call('nlt_unwrap_edge_keys', lv, n_loops, fo, f, int(n_verts), keys.data_ptr(), loop_face.data_ptr())
+    keys_sorted, order = torch.sort(keys, stable=True)
+    _call('nlt_unwrap_islands_init', gp, f, label.data_ptr())
+    for rounds in range(1, int(max_rounds) + 1):
+        _call('nlt_unwrap_islands_round', _tptr(keys_sorted, torch.int64, 'keys_sorted'), _tptr(order, torch.int64, 'order'),
+              loop_face.data_ptr(), n_loops, gp, f, label.data_ptr(), changed.data_ptr())
+        if int(changed.cpu()[0]) == 0:
+            return label, loop_face, rounds
+    raise NLTError("unwrap_islands: the labels still changed after %d rounds" % max_rounds)
+
+
+def unwrap_boxes(verts, loop_verts, loop_face, group, island, frames, n_islands):
+    """frames [K,2,3] float64, island int32 [F] -> (puv float64 [L,2], boxes float64 [n_islands,4]) (nlt_unwrap_boxes)."""
+    n_loops, f, dev = loop_verts.numel(), group.numel(), verts.device
+    if frames.dim() != 3 or tuple(frames.shape[1:]) != (2, 3) or island.numel() != f or loop_face.numel() != n_loops:
+        raise NLTError("unwrap_boxes: frames [K,2,3], island [F], loop_face [L] expected")
+    puv = torch.empty((n_loops, 2), device=dev, dtype=torch.float64)
+    boxes = torch.empty((max(int(n_islands), 0), 4), device=dev, dtype=torch.float64)
+    _call('nlt_unwrap_boxes', _tptr(verts, torch.float64, 'verts'), _tptr(loop_verts, torch.int32, 'loop_verts'),
+          _tptr(loop_face, torch.int32, 'loop_face'), n_loops, _tptr(group, torch.int32, 'group'), _tptr(island, torch.int32, 'island'), f,
+          _tptr(frames, torch.float64, 'frames'), frames.shape[0], puv.data_ptr(), boxes.data_ptr(), int(n_islands))
+    return puv, boxes
+
+
+def unwrap_uv(puv, face_off, island, boxes, rot, offsets, scale, vmax):
+    """puv [L,2], boxes [I,4], rot uint8 [I], offsets [I,2] -> the dense uv float64 [F,vmax,2] (nlt_unwrap_uv)."""
+    f, n_islands = face_off.numel() - 1, boxes.shape[0]
+    if rot.numel() != n_islands or offsets.numel() != 2 * n_islands or island.numel() != f:
+        raise NLTError("unwrap_uv: rot [I], offsets [I,2] and island [F] must match boxes [I,4] and face_off [F+1]")
+    uv = torch.empty((max(f, 0), int(vmax), 2), device=puv.device, dtype=torch.float64)
+    _call('nlt_unwrap_uv', _tptr(puv, torch.float64, 'puv'), puv.shape[0], _tptr(face_off, torch.int32, 'face_off'),
+          _tptr(island, torch.int32, 'island'), f, _tptr(boxes, torch.float64, 'boxes'), _tptr(rot, torch.uint8, 'rot'),
+          _tptr(offsets, torch.float64, 'offsets'), n_islands, float(scale), int(vmax), uv.data_ptr())
+    return uv
 
 
 # ---------------------------------------------------------------- texel-buffer assembly

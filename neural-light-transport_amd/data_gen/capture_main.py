@@ -5,6 +5,9 @@ truth can be rendered), the neighbour tables, the diffuse bases and the index `d
 
     python -m nlt_amd.data_gen.capture_main --mesh bunny.ply --uv_unwrap unwrap.pickle --outroot out/bunny --n_cams 8 --n_lights 12 \\
         --n_test 2 --imh 512 --uvs 1024 --spp 16 [--bounces 8 --light_samples 4 --light_size 0.1]
+
+--uv_unwrap smart [--angle_limit 89 --area_weight 1 --margin 0.002] unwraps the mesh here (data_gen/unwrap.py), writes the
+table to <outroot>.uv.pickle and records the unwrap in <outroot>.capture.json.
 """
 import math
 from argparse import ArgumentParser
@@ -15,17 +18,20 @@ import numpy as np
 
 from . import get_neighbors as _nn
 from . import postproc
-from .mesh import Mesh, dense_unwrap, unwrap_from_obj
+from .mesh import Mesh, dense_unwrap
 from .render import write_sample
 from .rig import light_stage
 from .shade import Material, render_view, spp_side
+from .unwrap import add_unwrap_flags, check_unwrap_flags, load_or_unwrap, write_unwrap
 from .util import dump_json, load_json
 
 
 def parse_args(argv=None):
     p = ArgumentParser(description=__doc__.split('\n')[0])
     p.add_argument('--mesh', required=True, help="the object's mesh, .ply or .obj, in world coordinates")
-    p.add_argument('--uv_unwrap', required=True, help="the cached .pickle of data_gen/uv_unwrap.py, or an .obj whose `vt` are the unwrap")
+    p.add_argument('--uv_unwrap', required=True, help="the cached .pickle of data_gen/uv_unwrap.py, an .obj whose `vt` are the unwrap, or `smart`: "
+                   "unwrap the mesh here")
+    add_unwrap_flags(p)
     p.add_argument('--outroot', required=True, help="the capture's directory; the index goes to <outroot>.json")
     p.add_argument('--n_cams', type=int, default=8)
     p.add_argument('--n_lights', type=int, default=8)
@@ -56,6 +62,7 @@ def parse_args(argv=None):
         p.error("--bounces takes 0 to 64, --light_samples 1 to 64")
     if args.light_size is not None and not (args.light_size >= 0.0 and math.isfinite(args.light_size)):
         p.error("--light_size takes a finite radius >= 0")
+    check_unwrap_flags(p, args)
     try:
         spp_side(args.spp)
     except ValueError as e:
@@ -85,12 +92,13 @@ def neighbor_tables(cams, lights, test_cams, test_lights, device='cuda'):
 
 
 def write_capture(mesh, unwrap, outroot, cams, lights, test_pairs=(), imh=512, uvs=1024, spp=16, material=None, exposure=None,
-                  intensity=1.0, rig=None, workers=None, bounces=0, light_samples=1, light_size=None):
+                  intensity=1.0, rig=None, workers=None, bounces=0, light_samples=1, light_size=None, unwrap_record=None):
     """Writes `trainvali_%09d_{cam}_{light}` for the full product cams x lights and `test_%09d_{cam}_{light}` for every
     (cam, light) of test_pairs, then `postproc.postprocess` and `<outroot>.capture.json` (exposure, intensity, material, rig)
     beside the index.  unwrap: the {face: rows} table or its dense form.  exposure = None: `default_exposure` at the mean distance
     of the lights from the mesh box's centre.  bounces, light_samples, light_size: `shade.render_view`'s (the defaults are its
-    direct-lighting render) and recorded in capture.json.  Returns (the index `postprocess` wrote, the capture.json dict)."""
+    direct-lighting render) and recorded in capture.json.  unwrap_record: `Unwrap.record()` when the unwrap was computed for this
+    capture; capture.json then carries it as `unwrap` (else it has no such entry).  Returns (the index `postprocess` wrote, the capture.json dict)."""
     material = material or Material()
     if isinstance(unwrap, dict) and 'uv' not in unwrap:
         unwrap = dense_unwrap(unwrap)
@@ -115,6 +123,8 @@ def write_capture(mesh, unwrap, outroot, cams, lights, test_pairs=(), imh=512, u
                 rig=rig, cams=[c['name'] for c in cams], lights=[l['name'] for l in lights],
                 test=[[c['name'], l['name']] for c, l in test_pairs], bounces=int(bounces), light_samples=int(light_samples),
                 light_size=None if light_size is None else float(light_size))
+    if unwrap_record is not None:
+        info['unwrap'] = unwrap_record
     dump_json(info, outroot.rstrip('/') + '.capture.json')
     return index, info
 
@@ -146,16 +156,14 @@ def build_rig(args, centre, half_diagonal):
 def main(argv=None):
     args = parse_args(argv)
     mesh = Mesh.load(args.mesh, device=args.device)
-    if args.uv_unwrap.lower().endswith('.obj'):
-        unwrap = unwrap_from_obj(Mesh.load(args.uv_unwrap, device=None))
-    else:
-        import pickle
-        with open(args.uv_unwrap, 'rb') as h:
-            unwrap = pickle.load(h)
+    unwrap, computed = load_or_unwrap(args, mesh)
+    if computed is not None:
+        write_unwrap(args.outroot.rstrip('/') + '.uv.pickle', computed.table())
     cams, lights, test_pairs, rig = build_rig(args, *mesh_box(mesh))
     material = Material(kd=args.kd, ks=args.ks, roughness=args.roughness, smooth=not args.flat)
     return write_capture(mesh, unwrap, args.outroot, cams, lights, test_pairs, args.imh, args.uvs, args.spp, material, args.exposure,
-                         args.intensity, rig, bounces=args.bounces, light_samples=args.light_samples, light_size=args.light_size)
+                         args.intensity, rig, bounces=args.bounces, light_samples=args.light_samples, light_size=args.light_size,
+                         unwrap_record=None if computed is None else computed.record())
 
 
 if __name__ == '__main__':

@@ -202,11 +202,12 @@ def corner_normals(mesh):
 
 def unwrap_from_obj(mesh):
     """The {face: [[loop, vert, u, v], ...]} table of data_gen/uv_unwrap.py:59-63 from the UVs the mesh file itself carries
-    (`Mesh.load` / `load_mesh` of an .obj with `vt`).  No unwrapping is done here: a mesh without UVs raises."""
+    (`Mesh.load` / `load_mesh` of an .obj with `vt`).  No unwrapping is done here: a mesh without UVs raises (data_gen/unwrap.py
+    unwraps one)."""
     faces, uvs = (mesh['faces'], mesh['loop_uvs']) if isinstance(mesh, dict) else (mesh.faces, mesh.loop_uvs)
     if uvs is None:
-        raise ValueError("the mesh carries no UVs (no `vt` in the file) and smart-UV unwrapping is out of scope: unwrap it in "
-                         "Blender (data_gen/uv_unwrap.py) and pass that pickle")
+        raise ValueError("the mesh carries no UVs (no `vt` in the file): unwrap it with data_gen.unwrap.smart_unwrap "
+                         "(`--uv_unwrap smart`, or python -m nlt_amd.data_gen.unwrap_main) and pass that table")
     table, loop = {}, 0
     for fi, (f, uv) in enumerate(zip(faces, uvs)):
         table[fi] = [[loop + k, int(vi), float(uv[k, 0]), float(uv[k, 1])] for k, vi in enumerate(f)]
